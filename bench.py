@@ -17,16 +17,36 @@ as `strong_scaling`.
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks
 itself (one fresh child process per GPU, before anything here touches HIP) and
 relays rank 0's JSON line; under torch.distributed.run the ranks are taken from
-the environment as usual.  The K-step region is timed `--repeats` times (default 5),
-each bracketed by barrier + synchronize and maximised over ranks; the line reports
-the median (and min / max).
+the environment as usual.  The K-step region is timed `--repeats` times (default 1,
+5 with --full), each bracketed by barrier + synchronize and maximised over ranks;
+the line reports the median (and min / max).
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the timed
+K-step region(s), the result line.  `--full` adds everything else the benchmark
+measures or checks (below), as separate runs after the headline region.  The
+`metric` and `dtype` strings are the same in both forms, so that lines stay
+comparable: the EPE that `metric` names (`epe_vs_oracle_m`) and the `value_f64`
+that `dtype` points to are carried by a --full line only.
+
+`--dump-outputs DIR` writes what the timed path returned in its last step -- the
+four outputs of the ring slot that step streamed -- as DIR/<name>.npy (float32,
+target_cls converted from int64); inputs are seeded, so two builds can be compared
+output for output.  Above 64 MB in all, a fixed seeded sample of batch rows is
+written, with their indices as DIR/sample_rows.npy.
 
 One JSON line on stdout (rank 0).  Extra objects:
-  roofline      dominant kernel of the headline step (scan_preprocess_kernel)
+  roofline      dominant kernel of the headline step (scan_preprocess_kernel);
+                its HIP-event figure (`events`) with --full only
+  --full only:
+  epe_vs_oracle_m  flow of the headline outputs against the NumPy oracle
   cpu_baseline  the NumPy oracle (a port of the reference's per-sample path)
                 timed on this host's cores, rank 0, N=1 only, bounded sample
-  cutout        secondary measurement: the A8 cutout kernel at BASELINE config 3
-                shape with its own HBM roofline (not part of `value`)
+  value_f64, single_batch_launches, strong_scaling (N > 1)
+                the same steps as float64 outputs, one batch per launch, and
+                one 4096-scan batch split over the ranks
+  box_head_train, detector_train, host_fed, cutout, ...
+                secondary measurements with their own regions and rooflines
+                (not part of `value`)
 """
 import argparse
 import json
@@ -102,12 +122,43 @@ def parse():
     ap.add_argument("--no-train", action="store_true",
                     help="skip the training-step rows (box head incl. its hipGraph replay, detector): the rocprofv3 "
                          "--pmc passes leave them out -- counter collection aborts the queue on the captured step")
-    ap.add_argument("--repeats", type=int, default=5, help="timed repeats of the K-step region (median reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repeats of the K-step region (median reported; default 1, with --full 5)")
     ap.add_argument("--spawn", action="store_true", help="start the rank processes from this one even for --gpus 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: HIP-event regions, float64 and one-batch-per-launch "
+                         "legs, strong split (N > 1), parity against the oracle, CPU baseline, training rows and "
+                         "per-kernel extras (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
     if a.no_graph:
         a.launch = "eager"
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
     return a
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, outs):
+    """The outputs a caller of the timed path receives (dict name -> device tensor [B, ...]) as float32 / float64
+    .npy files; above DUMP_LIMIT_BYTES in all, the same seeded sample of batch rows of every output."""
+    arrays = {}
+    for name, t in outs.items():
+        v = t.detach().cpu().numpy()
+        arrays[name] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)
+    total = sum(v.nbytes for v in arrays.values())
+    B = len(next(iter(arrays.values())))
+    os.makedirs(path, exist_ok=True)
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES * B // (total + 8 * B))    # rows of every output + their float64 index
+        rows = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def cpu_sample_worker(args):
@@ -260,7 +311,7 @@ def main():
             sb.dets[b] = {"wc": np.zeros((0, 2)), "wa": np.zeros((0, 2)), "wp": d}
     # CPU baseline first: the worker pool is forked before this process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(sb)
 
     # test hooks (single-GPU rehearsal of the N > 1 path): POF_BENCH_SHARE_GPU=1 puts every rank
@@ -389,17 +440,23 @@ def main():
             graph = True
 
         prepared = {}
+        marshalled = {}
 
         def prepared_for(n):
-            """trip(n) as marshalled launches (ops.PreparedScanLaunch): what a loader cycling through its ring keeps."""
+            """trip(n) as marshalled launches (ops.PreparedScanLaunch): what a loader cycling through its ring keeps.
+            A launch is fixed by its ring position and slot count, so each combination is marshalled once (set-up
+            time independent of n)."""
             if n not in prepared:
                 lst, p, left = [], 0, n
                 while left > 0:
                     m = min(S, left)
-                    cur = [ring[(p + j) % a.ring] for j in range(m)]
-                    nxt = [] if a.no_params else [ring[(p + S + j) % a.ring] for j in range(m)]
-                    lst.append(ops.scan_preprocess_multi(cur, tab, next_batches=nxt, want=want, out_dtype=out_dtype,
-                                                         prepare=True))
+                    key = (p % a.ring, m)
+                    if key not in marshalled:
+                        cur = [ring[(p + j) % a.ring] for j in range(m)]
+                        nxt = [] if a.no_params else [ring[(p + S + j) % a.ring] for j in range(m)]
+                        marshalled[key] = ops.scan_preprocess_multi(cur, tab, next_batches=nxt, want=want,
+                                                                    out_dtype=out_dtype, prepare=True)
+                    lst.append(marshalled[key])
                     p += m
                     left -= m
                 prepared[n] = lst
@@ -439,7 +496,7 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 dt = float(t.item())
             walls.append(dt)
-        for _ in range(max(1, min(3, a.repeats))):
+        for _ in range(max(1, min(3, a.repeats)) if a.full else 0):
             barrier()
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
@@ -447,26 +504,32 @@ def main():
             ev1.record()
             barrier()
             devs.append(ev0.elapsed_time(ev1))
+        # ring slot of the last of the K steps: every launch sequence (trip, prepared_for, each captured graph) starts
+        # at ring position 0, so step i of a sequence streams slot i % ring; a graph region is replayed as graphs of
+        # kGraphSteps steps plus one of the remainder
+        last = (a.steps - 1) % kGraphSteps if graph is not None else a.steps - 1
         return {"wall_s": walls, "dev_ms": devs, "ring": ring, "graph": graph is not None, "slots": S,
-                "launches": -(-a.steps // S)}
+                "launches": -(-a.steps // S), "last_slot": last % a.ring}
 
     weak = measure(sb, a.slots)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, weak["ring"][weak["last_slot"]]["out"])     # the outputs of the last timed step
     # the same steps one batch per launch (the per-kernel duration rocprofv3 reports for THAT form is one step)
-    single = measure(sb, 1) if (a.slots > 1 and not a.no_single) else None
+    single = measure(sb, 1) if (a.full and a.slots > 1 and not a.no_single) else None
     # the float64-output instantiation (the reference's float64 operation order for the flow: utils.py:47-48,
     # 639-662), same region shape
     f64 = f64_out = None
-    if not a.no_single:
+    if a.full and not a.no_single:
         f64 = measure(sb, a.slots, torch.float64)
         f64_out = f64["ring"][0]["out"]["flow"][:64].cpu().numpy()
         f64 = {k: v for k, v in f64.items() if k != "ring"}
     torch.cuda.empty_cache()
     dt = float(np.median(weak["wall_s"]))
-    dev_ms = float(np.median(weak["dev_ms"]))
+    dev_ms = float(np.median(weak["dev_ms"])) if weak["dev_ms"] else None
     ring = weak["ring"]
     graph = weak["graph"]
     strong = None
-    if world > 1 and B % world == 0:
+    if a.full and world > 1 and B % world == 0:
         # the contiguous split of ONE 4096-scan batch, 4096 / N scans per rank and step
         per = B // world
         sbg = synth.make_batch(seed=2, B=B, T=2, N=N)
@@ -482,18 +545,20 @@ def main():
         del st
 
     # ---- parity of what was just computed (outside the timed region) ------------
-    from oracle import ref_numpy as R
-    outs = ring[0]["out"]
-    phi = R.laser_phi()
-    flow = outs["flow"][:64].cpu().numpy()
-    epe = epe64 = 0.0
-    for b in range(64):
-        cur = sb.scans[b, -1]
-        xy = np.array(R.polar_to_xy(cur, phi)).T
-        ref = R.flow_to_canonical(R.displacement_from_odometry(xy, sb.odom0[b], sb.odom1[b]), phi)
-        epe += float(np.linalg.norm(flow[b] - ref, axis=-1).mean()) / 64
-        if f64_out is not None:
-            epe64 += float(np.linalg.norm(f64_out[b] - ref, axis=-1).mean()) / 64
+    epe = epe64 = None
+    if a.full:
+        from oracle import ref_numpy as R
+        outs = ring[0]["out"]
+        phi = R.laser_phi()
+        flow = outs["flow"][:64].cpu().numpy()
+        epe = epe64 = 0.0
+        for b in range(64):
+            cur = sb.scans[b, -1]
+            xy = np.array(R.polar_to_xy(cur, phi)).T
+            ref = R.flow_to_canonical(R.displacement_from_odometry(xy, sb.odom0[b], sb.odom1[b]), phi)
+            epe += float(np.linalg.norm(flow[b] - ref, axis=-1).mean()) / 64
+            if f64_out is not None:
+                epe64 += float(np.linalg.norm(f64_out[b] - ref, axis=-1).mean()) / 64
 
     # the training rows run on all ranks (they hold collectives).  They are extras: an error in one of them (the
     # same on every rank) is reported in its place instead of costing the line its headline measurement
@@ -505,9 +570,9 @@ def main():
             sys.stderr.write("bench.py: %s failed on rank %d:\n%s\n" % (fn.__name__, rank, traceback.format_exc()))
             return {"error": "%s: %s" % (type(e).__name__, e)}
 
-    box = None if (a.no_extra or a.no_train) else guarded(bench_box_head, dev, world, rank, backend, barrier,
+    box = None if (not a.full or a.no_extra or a.no_train) else guarded(bench_box_head, dev, world, rank, backend, barrier,
                                                             a.graph_collectives)
-    det_train = None if (a.no_extra or a.no_model or a.no_train) else guarded(bench_detector_train, ops, synth, tab, dev,
+    det_train = None if (not a.full or a.no_extra or a.no_model or a.no_train) else guarded(bench_detector_train, ops, synth, tab, dev,
                                                                              world, rank, backend, barrier)
 
     result = None
@@ -523,7 +588,6 @@ def main():
         # both sides, graph launch and the final synchronize included); the HIP-event interval on the launch
         # stream is carried beside it
         achieved = bytes_per_scan * B / (ms_step * 1e-3) / 1e9
-        ev_step = dev_ms / a.steps
         kernel = "scan_flat_kernel<float, headline cfg>"
         traffic, traffic_src = pmc_traffic(("scan_flat_kernel<float",))
         if B != BATCH:
@@ -560,7 +624,6 @@ def main():
                        "parallelism": "weak: batch-sharded x%d, %d scans per rank and step, no data-path collective" % (world, B),
                        "rccl_ranks": (dist.get_world_size() if world > 1 and backend == "nccl" else None),
                        "collective_backend": (backend if world > 1 else None)},
-            "epe_vs_oracle_m": epe,
             "roofline": {"bound": "hbm", "kernel": kernel,
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -573,15 +636,21 @@ def main():
                          "bytes_per_launch": bytes_per_scan * B * a.steps / weak["launches"],
                          "launch_ms": ms_step * a.steps / weak["launches"],
                          "launches": weak["launches"], "steps_per_launch": S,
-                         "events": {"ms_per_step": ev_step, "achieved": bytes_per_scan * B / (ev_step * 1e-3) / 1e9,
-                                    "frac": bytes_per_scan * B / (ev_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                    "ms_per_step_min": min(weak["dev_ms"]) / a.steps,
-                                    "ms_per_step_max": max(weak["dev_ms"]) / a.steps,
-                                    "note": "HIP events on the launch stream around K-step regions of their own (the same launches; the wall regions hold no event records)"},
                          "note": "one kernel launch covers up to %d steps (ring slots): a per-kernel duration as "
                                  "rocprofv3 lists it is launch_ms = ms_per_step x steps / launches (%d x ms_per_step for "
                                  "full launches); `traffic` is per full launch" % (S, S)},
         }
+        if epe is not None:
+            result["epe_vs_oracle_m"] = epe
+        if dev_ms is not None:
+            ev_step = dev_ms / a.steps
+            result["roofline"]["events"] = {
+                "ms_per_step": ev_step, "achieved": bytes_per_scan * B / (ev_step * 1e-3) / 1e9,
+                "frac": bytes_per_scan * B / (ev_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "ms_per_step_min": min(weak["dev_ms"]) / a.steps,
+                "ms_per_step_max": max(weak["dev_ms"]) / a.steps,
+                "note": "HIP events on the launch stream around K-step regions of their own (the same launches; the "
+                        "wall regions hold no event records)"}
         if f64 is not None:
             f_dt = float(np.median(f64["wall_s"]))
             f_ms = f_dt / a.steps * 1e3
@@ -608,7 +677,7 @@ def main():
             result["box_head_train"] = box
         if det_train is not None:
             result["detector_train"] = det_train
-        if not a.no_extra and world == 1:   # per-kernel extras only on the single-GPU line
+        if a.full and not a.no_extra and world == 1:   # per-kernel extras only on the single-GPU line
             if not a.no_host_fed:
                 result["host_fed"] = bench_host_fed(ops, sb, tab, dev)
             result["cutout"] = bench_cutout(ops, synth, tab, dev, variants=not a.no_model)

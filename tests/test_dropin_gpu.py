@@ -796,14 +796,14 @@ def test_bench_plain_command_line_starts_its_own_ranks():
     """`python bench.py --gpus 2` -- the plain command line, no launcher, no WORLD_SIZE: the parent starts two
     fresh rank processes itself and relays rank 0's line.  Rehearsed with both ranks on the one GPU (gloo
     instead of RCCL, which needs a device per rank)."""
-    d = _bench_line(["--gpus", "2", "--steps", "40", "--warmup", "8", "--repeats", "3"],
+    d = _bench_line(["--full", "--gpus", "2", "--steps", "40", "--warmup", "8", "--repeats", "3"],
                     {"POF_BENCH_SHARE_GPU": "1", "POF_BENCH_BACKEND": "gloo"})
     _check_two_rank_line(d)
 
 
 def test_bench_two_ranks_under_torch_distributed_run():
     """The driver's N > 1 launch line (torch.distributed.run): ranks from the environment, same line."""
-    d = _bench_line(["--gpus", "2", "--steps", "40", "--warmup", "8", "--repeats", "3"],
+    d = _bench_line(["--full", "--gpus", "2", "--steps", "40", "--warmup", "8", "--repeats", "3"],
                     {"POF_BENCH_SHARE_GPU": "1", "POF_BENCH_BACKEND": "gloo"}, launcher=True)
     _check_two_rank_line(d)
 
@@ -811,7 +811,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
 def test_bench_launcher_path_equals_direct_path_at_one_gpu():
     """--gpus 1 through the rank launcher (--spawn) against the direct path: same line, same rate (medians of 5
     timed regions; 10 % covers the run-to-run spread of a 15 us launch on one box)."""
-    args = ["--steps", "400", "--warmup", "40", "--no-cpu-baseline", "--no-extra"]
+    args = ["--full", "--steps", "400", "--warmup", "40", "--no-cpu-baseline", "--no-extra"]
     direct = _bench_line(args, {})
     spawned = _bench_line(args + ["--spawn"], {})
     assert spawned["n_gpus"] == direct["n_gpus"] == 1
@@ -822,7 +822,7 @@ def test_bench_single_gpu_line_and_world_size_check():
     """--gpus 1: roofline / cpu_baseline / host-fed objects present and consistent; a WORLD_SIZE that disagrees
     with --gpus is refused instead of silently measuring one GPU."""
     import os, subprocess, sys
-    d = _bench_line(["--steps", "80", "--warmup", "8", "--repeats", "3", "--no-model"], {})
+    d = _bench_line(["--full", "--steps", "80", "--warmup", "8", "--repeats", "3", "--no-model"], {})
     assert d["n_gpus"] == 1 and "strong_scaling" not in d
     rf = d["roofline"]
     assert rf["bound"] == "hbm" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12
@@ -851,6 +851,49 @@ def test_bench_single_gpu_line_and_world_size_check():
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "8"],
                        capture_output=True, text=True, env=env, cwd=repo, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
+
+
+def _check_dumped_step(path, slot):
+    """The four dumped outputs are whole float32 arrays of the ring slot `slot`, whose batch is the seed-2 batch
+    rolled by (slot x 509) rows: flow and association of a few rows against the oracle."""
+    shapes = {"flow": (4096, 450, 2), "target_cls": (4096, 450), "target_reg": (4096, 450, 2),
+              "exclude_mask": (4096, 450)}
+    got = {p.stem: np.load(p) for p in path.glob("*.npy")}
+    assert {k: v.shape for k, v in got.items()} == shapes
+    assert all(v.dtype == np.float32 for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 * 10 ** 6
+    sb = synth.make_batch(seed=2, B=4096, T=2, N=450)
+    sh = slot * 509
+    phi = R.laser_phi()
+    for b in (0, 1, 2000, 4095):
+        src = (b - sh) % 4096
+        cur = sb.scans[src, -1]
+        xy = np.array(R.polar_to_xy(cur, phi)).T
+        want = R.flow_to_canonical(R.displacement_from_odometry(xy, sb.odom0[src], sb.odom1[src]), phi)
+        assert np.linalg.norm(got["flow"][b] - want, axis=-1).mean() < 1e-5, (slot, b)
+        cls, _ = R.regression_target(cur, phi, [], [], sb.dets[src]["wp"])
+        assert np.array_equal(got["target_cls"][b], cls), (slot, b)
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """The plain command line times the K steps once and carries the headline fields only (everything else is
+    --full); --dump-outputs writes the four outputs of the LAST timed step.  Every launch sequence starts at ring
+    position 0: step i streams slot i % ring, and a graph region is replayed as 512-step graphs plus the remainder."""
+    d = _bench_line(["--gpus", "1", "--steps", "24", "--warmup", "4", "--dump-outputs", str(tmp_path / "p")], {})
+    assert d["n_gpus"] == 1 and d["steps"] == 24 and d["warmup"] == 4 and d["timed_repeats"] == 1
+    assert d["unit"] == "scans/s" and d["higher_is_better"] is True and "f32" in d["dtype"]
+    assert d["ms_per_step_min"] == d["ms_per_step"] == d["ms_per_step_max"] > 0
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert "events" not in d["roofline"] and abs(d["roofline"]["achieved"] - 14400 * 4096 / (d["ms_per_step"] * 1e-3) / 1e9) \
+        < 1e-6 * d["roofline"]["achieved"]
+    for k in ("epe_vs_oracle_m", "value_f64", "single_batch_launches", "cpu_baseline", "box_head_train",
+              "detector_train", "host_fed", "cutout", "small_kernels"):
+        assert k not in d, k
+    _check_dumped_step(tmp_path / "p", 23 % 16)
+    # graph replay with a ring that does not divide 512: 600 steps = one 512-step graph + one 88-step graph
+    d = _bench_line(["--gpus", "1", "--steps", "600", "--warmup", "4", "--launch", "graph", "--ring", "24",
+                     "--dump-outputs", str(tmp_path / "g")], {})
+    assert d["steps"] == 600 and d["config"]["ring_batches"] == 24
+    _check_dumped_step(tmp_path / "g", 87 % 24)
 
 
 def test_box_head_gpu_forward_equals_reference(golden):

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 GROUPS_=("VALUBusy" "MemUnitStalled" "WriteUnitStalled" "SQ_WAVES SQ_BUSY_CYCLES" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD" "SQ_INSTS_LDS SQ_INSTS_FLAT SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU" "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_WAIT_ANY")
 for grp in "${GROUPS_[@]}"; do
   tag=$(echo $grp | tr ' ' '_')
-  rocprofv3 --pmc $grp --output-format csv -d $OUT/$tag -- python3 bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-extra > /dev/null 2> $OUT/$tag.err || echo "pass $tag failed"
+  rocprofv3 --pmc $grp --output-format csv -d $OUT/$tag -- python3 bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-extra > /dev/null 2> $OUT/$tag.err || echo "pass $tag failed"
 done
 python3 - $OUT <<'PY'
 import sys, glob, csv, collections

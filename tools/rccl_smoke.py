@@ -64,11 +64,39 @@ red2 = pd.GradientAllReduce(gm, always=True)
 gstep = GraphedTrainStep(gm, gopt, {"input": x, "target": y}, reducer=red2)
 assert gstep._fused_collective and len(gstep._graphs) == 1
 assert all(p.grad.data_ptr() == v.data_ptr() for p, v in zip(red2.params, red2.views))
-worst_loss = 0.0
+# The gradients are checked against a float64 CPU evaluation of the same step at the weights the step started from
+# (stock BatchNorm == one-rank SyncBatchNorm), not against the eager twin: on these shapes MIOpen's timed solver choice
+# sometimes picks a weight-gradient solver that computes conv4's weight gradient wrong in the EAGER step (2.25e-2 of
+# scale on the fourth batch below; profiles/r3_graph_capture_miopen.txt), while the
+# captured step is right on every solver.  The eager twin keeps MIOpen's default choice; its losses are compared, and
+# its gradient deviation from the reference is reported.
+cpu_ref = get_model(cfg).double().train()
+
+
+def ref_grads(weights, xb, yb):
+    with torch.no_grad():
+        for p, w in zip(cpu_ref.parameters(), weights):
+            p.copy_(w.double().cpu())
+    cpu_ref.zero_grad(set_to_none=True)
+    cpu_ref.loss_fn(cpu_ref(xb.double().cpu()), yb.double().cpu()).backward()
+    return [p.grad for p in cpu_ref.parameters()]
+
+
+def grad_err(m, ref):
+    """worst |grad - reference| over the model, on the scale of the largest reference gradient (the gradients of a
+    bias in front of a BatchNorm are pure round-off)"""
+    rs = max(r.abs().max().item() for r in ref if r is not None)
+    return max((p.grad.double().cpu() - r).abs().max().item() for p, r in zip(m.parameters(), ref)
+               if r is not None and p.grad is not None) / rs
+
+
+worst_loss = worst_graph = worst_eager = 0.0
 for it in range(4):
     xb = torch.randn(12, 64, 3, device="cuda")
     yb = torch.randn(12, 3, device="cuda")
     red2.set_stop(it == 2)
+    g_w = [p.detach().clone() for p in gm.parameters()]
+    e_w = [p.detach().clone() for p in em.parameters()]
     torch.cuda.set_sync_debug_mode("error")
     gl = gstep({"input": xb, "target": yb})
     torch.cuda.set_sync_debug_mode("default")
@@ -79,13 +107,14 @@ for it in range(4):
     eopt.step()
     worst_loss = max(worst_loss, abs(gl.item() - el.item()) / max(abs(el.item()), 1e-6))
     assert red2.stop_requested() == (it == 2), it       # the flag of THIS step's all-reduce, read after it
+    # this step's gradients (the graph's live in the flat bucket) against the reference at each model's own weights
+    # (weights drift apart by round-off: where a gradient is pure round-off, Adam normalises it to steps of +-lr)
+    gerr = grad_err(gm, ref_grads(g_w, xb, yb))
+    assert gerr < 1e-4, (it, gerr)
+    worst_graph = max(worst_graph, gerr)
+    worst_eager = max(worst_eager, grad_err(em, ref_grads(e_w, xb, yb)))
 assert worst_loss < 1e-5, worst_loss
-# the gradients of the last step (the graph's live in the flat bucket), on the scale of the largest one.  (Weights are
-# not compared: where a gradient is pure round-off -- a bias in front of a BatchNorm -- Adam normalises the round-off
-# to steps of +-lr on either side; the losses above do not depend on those parameters.)
-gscale = max(q.grad.abs().max().item() for q in em.parameters() if q.grad is not None)
-wdiff = max((p.grad - q.grad).abs().max().item() for p, q in zip(gm.parameters(), em.parameters())) / gscale
-assert wdiff < 1e-4, wdiff
 dist.destroy_process_group()
 print("RCCL_OK worst relative gradient difference SyncBN vs BatchNorm: %.2e; captured step with collectives: "
-      "loss diff %.1e, gradient diff %.1e of scale, no host sync in the replay" % (worst, worst_loss, wdiff))
+      "loss diff %.1e vs the eager twin, gradients %.1e of scale from the float64 reference (eager twin on MIOpen's "
+      "default solvers: %.1e), no host sync in the replay" % (worst, worst_loss, worst_graph, worst_eager))

@@ -4,7 +4,7 @@
 STEPS=${1:-400}
 for tune in 128,1 64,1 256,1 128,2 64,2 256,2; do
   for slots in 1 4; do
-    POF_FLAT_TUNE=$tune python bench.py --steps $STEPS --warmup 40 --slots $slots --no-extra --no-cpu-baseline 2>/dev/null | \
+    POF_FLAT_TUNE=$tune python bench.py --full --steps $STEPS --warmup 40 --slots $slots --no-extra --no-cpu-baseline 2>/dev/null | \
       python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
