@@ -103,7 +103,13 @@ int pof_scan_preprocess(const float *ranges, long long sample_stride, int B, int
  * batches on two streams (params of batch i+1 under the streaming launch of
  * batch i): phases = 1 runs only the per-sample params launch (fills the
  * workspace), phases = 2 only the streaming launch (workspace must have been
- * filled for these inputs), phases = 3 both (= pof_scan_preprocess). */
+ * filled for these inputs), phases = 3 both (= pof_scan_preprocess).
+ * Alignment (this call, pof_scan_preprocess and pof_scan_preprocess_chained): none required.  The flat kernel runs
+ * when N is even and >= 128, sample_stride is even, ranges is 8-byte and every non-NULL output 16-byte aligned;
+ * the same rows with aligned pointers but a short N run 2 points per lane (float2 loads, 16-byte stores), and
+ * anything else 1 point per lane with scalar loads and stores.  All three give the same bits, except float32 flow
+ * (flow_kind != 1): the flat kernel evaluates it in float32 arithmetic, the per-point kernels round the float64
+ * result once, so the last bits may differ (both within 1e-5 m of the float64 reference). */
 int pof_scan_preprocess_phase(const float *ranges, long long sample_stride, int B, int N,
                               const double *tab, const double *odom0, const double *odom1,
                               int flow_kind, int canonical, int out_f64, void *xy, void *flow,
@@ -152,6 +158,8 @@ int pof_scan_preprocess_chained(const float *ranges, long long sample_stride, in
  * tab_cs_f32: optional [N][2] float32 copy of the table's (cos, sin) pairs, each rounded once from the float64
  * entry (what the float32-output kernel would otherwise convert per point); NULL is allowed.
  * Shapes: N even, N >= 128 (POF_E_SHAPE otherwise: use pof_scan_preprocess_chained), sample_stride even.
+ * Alignment: ranges 8-byte and every non-NULL output 16-byte aligned; there is no fallback: POF_E_SHAPE otherwise
+ * (use pof_scan_preprocess_chained for such buffers).
  * Replaces the same reference calls as pof_scan_preprocess (dataset_dr_spaam.py:384-409), for a window of
  * consecutive DataLoader batches (dataset_dr_spaam.py:26-28, prefetching workers). */
 #define POF_SCAN_MAX_SLOTS 8
@@ -235,7 +243,10 @@ int pof_cutout_ex(const float *scans, int B, int T, int N, const double *tab, in
 /* BASELINE config 5 storage (reference src/utils/utils.py:259-334 returns float32): the same cutout
  * written as IEEE float16 (the float32 result
  * rounded to nearest even once more), out_f16 [B][ceil(N/stride)][T][P] half.  Halves the
- * dominant write traffic (3600*11*(4 + 56*2) bytes per dense sample). */
+ * dominant write traffic (3600*11*(4 + 56*2) bytes per dense sample).
+ * Alignment (this call, pof_cutout and pof_cutout_ex): none required.  Rows are staged in LDS with float2 loads
+ * only when scans is 8-byte aligned and T*N even (scalar loads otherwise); outputs are written as float4 / half4
+ * only when P % 4 == 0 and out is 16-byte aligned (scalar stores otherwise).  The bits do not depend on either. */
 int pof_cutout_f16(const float *scans, int B, int T, int N, const double *tab, int stride, int centered,
                    int fixed, double window_width, double window_depth, int num_cutout_pts,
                    double padding_val, int area_mode, int value_mode, void *out_f16, int32_t *workspace,
@@ -275,7 +286,9 @@ int pof_band_correlation(const float *feat1, const float *feat2, float *out, int
 
 /* BASELINE config 5 ("fp16 correlation"; no counterpart in the reference, which is float32
  * throughout prototype.py:118-156): the same with float16 feature storage.  Products and
- * accumulation are float32 (a float16 converts exactly), the output stays float32. */
+ * accumulation are float32 (a float16 converts exactly), the output stays float32.
+ * Alignment (both forms and the backward): none required beyond the element size; feature rows are read with
+ * element-aligned loads, so a chunk of a larger batch may start anywhere. */
 int pof_band_correlation_f16(const void *feat1_f16, const void *feat2_f16, float *out, int B, int C, int n,
                              int kernel_size, int max_disp, pof_stream_t stream);
 
@@ -293,6 +306,9 @@ int pof_band_correlation_backward(const float *feat1, const float *feat2, const 
  * band [B][N][w] pre-softmax similarities (clamped duplicates kept),
  * prob [B][N][w] softmax weights with duplicates zeroed (scratch, also useful
  * for the backward pass), out [B][N][F] = alpha*x + (1-alpha)*sum_k prob*tmpl.
+ * F % 4 == 0 (POF_E_SHAPE otherwise).  Alignment (forward, f16 form and backward): none required beyond the
+ * element size; rows are read and written 4 elements at a time whatever their address (the hardware's unaligned
+ * global access), with the same bits as aligned buffers.
  * ---------------------------------------------------------------------- */
 int pof_spatial_attention(const float *emb_x, const float *emb_t, const float *x, const float *tmpl,
                           int B, int N, int E, int F, int window, double alpha, float *band,
@@ -399,6 +415,8 @@ int pof_associate_odometry(const float *scans_t, const float *odoms_t, const flo
  * [3][Ci][Co]; scale[Co] = gamma / sqrt(running_var + eps), shift[Co] = beta +
  * (conv_bias - running_mean) * scale (the caller folds them once per checkpoint).
  * Implicit GEMM on the float32 MFMA (exact float32 products, k-ordered accumulation).
+ * Alignment (this call, pof_conv1d_bn_lrelu and pof_conv3_first_two): none required beyond 4 bytes; loads and
+ * stores are vector-wide whatever the address, with the same bits as aligned buffers.
  * ---------------------------------------------------------------------- */
 int pof_conv3_bn_lrelu(const float *x, const float *wt, const float *scale, const float *shift,
                        int S, int Ci, int Co, int L, int pool, double negative_slope, float *out,
@@ -441,6 +459,7 @@ int pof_drow_heads(const float *feat, int S, int C, int L, const float *w_cls, c
  * save_mean / save_invstd are then [groups][C] and the running statistics receive the groups'
  * updates in order, as `groups` separate calls would give.
  * workspace: pof_bn_lrelu_pool_workspace_bytes(S, C, L, groups) bytes (0 = unsupported shape).
+ * Alignment: none required beyond 4 bytes (float4 accesses at any address, same bits as aligned buffers).
  * ---------------------------------------------------------------------- */
 size_t pof_bn_lrelu_pool_workspace_bytes(long long S, int C, int L, int groups);
 int pof_bn_lrelu_pool_forward(const float *y, long long S, int C, int L, int groups, const float *gamma,
@@ -482,7 +501,11 @@ int pof_conv3_wgrad(const float *x, const float *dy, int S, int Ci, int Co, int 
                     void *workspace, size_t workspace_bytes, pof_stream_t stream);
 /* The same pass for kernel_size 1 | 3 (1: the point-wise convolutions of the box-regression PointNet,
  * src/model/box_regression.py:8-17, and of the Prototype head, src/depracted/model/prototype.py:52-58):
- * dw [Co][Ci][kernel_size]; kernel_size 3 is pof_conv3_wgrad. */
+ * dw [Co][Ci][kernel_size]; kernel_size 3 is pof_conv3_wgrad.
+ * Alignment: the load width is 4 / 2 / 1 floats by L % 4, L % 2 when x and dy are both 16-byte aligned, 1 float
+ * otherwise.  The workspace size and the shapes supported are those of 16-byte aligned operands: with an unaligned
+ * x or dy a supported shape may return POF_E_SHAPE (rows of more than 32 floats) or POF_E_WORKSPACE (the split
+ * doubles).  Callers hand the kernel aligned copies (ops.conv3_wgrad does). */
 size_t pof_conv1d_wgrad_workspace_bytes(int S, int Ci, int Co, int L, int kernel_size);
 int pof_conv1d_wgrad(const float *x, const float *dy, int S, int Ci, int Co, int L, int kernel_size, float *dw,
                      void *workspace, size_t workspace_bytes, pof_stream_t stream);
@@ -490,7 +513,8 @@ int pof_conv1d_wgrad(const float *x, const float *dy, int S, int Ci, int Co, int
 /* ----------------------------------------------------------------------
  * configs[3] box-regression head, dense layers    src/model/box_regression.py:26-45 (_fc), :139-141
  * out[b][n] = sum_k x[b][k] * w[n][k] + bias[n] (torch.nn.Linear's forward; x [B][K], w [N][K],
- * bias [N] or NULL, out [B][N], float32, K a multiple of 4, x and w 16-byte aligned).  For the
+ * bias [N] or NULL, out [B][N], float32, K a multiple of 4, x and w 16-byte aligned: POF_E_SHAPE
+ * otherwise, no fallback -- ops.linear_bias copies unaligned operands; bias and out may be anywhere).  For the
  * head's batch (a few hundred rows): one workgroup per 32 x 32 output tile, K split over its
  * four waves, float32 MFMA, deterministic.  The backward GEMMs stay with the BLAS library.
  * ---------------------------------------------------------------------- */
@@ -540,6 +564,9 @@ int pof_segment_resample(const double *points, int D, const int32_t *seg_offsets
  * the truncated-signed-distance column of every beam (the "fc2d" network input,
  * src/utils/dataset_dr_spaam.py:455-458).  float32 arithmetic as NumPy >= 2 evaluates
  * the reference (bit-exact against it); tsdf_clip <= 0 disables the distance ramp.
+ * Alignment: none required.  The flat kernel (16-byte stores) runs when out is 16-byte aligned and
+ * N * 8 + (2R + 1) * 4 <= 60 KB; otherwise 4 points per lane with float4 accesses when N % 4 == 0 and scans and
+ * out are 16-byte aligned, else 1 point per lane.  All three give the same bits.
  * ---------------------------------------------------------------------- */
 int pof_polar_grid(const float *scans, int B, int T, int N, double min_range, double max_range,
                    double range_bin_size, double tsdf_clip, int normalize, float *out,

@@ -172,8 +172,13 @@ def call(name, *args):
             warnings.warn("%s: HIP error %d was pending from an earlier call of this thread" % (name, stale),
                           StaleHipError, stacklevel=2)
     if code != POF_OK:
-        msg = lib.pof_error_string(code).decode()
-        if code == POF_E_BADARG:
-            raise AssertionError("%s: %s" % (name, msg))
-        raise PofError(name, code, msg)
+        raise_for(name, code)
     return code
+
+
+def raise_for(name, code):
+    """The exception call() raises for a non-zero code of entry point `name`."""
+    msg = load().pof_error_string(code).decode()
+    if code == POF_E_BADARG:
+        raise AssertionError("%s: %s" % (name, msg))
+    raise PofError(name, code, msg)

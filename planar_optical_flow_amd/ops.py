@@ -23,6 +23,11 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _aligned16(t):
+    """t itself when its data starts on a 16-byte boundary, otherwise a fresh (allocator-aligned) copy."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def _dev(t, dtype, name):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise TypeError("%s must be a tensor on the HIP device (no CPU path)" % name)
@@ -291,11 +296,17 @@ def scan_preprocess_multi(batches, tab, next_batches=(), flow_kind=FLOW_DISPLACE
                   "target_cls": ((B, N), torch.int64), "target_reg": ((B, N, 2), torch.float32),
                   "dyn_mask": ((B, N), torch.float32), "valid_mask": ((B, N), torch.float32),
                   "exclude_mask": ((B, N), torch.float32)}
+        if (scans.data_ptr() + 4 * off) % 8 or stride % 2:
+            raise ValueError("batch %d: the current scans must start on an 8-byte boundary with an even sample stride"
+                             % k)
         for name in known:
             if name in want:
                 t = _dev(out[name], shapes[name][1], name)
                 if tuple(t.shape) != shapes[name][0]:
                     raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), shapes[name][0]))
+                if t.data_ptr() % 16:
+                    raise ValueError("batch %d: output %s must start on a 16-byte boundary (the one-launch form "
+                                     "has no unaligned variant; use scan_preprocess)" % (k, name))
                 setattr(c, name, t.data_ptr())
         c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
         keep.append((scans, out, ws))
@@ -325,7 +336,7 @@ class PreparedScanLaunch:
     def __call__(self):
         code = self._fn(*self._args, torch.cuda.current_stream(self._device).cuda_stream)
         if code != _lib.POF_OK:
-            _lib.call("pof_scan_preprocess_multi", *self._args, _stream())      # the checked path raises the exception
+            _lib.raise_for("pof_scan_preprocess_multi", code)
 
 
 def flow_from_xy(xy, odom0, odom1, flow_kind=FLOW_DISPLACEMENT, canonical=False, tab=None):
@@ -570,6 +581,10 @@ def conv3_wgrad(x, dy, kernel_size=3):
     if kernel_size not in (1, 3):
         raise ValueError("kernel_size must be 1 or 3")
     Co = dy.shape[1]
+    # the library picks its load width from the operands' alignment and sizes the workspace (and the shapes it takes)
+    # for 16-byte aligned ones: a view at an offset goes through an aligned copy
+    x = _aligned16(x)
+    dy = _aligned16(dy)
     nbytes = int(_lib.load().pof_conv1d_wgrad_workspace_bytes(S, Ci, Co, L, kernel_size))
     if nbytes == 0:
         raise ValueError("conv3_wgrad: unsupported shape S=%d Ci=%d Co=%d L=%d" % (S, Ci, Co, L))
@@ -606,6 +621,8 @@ def linear_bias(x, weight, bias=None, out=None):
     N = weight.shape[0]
     if K % 4:
         raise ValueError("linear_bias: K = %d is not a multiple of 4" % K)
+    x = _aligned16(x)                # 16-byte operand loads: views at an offset go through a copy
+    weight = _aligned16(weight)
     if bias is not None and _dev(bias, torch.float32, "bias").numel() != N:
         raise ValueError("bias must have N entries")
     if out is None:
