@@ -343,6 +343,13 @@ int pof_spatial_attention_backward_fused(const float *emb_x, const float *emb_t,
                                          float *d_tmpl, void *workspace, size_t workspace_bytes,
                                          pof_stream_t stream);
 
+/* No device work (no HIP call).  Points per lane segment of one call on B <= 65535 scans of N
+ * points and F features: forward_segment for the merge walk of pof_spatial_attention(_f16) and the
+ * transposed merge of pof_spatial_attention_backward, backward_segment for the fused walk of
+ * pof_spatial_attention_backward_fused.  POF_E_BADARG for NULL outputs or sizes < 1, POF_E_SHAPE
+ * for F % 4 != 0 or B > 65535. */
+int pof_spatial_attention_plan(int B, int N, int F, int *forward_segment, int *backward_segment);
+
 /* ------------------------------------------------------------------------
  * A13 jump-distance segmentation + per-segment least squares
  *   src/depracted/model/adaboost_person_det.py:71-90 (cuts), :102-210 (features)
@@ -430,6 +437,17 @@ int pof_conv3_bn_lrelu(const float *x, const float *wt, const float *scale, cons
 int pof_conv1d_bn_lrelu(const float *x, const float *wt, const float *scale, const float *shift,
                         int S, int Ci, int Co, int L, int kernel_size, int stride, int pool,
                         double negative_slope, float *out, pof_stream_t stream);
+
+/* No device work (no HIP call at all: it answers on a machine without a GPU).  The kernel form
+ * pof_conv3_bn_lrelu (kernel_size 3, stride 1), pof_conv1d_bn_lrelu or, with fused_first != 0,
+ * pof_conv3_first_two (Ci = C1) would launch for these sizes, POF_CONV_CT included: split_k (1: the
+ * four waves of a workgroup share one column tile and split the K loop), channels_per_workgroup (32,
+ * 64 or 128), both of the first launch; launches (sequences go in chunks of < 2^30 input elements,
+ * and a smaller last chunk may take a narrower form); wide_offsets = how many launches write at
+ * least 2^30 output elements (64-bit output offsets).  POF_E_BADARG for NULL outputs or sizes < 1,
+ * POF_E_SHAPE for what the launchers refuse as a shape. */
+int pof_conv1d_plan(int S, int Ci, int Co, int L, int kernel_size, int stride, int pool, int fused_first,
+                    int *split_k, int *channels_per_workgroup, int *launches, int *wide_offsets);
 
 /* ----------------------------------------------------------------------
  * N2 detector heads, inference                  src/depracted/model/dr_spaam.py:104-121

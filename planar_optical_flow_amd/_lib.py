@@ -52,6 +52,7 @@ SIGNATURES = {
     "pof_spatial_attention_backward_fused": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "pof_spatial_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p]),
     "pof_spatial_attention": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p]),
+    "pof_spatial_attention_plan": (_i, [_i, _i, _i, _p, _p]),
     "pof_segment_features": (_i, [_p, _p, _i, _i, _d, _i, _p, _p, _p, _p]),
     "pof_segment_features_ex": (_i, [_p, _p, _p, _i, _i, _d, _p, _p, _p, _d, _i, _p, _p, _p, _p, _p, _p]),
     "pof_gather_windows": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
@@ -59,6 +60,7 @@ SIGNATURES = {
     "pof_rotate_iou": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p]),
     "pof_conv3_bn_lrelu": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p]),
     "pof_conv1d_bn_lrelu": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _p]),
+    "pof_conv1d_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "pof_bn_lrelu_pool_workspace_bytes": (_sz, [_ll, _i, _i, _i]),
     "pof_bn_lrelu_pool_forward": (_i, [_p, _ll, _i, _i, _i, _p, _p, _p, _p, _d, _d, _d, _i, _p, _p, _p, _p, _sz, _p]),
     "pof_bn_lrelu_pool_backward": (_i, [_p, _p, _ll, _i, _i, _i, _p, _p, _p, _p, _d, _i, _p, _p, _p, _p, _p, _sz, _p]),

@@ -454,6 +454,72 @@ void launch_conv1d(const ConvArgs &a, dim3 grid, int ct, hipStream_t s)
     else conv1d_kernel<4, KW, STRIDE, FUSE1><<<grid, 64 * kCvWaves, 0, s>>>(a);
 }
 
+// Shape checks and sequence chunking of one call (host arithmetic only, shared with pof_conv1d_plan).
+// 32-bit byte offsets per lane inside one launch: sequences go in chunks of < 2^30 input elements
+int conv_shape(int S, int Ci, int Co, int L, int kernel, int stride, int pool, bool fused, int *Lc, int *Lout,
+               int *s_max)
+{
+    if (S < 0 || Ci < 1 || Co < 1 || L < 1) return POF_E_BADARG;
+    if (fused && (kernel != 3 || stride != 1 || Ci > 128)) return POF_E_SHAPE;
+    if (!((kernel == 3 && (stride == 1 || stride == 2)) || (kernel == 1 && stride == 1))) return POF_E_SHAPE;
+    *Lc = stride == 1 ? L : (L + 1) / 2;                 // (L + 2 pad - kernel) / stride + 1 with pad = kernel / 2
+    if (pool && (stride != 1 || *Lc < 2 || (*Lc & 1))) return POF_E_SHAPE;   // pooled pairs sit on adjacent lanes: even L
+    *Lout = pool ? *Lc / 2 : *Lc;
+    const long long per_seq = (long long)Ci * L;
+    if (per_seq >= (1LL << 30)) return POF_E_SHAPE;
+    *s_max = (int)std::max<long long>(1, std::min<long long>(S, ((1LL << 30) - 1) / per_seq));
+    return POF_OK;
+}
+
+// The kernel form of one launch of S sequences (host arithmetic only, shared with pof_conv1d_plan).
+struct ConvForm {
+    bool splitk;
+    int ct;                   // 32-channel tiles per workgroup: 1, 2 or 4
+    long long gx;             // grid.x
+};
+
+int conv_form(int S, int Ci, int Co, int Lc, int kernel, int stride, bool fused, ConvForm *f)
+{
+    const long long ncol = (long long)S * Lc;
+    const long long tiles = (ncol + 31) / 32;
+    const long long gx = (tiles + kCvWaves - 1) / kCvWaves;
+    if (gx > 0x7fffffffLL) return POF_E_SHAPE;
+    // output channels per workgroup: 128 (64 for the narrow layers) when the launch gives every SIMD a wave
+    // (one wave's four independent accumulators already keep its MFMA pipe busy).  A smaller launch
+    // (streaming inference: a few dozen column tiles) leaves SIMDs idle and is bound by one wave's serial
+    // K loop, so it takes narrower channel groups -- more and proportionally shorter workgroups, same
+    // summation order, bit-identical results
+    int ct = Co <= 32 ? 1 : (Co <= 64 ? 2 : 4);
+    while (ct > 1 && gx * ((Co + 32 * ct - 1) / (32 * ct)) < kCvFillWorkgroups) ct >>= 1;
+    // fewer than two resident rounds of 128-channel workgroups (4 per CU x 256 CUs): the last, partly filled round
+    // costs a whole round -- 64-channel workgroups quantise finer (measured at S = 3600, one scan of a training
+    // batch: 256 -> 256 L = 14 0.234 -> 0.218 ms, 512 -> 256 L = 14 0.425 -> 0.390, 256 -> 128 L = 28 0.214 -> 0.195),
+    // at equal summation order
+    if (ct == 4 && gx * ((Co + 127) / 128) < 8 * kCvFillWorkgroups) ct = 2;
+    { static const int force = [] { const char *e = getenv("POF_CONV_CT"); return e ? atoi(e) : 0; }();
+      if (force == 1 || force == 2 || force == 4) ct = (Co <= 32 && force > 1) ? 1 : (Co <= 64 && force > 2) ? 2 : force; }
+    const long long wgs = gx * ((Co + 32 * ct - 1) / (32 * ct));
+    const int nchunk = (Ci + kCvCC - 1) / kCvCC;
+    if (!fused && kernel == 3 && stride == 1 && wgs < 2 * kCvFillWorkgroups && Ci >= Co && nchunk >= 8 * kCvWaves &&
+        tiles <= 0x7fffffffLL) {
+        // still a launch that leaves most SIMDs with at most one wave, and a K loop long enough to pay for
+        // the reduction (Ci >= 128; measured at one scan per call: 512->256 L=7 92 -> 58 us, 256->128 L=7
+        // 43 -> 19 us, 256->256 L=14 52 -> 45 us; the widening layers Co = 2 Ci and Ci = 64 lose 10-50 %
+        // to it and keep the one-wave-per-tile form): split K over the workgroup's waves
+        // the partial sums go through LDS: 32 or 64 channels per workgroup.  With a very long K (Ci >= 512) the
+        // 64-channel form wins even when the 32-channel one fills more SIMDs -- two MFMAs per A-operand read
+        // instead of one over 96+ k-steps per wave (512 -> 256, L = 7, one scan: 57 -> 45 us)
+        f->splitk = true;
+        f->ct = (ct > 2 || (nchunk >= 32 * kCvWaves && Co >= 64)) ? 2 : ct;
+        f->gx = tiles;
+    } else {
+        f->splitk = false;
+        f->ct = ct;
+        f->gx = gx;
+    }
+    return POF_OK;
+}
+
 // l1 != nullptr: x is the single-channel input [S][L] and the Ci input channels of this (k = 3, stride 1) convolution
 // are the first layer's outputs, computed in the kernel (ConvArgs::l1)
 int conv1d_bn_lrelu(const float *x, const float *wt, const float *scale, const float *shift, int S, int Ci, int Co,
@@ -461,17 +527,12 @@ int conv1d_bn_lrelu(const float *x, const float *wt, const float *scale, const f
                     const float *l1 = nullptr, double slope1 = 0.0)
 {
     if (!x || !wt || !scale || !shift || !out) return POF_E_BADARG;
-    if (S < 0 || Ci < 1 || Co < 1 || L < 1) return POF_E_BADARG;
-    if (l1 && (kernel != 3 || stride != 1 || Ci > 128 || !(slope1 >= 0.0 && slope1 <= 1.0))) return POF_E_SHAPE;
-    if (!((kernel == 3 && (stride == 1 || stride == 2)) || (kernel == 1 && stride == 1))) return POF_E_SHAPE;
-    const int Lc = stride == 1 ? L : (L + 1) / 2;         // (L + 2 pad - kernel) / stride + 1 with pad = kernel / 2
-    if (pool && (stride != 1 || Lc < 2 || (Lc & 1))) return POF_E_SHAPE;   // pooled pairs sit on adjacent lanes: even L
+    int Lc, Lout, s_max;
+    const int rc = conv_shape(S, Ci, Co, L, kernel, stride, pool, l1 != nullptr, &Lc, &Lout, &s_max);
+    if (rc != POF_OK) return rc;
+    if (l1 && !(slope1 >= 0.0 && slope1 <= 1.0)) return POF_E_SHAPE;
     if (S == 0) return POF_OK;
-    // 32-bit byte offsets per lane inside one launch: sequences go in chunks of < 2^30 input elements
     const long long per_seq = (long long)Ci * L;
-    if (per_seq >= (1LL << 30)) return POF_E_SHAPE;
-    const int s_max = (int)std::min<long long>(S, ((1LL << 30) - 1) / per_seq);
-    const int Lout = pool ? Lc / 2 : Lc;
     hipStream_t s = pof_stream(stream);
     for (int s0 = 0; s0 < S; s0 += s_max) {
         ConvArgs a;
@@ -481,45 +542,18 @@ int conv1d_bn_lrelu(const float *x, const float *wt, const float *scale, const f
         a.Ci = Ci; a.Co = Co; a.L = L; a.Lc = Lc; a.pool = pool ? 1 : 0; a.slope = (float)negative_slope;
         a.l1 = l1; a.slope1 = (float)slope1;
         if (l1) a.x = x + (long long)s0 * L;              // one input channel
-        const long long ncol = (long long)a.S * Lc;
-        const long long tiles = (ncol + 31) / 32;
-        const long long gx = (tiles + kCvWaves - 1) / kCvWaves;
-        if (gx > 0x7fffffffLL) return POF_E_SHAPE;
-        // output channels per workgroup: 128 (64 for the narrow layers) when the launch gives every SIMD a wave
-        // (one wave's four independent accumulators already keep its MFMA pipe busy).  A smaller launch
-        // (streaming inference: a few dozen column tiles) leaves SIMDs idle and is bound by one wave's serial
-        // K loop, so it takes narrower channel groups -- more and proportionally shorter workgroups, same
-        // summation order, bit-identical results
-        int ct = Co <= 32 ? 1 : (Co <= 64 ? 2 : 4);
-        while (ct > 1 && gx * ((Co + 32 * ct - 1) / (32 * ct)) < kCvFillWorkgroups) ct >>= 1;
-        // fewer than two resident rounds of 128-channel workgroups (4 per CU x 256 CUs): the last, partly filled round
-        // costs a whole round -- 64-channel workgroups quantise finer (measured at S = 3600, one scan of a training
-        // batch: 256 -> 256 L = 14 0.234 -> 0.218 ms, 512 -> 256 L = 14 0.425 -> 0.390, 256 -> 128 L = 28 0.214 -> 0.195),
-        // at equal summation order
-        if (ct == 4 && gx * ((Co + 127) / 128) < 8 * kCvFillWorkgroups) ct = 2;
-        { static const int force = [] { const char *e = getenv("POF_CONV_CT"); return e ? atoi(e) : 0; }();
-          if (force == 1 || force == 2 || force == 4) ct = (Co <= 32 && force > 1) ? 1 : (Co <= 64 && force > 2) ? 2 : force; }
-        const long long wgs = gx * ((Co + 32 * ct - 1) / (32 * ct));
-        const int nchunk = (Ci + kCvCC - 1) / kCvCC;
-        if (!l1 && kernel == 3 && stride == 1 && wgs < 2 * kCvFillWorkgroups && Ci >= Co && nchunk >= 8 * kCvWaves &&
-            tiles <= 0x7fffffffLL) {
-            // still a launch that leaves most SIMDs with at most one wave, and a K loop long enough to pay for
-            // the reduction (Ci >= 128; measured at one scan per call: 512->256 L=7 92 -> 58 us, 256->128 L=7
-            // 43 -> 19 us, 256->256 L=14 52 -> 45 us; the widening layers Co = 2 Ci and Ci = 64 lose 10-50 %
-            // to it and keep the one-wave-per-tile form): split K over the workgroup's waves
-            // the partial sums go through LDS: 32 or 64 channels per workgroup.  With a very long K (Ci >= 512) the
-            // 64-channel form wins even when the 32-channel one fills more SIMDs -- two MFMAs per A-operand read
-            // instead of one over 96+ k-steps per wave (512 -> 256, L = 7, one scan: 57 -> 45 us)
-            const int cts = (ct > 2 || (nchunk >= 32 * kCvWaves && Co >= 64)) ? 2 : ct;
-            const dim3 grid((unsigned)tiles, (Co + 32 * cts - 1) / (32 * cts));
-            if (cts == 1) conv3_splitk_kernel<1><<<grid, 64 * kCvWaves, 0, s>>>(a);
+        ConvForm f;
+        const int frc = conv_form(a.S, Ci, Co, Lc, kernel, stride, l1 != nullptr, &f);
+        if (frc != POF_OK) return frc;
+        const dim3 grid((unsigned)f.gx, (Co + 32 * f.ct - 1) / (32 * f.ct));
+        if (f.splitk) {
+            if (f.ct == 1) conv3_splitk_kernel<1><<<grid, 64 * kCvWaves, 0, s>>>(a);
             else conv3_splitk_kernel<2><<<grid, 64 * kCvWaves, 0, s>>>(a);
         } else {
-            const dim3 grid((unsigned)gx, (Co + 32 * ct - 1) / (32 * ct));
-            if (l1) launch_conv1d<3, 1, true>(a, grid, ct, s);
-            else if (kernel == 1) launch_conv1d<1, 1>(a, grid, ct, s);
-            else if (stride == 2) launch_conv1d<3, 2>(a, grid, ct, s);
-            else launch_conv1d<3, 1>(a, grid, ct, s);
+            if (l1) launch_conv1d<3, 1, true>(a, grid, f.ct, s);
+            else if (kernel == 1) launch_conv1d<1, 1>(a, grid, f.ct, s);
+            else if (stride == 2) launch_conv1d<3, 2>(a, grid, f.ct, s);
+            else launch_conv1d<3, 1>(a, grid, f.ct, s);
         }
         POF_CHECK_LAUNCH();
     }
@@ -551,4 +585,26 @@ extern "C" int pof_conv1d_bn_lrelu(const float *x, const float *wt, const float 
 {
     POF_CLEAR_STALE_ERROR();
     return conv1d_bn_lrelu(x, wt, scale, shift, S, Ci, Co, L, kernel_size, stride, pool, negative_slope, out, stream);
+}
+
+extern "C" int pof_conv1d_plan(int S, int Ci, int Co, int L, int kernel_size, int stride, int pool, int fused_first,
+                               int *split_k, int *channels_per_workgroup, int *launches, int *wide_offsets)
+{
+    if (!split_k || !channels_per_workgroup || !launches || !wide_offsets) return POF_E_BADARG;
+    if (S < 1 || kernel_size < 1 || stride < 1) return POF_E_BADARG;
+    int Lc, Lout, s_max;
+    int rc = conv_shape(S, Ci, Co, L, kernel_size, stride, pool, fused_first != 0, &Lc, &Lout, &s_max);
+    if (rc != POF_OK) return rc;
+    ConvForm f;
+    rc = conv_form(std::min(s_max, S), Ci, Co, Lc, kernel_size, stride, fused_first != 0, &f);
+    if (rc != POF_OK) return rc;
+    *split_k = f.splitk ? 1 : 0;
+    *channels_per_workgroup = 32 * f.ct;
+    *launches = (int)((S + (long long)s_max - 1) / s_max);
+    // launches whose epilogue takes 64-bit output offsets (conv_epilogue's `small` is false)
+    int wide = 0;
+    for (long long s0 = 0; s0 < S; s0 += s_max)
+        wide += std::min<long long>(s_max, S - s0) * Co * Lout >= (1LL << 30);
+    *wide_offsets = wide;
+    return POF_OK;
 }

@@ -237,17 +237,23 @@ void launch_merge(const T *x, const T *tmpl, const float *prob, T *out, T *out2,
         (float)(1.0 - alpha));
 }
 
-template <bool TRANS, typename T>
-int dispatch_merge(int W, const T *x, const T *tmpl, const float *prob, T *out, T *out2, int B,
-                   int N, int F, double alpha, hipStream_t s)
+// segment length of the merge walk (host arithmetic only, shared with pof_spatial_attention_plan): whole scan per
+// lane when the batch alone fills the chip, shorter segments (more workgroups, a little halo re-read) for small batches
+int merge_segment(int B, int N, int F)
 {
-    // segment length: whole scan per lane when the batch alone fills the chip,
-    // shorter segments (more workgroups, a little halo re-read) for small batches
     const long long colblocks = (F / 4 + 127) / 128;
     int L = N;
     // small batches: segments down to 8 points (a 10-row halo per segment re-read from L2) -- at one scan per call the
     // walk is bound by its 105 workgroups, not by bytes: B = 1 forward 37 -> 27 us, B = 8 69 -> 46 us (tools/exp_attn_small.py)
     while (L > 8 && colblocks * ((N + L - 1) / L) * B < 3072) L = (L + 1) / 2;
+    return L;
+}
+
+template <bool TRANS, typename T>
+int dispatch_merge(int W, const T *x, const T *tmpl, const float *prob, T *out, T *out2, int B,
+                   int N, int F, double alpha, hipStream_t s)
+{
+    const int L = merge_segment(B, N, F);
     switch (W) {
         case 1: launch_merge<1, TRANS, T>(x, tmpl, prob, out, out2, B, N, F, L, alpha, s); break;
         case 3: launch_merge<3, TRANS, T>(x, tmpl, prob, out, out2, B, N, F, L, alpha, s); break;
@@ -625,6 +631,18 @@ __global__ __launch_bounds__(256) void attn_dsim_finish_kernel(const float *__re
         dsim[row * W + k] = prob[row * W + k] * (dp[k] - s) + (g_band ? g_band[row * W + k] : 0.0f);
 }
 
+// segment length of the fused backward walk (host arithmetic only, shared with pof_spatial_attention_plan): as for
+// the merge kernel, whole scan per lane when the batch alone fills the chip
+int fused_backward_segment(int B, int N, int F)
+{
+    const long long colblocks = (F / 4 + 127) / 128;
+    int L = N;
+    // the fused walk carries two rings: 16-point segments are its optimum at small batches (B = 1 70 -> 57 us;
+    // 8-point segments lose again at B = 8)
+    while (L > 16 && colblocks * ((N + L - 1) / L) * B < 3072) L = (L + 1) / 2;
+    return L;
+}
+
 template <int W>
 void launch_bwd_fused(const float *g, const float *tmpl, const float *prob, float *d_tmpl, float *d_x, float *partial,
                       int B, int N, int F, int L, double alpha, hipStream_t s)
@@ -668,12 +686,7 @@ extern "C" int pof_spatial_attention_backward_fused(const float *emb_x, const fl
     float *partial = static_cast<float *>(workspace);
     const int ncb = 2 * ((F / 4 + 127) / 128);
     {
-        // segment length as for the merge kernel: whole scan per lane when the batch alone fills the chip
-        const long long colblocks = (F / 4 + 127) / 128;
-        int L = N;
-            // the fused walk carries two rings: 16-point segments are its optimum at small batches (B = 1 70 -> 57 us;
-        // 8-point segments lose again at B = 8)
-        while (L > 16 && colblocks * ((N + L - 1) / L) * B < 3072) L = (L + 1) / 2;
+        const int L = fused_backward_segment(B, N, F);
         switch (W) {
             case 1: launch_bwd_fused<1>(g_out, tmpl, prob, d_tmpl, d_x, partial, B, N, F, L, alpha, s); break;
             case 3: launch_bwd_fused<3>(g_out, tmpl, prob, d_tmpl, d_x, partial, B, N, F, L, alpha, s); break;
@@ -735,5 +748,15 @@ extern "C" int pof_spatial_attention_backward(const float *emb_x, const float *e
     const int rc = dispatch_merge<true, float>(W, static_cast<const float *>(nullptr), g_out, prob, d_tmpl, d_x, B, N, F, alpha, s);
     if (rc != POF_OK) return rc;
     POF_CHECK_LAUNCH();
+    return POF_OK;
+}
+
+extern "C" int pof_spatial_attention_plan(int B, int N, int F, int *forward_segment, int *backward_segment)
+{
+    if (!forward_segment || !backward_segment) return POF_E_BADARG;
+    if (B < 1 || N < 1 || F < 1) return POF_E_BADARG;
+    if (F % 4 != 0 || B > 65535) return POF_E_SHAPE;
+    *forward_segment = merge_segment(B, N, F);
+    *backward_segment = fused_backward_segment(B, N, F);
     return POF_OK;
 }

@@ -545,6 +545,17 @@ def conv1d_bn_lrelu(x, wt, scale, shift, stride=1, pool=False, negative_slope=0.
     return out
 
 
+def conv1d_plan(S, Ci, Co, L, kernel_size=3, stride=1, pool=False, fused_first=False):
+    """Host-only: the kernel form conv3_bn_lrelu / conv1d_bn_lrelu / conv3_first_two (``fused_first``, Ci = C1) would
+    launch for these sizes -> dict(split_k, channels_per_workgroup, launches, wide_offsets); the first two describe the
+    first launch.  No device work."""
+    out = [C.c_int(0) for _ in range(4)]
+    _lib.call("pof_conv1d_plan", int(S), int(Ci), int(Co), int(L), int(kernel_size), int(stride), int(bool(pool)),
+              int(bool(fused_first)), *[C.byref(v) for v in out])
+    return dict(split_k=bool(out[0].value), channels_per_workgroup=out[1].value, launches=out[2].value,
+                wide_offsets=out[3].value)
+
+
 def drow_heads(feat, w_cls, b_cls, w_reg, b_reg):
     """N2 heads (inference): feat [S,C,L] f32, w_cls [n_cls,C], w_reg [2,C] -> (pred_cls [S,n_cls], pred_reg [S,2]):
     mean over positions + both 1x1 convolutions in one launch."""
@@ -876,6 +887,14 @@ def spatial_attention(emb_x, emb_t, x, tmpl, alpha=0.5, window_size=11, out=None
                       _ptr(tmpl[s:s + m]), m, N, E, F, int(window_size), float(alpha), _ptr(band[s:s + m]),
                       _ptr(prob[s:s + m]), _ptr(out[s:s + m]), _stream())
     return out, band, prob
+
+
+def spatial_attention_plan(B, N, F):
+    """Host-only: points per lane segment of one call on B <= 65535 scans -> (forward_segment, backward_segment):
+    the merge walk of spatial_attention (and of the two-pass backward), the fused backward walk.  No device work."""
+    fwd, bwd = C.c_int(0), C.c_int(0)
+    _lib.call("pof_spatial_attention_plan", int(B), int(N), int(F), C.byref(fwd), C.byref(bwd))
+    return fwd.value, bwd.value
 
 
 def band_correlation_backward(feat1, feat2, g_out, kernel_size=3, max_displacement=5):
