@@ -491,6 +491,45 @@ int pof_bn_lrelu_pool_backward(const float *y, const float *dz, long long S, int
                                float *dgamma, float *dbeta, float *dbias_in, void *workspace,
                                size_t workspace_bytes, pof_stream_t stream);
 
+/* ----------------------------------------------------------------------
+ * N2 trunk unit tail, training, GLOBAL-batch statistics             SURVEY 8(e)
+ * (no reference site: the reference has no data parallelism.)  The tail above cut in two at
+ * the per-channel sums, so that the ranks of a data-parallel job can add theirs between the
+ * calls; everything else -- shapes, pool modes, groups, workspace size
+ * (pof_bn_lrelu_pool_workspace_bytes of the LOCAL S), alignment -- is as above.  Exchange
+ * buffers, float64, one all-reduce(sum) each:
+ *   stat [groups][2C + 1] = sum y [C] | sum y^2 [C] | count (= S / groups * L, written by the kernel)
+ *   red  [groups][2C]     = sum dU [C] | sum dU * xhat [C]      (undivided)
+ * pof_bn_sync_forward_stats:   y -> stat (this rank's sums and count).
+ * pof_bn_sync_forward_apply:   stat (summed over the ranks) -> save_mean / save_invstd [groups][C]
+ *   (mean and biased variance over the global count), running statistics updated with the
+ *   unbiased variance over the global count, once per group in order; out as in the one-shot form.
+ * pof_bn_sync_backward_reduce: y, dz -> red (this rank's sums), dgamma / dbeta [C] of THIS rank's
+ *   samples (a gradient all-reduce averages them like every other parameter gradient).
+ * pof_bn_sync_backward_apply:  red (summed over the ranks) and stat (for the global count) ->
+ *   dy [S][C][L]; dbias_in [C] (may be NULL) = this rank's sum of dy over (S, L).
+ * With exchange buffers left as the first call of each pair wrote them (one rank), out,
+ * save_mean, save_invstd, the running statistics, dy, dgamma, dbeta and dbias_in have the bits
+ * of pof_bn_lrelu_pool_forward / _backward.
+ * ---------------------------------------------------------------------- */
+int pof_bn_sync_forward_stats(const float *y, long long S, int C, int L, int groups, double *stat,
+                              void *workspace, size_t workspace_bytes, pof_stream_t stream);
+int pof_bn_sync_forward_apply(const float *y, long long S, int C, int L, int groups, const double *stat,
+                              const float *gamma, const float *beta, float *running_mean,
+                              float *running_var, double momentum, double eps, double negative_slope,
+                              int pool, float *out, float *save_mean, float *save_invstd,
+                              void *workspace, size_t workspace_bytes, pof_stream_t stream);
+int pof_bn_sync_backward_reduce(const float *y, const float *dz, long long S, int C, int L, int groups,
+                                const float *gamma, const float *beta, const float *save_mean,
+                                const float *save_invstd, double negative_slope, int pool, double *red,
+                                float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                pof_stream_t stream);
+int pof_bn_sync_backward_apply(const float *y, const float *dz, long long S, int C, int L, int groups,
+                               const float *gamma, const float *beta, const float *save_mean,
+                               const float *save_invstd, const double *red, const double *stat,
+                               double negative_slope, int pool, float *dy, float *dbias_in,
+                               void *workspace, size_t workspace_bytes, pof_stream_t stream);
+
 /* The trunk's first TWO units in one launch (inference): x [S][L] float32 is the single-channel
  * cutout (dr_spaam.py:86-92, conv_block_1[0] and [1]); the C1 channels of the first unit,
  * lrelu_slope1(a0 x[q-1] + a1 x[q] + a2 x[q+1] + b) with l1[c] = {a0, a1, a2, b} (its taps times its

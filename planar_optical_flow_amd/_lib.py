@@ -64,6 +64,10 @@ SIGNATURES = {
     "pof_bn_lrelu_pool_workspace_bytes": (_sz, [_ll, _i, _i, _i]),
     "pof_bn_lrelu_pool_forward": (_i, [_p, _ll, _i, _i, _i, _p, _p, _p, _p, _d, _d, _d, _i, _p, _p, _p, _p, _sz, _p]),
     "pof_bn_lrelu_pool_backward": (_i, [_p, _p, _ll, _i, _i, _i, _p, _p, _p, _p, _d, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "pof_bn_sync_forward_stats": (_i, [_p, _ll, _i, _i, _i, _p, _p, _sz, _p]),
+    "pof_bn_sync_forward_apply": (_i, [_p, _ll, _i, _i, _i, _p, _p, _p, _p, _p, _d, _d, _d, _i, _p, _p, _p, _p, _sz, _p]),
+    "pof_bn_sync_backward_reduce": (_i, [_p, _p, _ll, _i, _i, _i, _p, _p, _p, _p, _d, _i, _p, _p, _p, _p, _sz, _p]),
+    "pof_bn_sync_backward_apply": (_i, [_p, _p, _ll, _i, _i, _i, _p, _p, _p, _p, _p, _p, _d, _i, _p, _p, _p, _sz, _p]),
     "pof_conv3_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pof_conv3_wgrad": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "pof_conv3_first_two": (_i, [_p, _p, _d, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p]),

@@ -424,6 +424,102 @@ __global__ __launch_bounds__(kBnThreads) void bn_sum_final_kernel(const double2 
     if (threadIdx.x == 0) out[c] = (float)acc.x;
 }
 
+// ---- split ("sync") form: the same passes with the per-channel sums handed out between "reduce" and "finish", so that
+// ranks of a data-parallel job can add theirs.  Exchange buffers, float64:
+//   stat [G][2C + 1] = sum x [C] | sum x^2 [C] | count      red [G][2C] = sum dU [C] | sum dU * xhat [C]
+// The collect kernels add the chunk partials in bn_finalize_kernel's / bn_bwd_final_kernel's order, and the finish
+// kernels use their operations, so an exchange buffer that nobody touched reproduces the one-shot form bit for bit.
+__global__ __launch_bounds__(kBnThreads) void bn_sync_stats_collect_kernel(const double2 *__restrict__ partial,
+                                                                           BnGeo g, double *__restrict__ stat)
+{
+    __shared__ double2 s_w[kBnThreads / 64];
+    const int c = blockIdx.x;
+    for (int grp = 0; grp < g.G; ++grp) {
+        double2 acc = make_double2(0.0, 0.0);
+        const double2 *p = partial + (long long)c * g.nchunk + grp * g.ncg;
+        for (long long i = threadIdx.x; i < g.ncg; i += kBnThreads) { acc.x += p[i].x; acc.y += p[i].y; }
+        acc = block_sum2(acc, s_w);
+        if (threadIdx.x == 0) {
+            double *o = stat + (long long)grp * (2 * g.C + 1);
+            o[c] = acc.x;
+            o[g.C + c] = acc.y;
+            if (c == 0) o[2 * g.C] = (double)g.Sg * g.L;       // written here: no host-to-device copy (capturable)
+        }
+        __syncthreads();      // s_w is reused by the next group
+    }
+}
+
+// one thread per channel: mean, 1/std, scale, shift and the running statistics from the (global) sums and count
+__global__ __launch_bounds__(kBnThreads) void bn_sync_finalize_kernel(const double *__restrict__ stat, int G, int C,
+                                                                      const float *gamma, const float *beta,
+                                                                      float *running_mean, float *running_var,
+                                                                      double momentum, double eps, float *save_mean,
+                                                                      float *save_invstd, float *scale, float *shift)
+{
+    const int c = blockIdx.x * kBnThreads + threadIdx.x;
+    if (c >= C) return;
+    float rm = running_mean ? running_mean[c] : 0.0f, rv = running_var ? running_var[c] : 0.0f;
+    for (int grp = 0; grp < G; ++grp) {
+        const double *in = stat + (long long)grp * (2 * C + 1);
+        const double n = in[2 * C];
+        double2 acc = make_double2(in[c], in[C + c]);
+        const double mean = acc.x / n;
+        double var = acc.y / n - mean * mean;
+        var = var > 0.0 ? var : 0.0;
+        const float invstd = (float)(1.0 / sqrt(var + eps));
+        const float m = (float)mean;
+        const float sc = gamma[c] * invstd;
+        const int o = grp * C + c;
+        save_mean[o] = m;
+        save_invstd[o] = invstd;
+        scale[o] = sc;
+        shift[o] = fmaf(-m, sc, beta[c]);
+        const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
+        rm = (float)((1.0 - momentum) * rm + momentum * mean);
+        rv = (float)((1.0 - momentum) * rv + momentum * unbiased);
+    }
+    if (running_mean) running_mean[c] = rm;
+    if (running_var) running_var[c] = rv;
+}
+
+__global__ __launch_bounds__(kBnThreads) void bn_sync_bwd_collect_kernel(const double2 *__restrict__ partial, BnGeo g,
+                                                                         double *__restrict__ red, float *dgamma,
+                                                                         float *dbeta)
+{
+    __shared__ double2 s_w[kBnThreads / 64];
+    const int c = blockIdx.x;
+    double tot_a = 0.0, tot_b = 0.0;
+    for (int grp = 0; grp < g.G; ++grp) {
+        double2 acc = make_double2(0.0, 0.0);
+        const double2 *p = partial + (long long)c * g.nchunk + grp * g.ncg;
+        for (long long i = threadIdx.x; i < g.ncg; i += kBnThreads) { acc.x += p[i].x; acc.y += p[i].y; }
+        acc = block_sum2(acc, s_w);
+        if (threadIdx.x == 0) {
+            red[(long long)grp * 2 * g.C + c] = acc.x;
+            red[(long long)grp * 2 * g.C + g.C + c] = acc.y;
+            tot_a += acc.x;
+            tot_b += acc.y;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        dbeta[c] = (float)tot_a;       // this rank's share: the gradient bucket averages them over the ranks
+        dgamma[c] = (float)tot_b;
+    }
+}
+
+__global__ __launch_bounds__(kBnThreads) void bn_sync_bwd_means_kernel(const double *__restrict__ red,
+                                                                       const double *__restrict__ stat, int G, int C,
+                                                                       float *k1, float *k2)
+{
+    const int i = blockIdx.x * kBnThreads + threadIdx.x;
+    if (i >= G * C) return;
+    const int grp = i / C, c = i - grp * C;
+    const double n = stat[(long long)grp * (2 * C + 1) + 2 * C];
+    k1[i] = (float)(red[(long long)grp * 2 * C + c] / n);
+    k2[i] = (float)(red[(long long)grp * 2 * C + C + c] / n);
+}
+
 // workspace: double2 partial[C * nchunk_max] | float coef[4 * G * C]
 constexpr int kStatsWgs = 4096, kStatsK = 64;      // reductions: few partial sums
 constexpr int kStreamWgs = 8192, kStreamK = 16;  // element-wise passes: short loops, many workgroups
@@ -511,6 +607,115 @@ extern "C" int pof_bn_lrelu_pool_backward(const float *y, const float *dz, long 
 #undef POF_REDUCE
     POF_CHECK_LAUNCH();
     bn_bwd_final_kernel<<<C, kBnThreads, 0, st>>>(partial, gs, dgamma, dbeta, k1, k2);
+    POF_CHECK_LAUNCH();
+#define POF_DGRAD(P_, D_) bn_bwd_dgrad_kernel<P_, D_><<<dgrid, kBnThreads, 0, st>>>( \
+        y, dz, ga, gamma, beta, save_mean, save_invstd, k1, k2, slope, dy, partial)
+    if (dbias_in) { if (pool == 2) POF_DGRAD(2, true); else if (pool) POF_DGRAD(1, true); else POF_DGRAD(0, true); }
+    else { if (pool == 2) POF_DGRAD(2, false); else if (pool) POF_DGRAD(1, false); else POF_DGRAD(0, false); }
+#undef POF_DGRAD
+    POF_CHECK_LAUNCH();
+    if (dbias_in) {
+        bn_sum_final_kernel<<<C, kBnThreads, 0, st>>>(partial, ga.nchunk, dbias_in);
+        POF_CHECK_LAUNCH();
+    }
+    return POF_OK;
+}
+
+extern "C" int pof_bn_sync_forward_stats(const float *y, long long S, int C, int L, int groups, double *stat,
+                                         void *workspace, size_t workspace_bytes, pof_stream_t stream)
+{
+    POF_CLEAR_STALE_ERROR();
+    if (!y || !stat || !workspace) return POF_E_BADARG;
+    BnGeo gs, ga;
+    if (!make_geo(S, C, L, groups, kStatsWgs, kStatsK, &gs) || !make_geo(S, C, L, groups, kStreamWgs, kStreamK, &ga))
+        return POF_E_SHAPE;
+    if (workspace_bytes < workspace_need(gs, ga)) return POF_E_WORKSPACE;
+    double2 *partial = static_cast<double2 *>(workspace);
+    hipStream_t st = pof_stream(stream);
+    bn_stats_kernel<<<dim3((unsigned)gs.nchunk, gs.nslice), kBnThreads, 0, st>>>(y, gs, partial);
+    POF_CHECK_LAUNCH();
+    bn_sync_stats_collect_kernel<<<C, kBnThreads, 0, st>>>(partial, gs, stat);
+    POF_CHECK_LAUNCH();
+    return POF_OK;
+}
+
+extern "C" int pof_bn_sync_forward_apply(const float *y, long long S, int C, int L, int groups, const double *stat,
+                                         const float *gamma, const float *beta, float *running_mean,
+                                         float *running_var, double momentum, double eps, double negative_slope,
+                                         int pool, float *out, float *save_mean, float *save_invstd, void *workspace,
+                                         size_t workspace_bytes, pof_stream_t stream)
+{
+    POF_CLEAR_STALE_ERROR();
+    if (!y || !stat || !gamma || !beta || !out || !save_mean || !save_invstd || !workspace) return POF_E_BADARG;
+    BnGeo gs, ga;
+    if (!make_geo(S, C, L, groups, kStatsWgs, kStatsK, &gs) || !make_geo(S, C, L, groups, kStreamWgs, kStreamK, &ga))
+        return POF_E_SHAPE;
+    if (!pool_ok(pool, L)) return POF_E_SHAPE;
+    if (!(eps >= 0.0)) return POF_E_BADARG;
+    if (workspace_bytes < workspace_need(gs, ga)) return POF_E_WORKSPACE;
+    float *coef = reinterpret_cast<float *>(static_cast<char *>(workspace) + workspace_need(gs, ga)) - 4 * groups * C;
+    float *scale = coef, *shift = coef + groups * C;
+    hipStream_t st = pof_stream(stream);
+    bn_sync_finalize_kernel<<<(C + kBnThreads - 1) / kBnThreads, kBnThreads, 0, st>>>(
+        stat, groups, C, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, scale, shift);
+    POF_CHECK_LAUNCH();
+    const dim3 grid((unsigned)ga.nchunk, ga.nslice);
+    if (pool == 2) bn_apply_kernel<2><<<grid, kBnThreads, 0, st>>>(y, ga, scale, shift, (float)negative_slope, out);
+    else if (pool) bn_apply_kernel<1><<<grid, kBnThreads, 0, st>>>(y, ga, scale, shift, (float)negative_slope, out);
+    else bn_apply_kernel<0><<<grid, kBnThreads, 0, st>>>(y, ga, scale, shift, (float)negative_slope, out);
+    POF_CHECK_LAUNCH();
+    return POF_OK;
+}
+
+extern "C" int pof_bn_sync_backward_reduce(const float *y, const float *dz, long long S, int C, int L, int groups,
+                                           const float *gamma, const float *beta, const float *save_mean,
+                                           const float *save_invstd, double negative_slope, int pool, double *red,
+                                           float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                           pof_stream_t stream)
+{
+    POF_CLEAR_STALE_ERROR();
+    if (!y || !dz || !gamma || !beta || !save_mean || !save_invstd || !red || !dgamma || !dbeta || !workspace)
+        return POF_E_BADARG;
+    BnGeo gs, ga;
+    if (!make_geo(S, C, L, groups, kStatsWgs, kStatsK, &gs) || !make_geo(S, C, L, groups, kStreamWgs, kStreamK, &ga))
+        return POF_E_SHAPE;
+    if (!pool_ok(pool, L)) return POF_E_SHAPE;
+    if (workspace_bytes < workspace_need(gs, ga)) return POF_E_WORKSPACE;
+    double2 *partial = static_cast<double2 *>(workspace);
+    const float slope = (float)negative_slope;
+    hipStream_t st = pof_stream(stream);
+    const dim3 rgrid((unsigned)gs.nchunk, gs.nslice);
+#define POF_REDUCE(P_) bn_bwd_reduce_kernel<P_><<<rgrid, kBnThreads, 0, st>>>(y, dz, gs, gamma, beta, save_mean, save_invstd, slope, partial)
+    if (pool == 2) POF_REDUCE(2); else if (pool) POF_REDUCE(1); else POF_REDUCE(0);
+#undef POF_REDUCE
+    POF_CHECK_LAUNCH();
+    bn_sync_bwd_collect_kernel<<<C, kBnThreads, 0, st>>>(partial, gs, red, dgamma, dbeta);
+    POF_CHECK_LAUNCH();
+    return POF_OK;
+}
+
+extern "C" int pof_bn_sync_backward_apply(const float *y, const float *dz, long long S, int C, int L, int groups,
+                                          const float *gamma, const float *beta, const float *save_mean,
+                                          const float *save_invstd, const double *red, const double *stat,
+                                          double negative_slope, int pool, float *dy, float *dbias_in,
+                                          void *workspace, size_t workspace_bytes, pof_stream_t stream)
+{
+    POF_CLEAR_STALE_ERROR();
+    if (!y || !dz || !gamma || !beta || !save_mean || !save_invstd || !red || !stat || !dy || !workspace)
+        return POF_E_BADARG;
+    BnGeo gs, ga;
+    if (!make_geo(S, C, L, groups, kStatsWgs, kStatsK, &gs) || !make_geo(S, C, L, groups, kStreamWgs, kStreamK, &ga))
+        return POF_E_SHAPE;
+    if (!pool_ok(pool, L)) return POF_E_SHAPE;
+    if (workspace_bytes < workspace_need(gs, ga)) return POF_E_WORKSPACE;
+    double2 *partial = static_cast<double2 *>(workspace);
+    float *coef = reinterpret_cast<float *>(static_cast<char *>(workspace) + workspace_need(gs, ga)) - 4 * groups * C;
+    float *k1 = coef + 2 * groups * C, *k2 = coef + 3 * groups * C;
+    const float slope = (float)negative_slope;
+    hipStream_t st = pof_stream(stream);
+    const dim3 dgrid((unsigned)ga.nchunk, ga.nslice);
+    bn_sync_bwd_means_kernel<<<(groups * C + kBnThreads - 1) / kBnThreads, kBnThreads, 0, st>>>(red, stat, groups, C,
+                                                                                                k1, k2);
     POF_CHECK_LAUNCH();
 #define POF_DGRAD(P_, D_) bn_bwd_dgrad_kernel<P_, D_><<<dgrid, kBnThreads, 0, st>>>( \
         y, dz, ga, gamma, beta, save_mean, save_invstd, k1, k2, slope, dy, partial)

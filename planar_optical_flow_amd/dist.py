@@ -160,6 +160,20 @@ def any_rank(flag, device=None):
     return bool(t.item() > 0)
 
 
+def all_reduce_sum_f64(t):
+    """Sum the small float64 device buffer `t` over the ranks, in place (the per-channel sums of the global-batch
+    BatchNorm tail).  RCCL: the collective on the device tensor -- stream-ordered, no host synchronisation,
+    capturable.  Any other backend: staged through a CPU tensor as `any_rank` does, which is what lets several ranks
+    share one GPU over gloo."""
+    if dist.get_backend() == "nccl":
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    else:
+        host = t.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM)
+        t.copy_(host)
+    return t
+
+
 class _SyncBatchNormFn(torch.autograd.Function):
     """BatchNorm over the GLOBAL batch: per-channel sum / sum of squares (2C + 1 numbers, float64) are all-reduced
     in the forward, per-channel sum(dy) / sum(dy * xhat) (2C numbers) in the backward.  Works on any backend
@@ -216,6 +230,12 @@ class SyncBatchNorm1d(torch.nn.BatchNorm1d):
         momentum = self.momentum if self.momentum is not None else 1.0 / float(self.num_batches_tracked)
         return _SyncBatchNormFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
                                       momentum)
+
+
+def sync_bn_active(bn):
+    """True when `bn` is a SyncBatchNorm1d whose training-mode forward takes global-batch statistics: it tracks
+    running statistics and a process group is initialised (one rank included)."""
+    return isinstance(bn, SyncBatchNorm1d) and bn.track_running_stats and dist.is_available() and dist.is_initialized()
 
 
 def convert_sync_batchnorm(module):

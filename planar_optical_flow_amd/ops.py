@@ -723,6 +723,98 @@ def bn_lrelu_pool_backward(y, dz, gamma, beta, save_mean, save_invstd, negative_
     return (dy, dgamma, dbeta, dbias) if bias_grad else (dy, dgamma, dbeta)
 
 
+def _bn_sync_shape(y, pool, groups):
+    y = _dev(y, torch.float32, "y")
+    S, C, L = y.shape
+    pool = int(pool)
+    if not bn_lrelu_pool_supported(S, C, L, pool, groups):
+        raise ValueError("bn_sync: unsupported shape S=%d C=%d L=%d groups=%d pool mode %d" % (S, C, L, groups, pool))
+    return y, S, C, L, pool
+
+
+def bn_sync_forward_stats(y, groups=1):
+    """First half of the global-batch tail: y [S,C,L] f32 -> stat [groups*(2C+1)] f64, per group
+    sum y [C] | sum y^2 [C] | count.  The ranks add their ``stat`` (one all-reduce) before bn_sync_forward_apply."""
+    y, S, C, L, _ = _bn_sync_shape(y, 0, groups)
+    ws, nbytes = _bn_workspace(S, C, L, groups, y.device)
+    stat = torch.empty(groups * (2 * C + 1), dtype=torch.float64, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.call("pof_bn_sync_forward_stats", _ptr(y), S, C, L, int(groups), _ptr(stat), _ptr(ws), nbytes, _stream())
+    return stat
+
+
+def bn_sync_forward_apply(y, stat, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5,
+                          negative_slope=0.1, pool=False, groups=1):
+    """Second half: the summed ``stat`` -> (z, save_mean [groups*C], save_invstd [groups*C]) as bn_lrelu_pool_forward
+    gives them, the statistics being those of the global batch; the running statistics are updated in place with the
+    unbiased variance over the global count."""
+    y, S, C, L, pool = _bn_sync_shape(y, pool, groups)
+    gamma = _dev(gamma, torch.float32, "gamma")
+    beta = _dev(beta, torch.float32, "beta")
+    if gamma.numel() != C or beta.numel() != C:
+        raise ValueError("gamma / beta must have C entries")
+    if _dev(stat, torch.float64, "stat").numel() != groups * (2 * C + 1):
+        raise ValueError("stat must have groups * (2C + 1) entries")
+    for name, t in (("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None and (_dev(t, torch.float32, name).numel() != C):
+            raise ValueError("%s must have C entries" % name)
+    ws, nbytes = _bn_workspace(S, C, L, groups, y.device)
+    out = torch.empty((S, C) if pool == 2 else (S, C, L // 2 if pool else L), dtype=torch.float32, device=y.device)
+    mean = torch.empty(groups * C, dtype=torch.float32, device=y.device)
+    invstd = torch.empty(groups * C, dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.call("pof_bn_sync_forward_apply", _ptr(y), S, C, L, int(groups), _ptr(stat), _ptr(gamma), _ptr(beta),
+                  _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), float(negative_slope), pool,
+                  _ptr(out), _ptr(mean), _ptr(invstd), _ptr(ws), nbytes, _stream())
+    return out, mean, invstd
+
+
+def _bn_sync_backward_args(y, dz, gamma, beta, save_mean, save_invstd, pool, groups):
+    y, S, C, L, pool = _bn_sync_shape(y, pool, groups)
+    dz = _dev(dz, torch.float32, "dz")
+    if tuple(dz.shape) != ((S, C) if pool == 2 else (S, C, L // 2 if pool else L)):
+        raise ValueError("dz must be [S, C%s]" % ("" if pool == 2 else ", L//2" if pool else ", L"))
+    for name, t, n in (("gamma", gamma, C), ("beta", beta, C), ("save_mean", save_mean, groups * C),
+                       ("save_invstd", save_invstd, groups * C)):
+        if _dev(t, torch.float32, name).numel() != n:
+            raise ValueError("%s must have %d entries" % (name, n))
+    return y, dz, S, C, L, pool
+
+
+def bn_sync_backward_reduce(y, dz, gamma, beta, save_mean, save_invstd, negative_slope=0.1, pool=False, groups=1):
+    """First half of the backward pass: -> (red [groups*2C] f64 = per group sum dU [C] | sum dU*xhat [C], undivided;
+    dgamma [C], dbeta [C] of this rank's samples).  The ranks add their ``red`` before bn_sync_backward_apply."""
+    y, dz, S, C, L, pool = _bn_sync_backward_args(y, dz, gamma, beta, save_mean, save_invstd, pool, groups)
+    ws, nbytes = _bn_workspace(S, C, L, groups, y.device)
+    red = torch.empty(groups * 2 * C, dtype=torch.float64, device=y.device)
+    dgamma = torch.empty(C, dtype=torch.float32, device=y.device)
+    dbeta = torch.empty(C, dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.call("pof_bn_sync_backward_reduce", _ptr(y), _ptr(dz), S, C, L, int(groups), _ptr(gamma), _ptr(beta),
+                  _ptr(save_mean), _ptr(save_invstd), float(negative_slope), pool, _ptr(red), _ptr(dgamma),
+                  _ptr(dbeta), _ptr(ws), nbytes, _stream())
+    return red, dgamma, dbeta
+
+
+def bn_sync_backward_apply(y, dz, gamma, beta, save_mean, save_invstd, red, stat, negative_slope=0.1, pool=False,
+                           bias_grad=False, groups=1):
+    """Second half: the summed ``red`` and the forward's summed ``stat`` (for the global count) -> dy [S,C,L] and, with
+    ``bias_grad``, (dy, sum(dy) over (S, L) [C])."""
+    y, dz, S, C, L, pool = _bn_sync_backward_args(y, dz, gamma, beta, save_mean, save_invstd, pool, groups)
+    if _dev(red, torch.float64, "red").numel() != groups * 2 * C:
+        raise ValueError("red must have groups * 2C entries")
+    if _dev(stat, torch.float64, "stat").numel() != groups * (2 * C + 1):
+        raise ValueError("stat must have groups * (2C + 1) entries")
+    ws, nbytes = _bn_workspace(S, C, L, groups, y.device)
+    dy = torch.empty_like(y)
+    dbias = torch.empty(C, dtype=torch.float32, device=y.device) if bias_grad else None
+    with torch.cuda.device(y.device):
+        _lib.call("pof_bn_sync_backward_apply", _ptr(y), _ptr(dz), S, C, L, int(groups), _ptr(gamma), _ptr(beta),
+                  _ptr(save_mean), _ptr(save_invstd), _ptr(red), _ptr(stat), float(negative_slope), pool, _ptr(dy),
+                  _ptr(dbias), _ptr(ws), nbytes, _stream())
+    return (dy, dbias) if bias_grad else dy
+
+
 def segment_inputs(points, centers, oris, radius=0.4, input_size=64, min_segment_size=5, seed=0,
                    return_mask=False):
     """N3: points [Np,D] f64, centers [S,D] f64, oris [S] f64 -> (x [S,input_size,D+1] f32, count [S] i32

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from planar_optical_flow_amd import ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.pof.*)
+from planar_optical_flow_amd.dist import sync_bn_active
 
 
 def flow_loss(pred, target, mask=None):
@@ -119,6 +120,7 @@ class DROW(nn.Module):
     pred_reg [B, n_cutout, 2]); the scans of a window are fused by summation (:41-121)."""
 
     _TRUNK = ((1, 64, 64, 128), (128, 128, 128, 256), (256, 256, 256, 512))
+    hip_sync_bn = True   # training: SyncBatchNorm1d units on the fused tail's global-batch form (False: the modules)
 
     def __init__(self, dropout=0.5, num_scans=5, num_pts=48, focal_loss_gamma=0.0, pedestrian_only=False):
         super().__init__()
@@ -231,7 +233,9 @@ class DROW(nn.Module):
         conv_ok = hip_conv and conv.kernel_size == (3,) and conv.padding == (1,) and conv.stride == (1,) \
             and conv.dilation == (1,) and conv.groups == 1 and conv.padding_mode == "zeros" \
             and dtype == torch.float32
-        tail_ok = type(bn) is nn.BatchNorm1d and bn.training and bn.affine and dtype == torch.float32 \
+        # (a SyncBatchNorm1d under an initialised process group: the tail's global-batch form)
+        tail_ok = (type(bn) is nn.BatchNorm1d or (DROW.hip_sync_bn and sync_bn_active(bn))) \
+            and bn.training and bn.affine and dtype == torch.float32 \
             and (groups == 1 or bn.momentum is not None) \
             and ops.bn_lrelu_pool_supported(S, conv.out_channels, L, last, groups)
         return conv_ok, tail_ok
@@ -256,7 +260,7 @@ class DROW(nn.Module):
             y = torch_ops.conv3_train(out, conv) if conv_ok else conv(out)
             if tail_ok and y.dtype == torch.float32:
                 out = torch_ops.bn_lrelu_pool_train(y, bn, act.negative_slope, last)
-            else:   # SyncBatchNorm, frozen statistics, autocast, odd shapes: the modules themselves
+            else:   # frozen statistics, autocast, odd shapes: the modules themselves
                 out = act(bn(y))
                 if last:
                     out = torch.max_pool1d(out, kernel_size=2)

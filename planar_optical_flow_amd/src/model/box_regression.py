@@ -59,6 +59,16 @@ class PointNet(nn.Module):
     gemm_pointwise = True   # GPU inference: the 1x1 convolutions as library GEMMs over [B*n, C]
     train_pointwise = False  # the same form in training mode (autograd through F.linear / BatchNorm on [B*n, C])
     hip_train = True        # GPU training: every unit one autograd node on the HIP kernels (torch_ops.ConvUnitTrain)
+    hip_sync_bn = True      # ... a dist.SyncBatchNorm1d unit too, on the tail's global-batch form (False: the modules)
+
+    @classmethod
+    def _bn_on_hip(cls, bn):
+        """The unit's BatchNorm goes through the fused tail: a plain BatchNorm1d (per-rank statistics), or a
+        SyncBatchNorm1d that tracks running statistics under an initialised process group (global statistics)."""
+        if type(bn) is nn.BatchNorm1d:
+            return True
+        from planar_optical_flow_amd import dist
+        return cls.hip_sync_bn and dist.sync_bn_active(bn)
 
     def forward(self, x):  # x [B, C, n]
         if x.is_cuda and self.gemm_pointwise and (self.train_pointwise or not self.training):
@@ -66,8 +76,8 @@ class PointNet(nn.Module):
         if x.is_cuda and self.training and self.hip_train and torch.is_grad_enabled():
             from planar_optical_flow_amd import torch_ops
             units = (self.conv1, self.conv2, self.conv3, self.conv4)
-            if all(type(u[1]) is nn.BatchNorm1d and torch_ops.conv_unit_train_supported(u[0], x.shape[2]) for u in units):
-                # (per-rank BatchNorm only: a SyncBatchNorm1d unit keeps the module path, whose statistics are global)
+            if all(self._bn_on_hip(u[1]) and torch_ops.conv_unit_train_supported(u[0], x.shape[2]) for u in units):
+                # (a SyncBatchNorm1d without a process group keeps the module path, which is the stock module then)
                 # float32-MFMA convolution + fused BatchNorm(train)/LeakyReLU tail forward; tail backward, data gradient
                 # on the same convolution kernel, weight gradient on the split-K kernel's one-tap form.  The library's
                 # path spends a third of its step on the weight-gradient kernels and their layout transposes.
@@ -128,7 +138,16 @@ class BoundingBoxRegressor(PointNet):
         if isinstance(unit, nn.Linear):
             return torch_ops.linear_small(x, unit)
         x = torch_ops.linear_small(x, unit[0])
-        for layer in list(unit)[1:]:
+        layers = list(unit)[1:]
+        if len(layers) == 2 and self.training and torch.is_grad_enabled() and PointNet.hip_sync_bn \
+                and isinstance(layers[1], nn.LeakyReLU) and x.dtype == torch.float32 and x.dim() == 2:
+            from planar_optical_flow_amd import dist, ops
+            if dist.sync_bn_active(layers[0]) and ops.bn_lrelu_pool_supported(x.shape[0], x.shape[1], 1):
+                # global-batch BatchNorm + LeakyReLU of [B, C] as the fused tail on [B, C, 1] (a plain BatchNorm1d
+                # dense unit stays on the torch module)
+                B, C = x.shape
+                return torch_ops.bn_lrelu_pool_train(x.view(B, C, 1), layers[0], layers[1].negative_slope, 0).view(B, C)
+        for layer in layers:
             x = layer(x)
         return x
 

@@ -24,11 +24,20 @@ without running a kernel, and an ``opcheck``-able schema.  Device kernels only: 
     pof::regression_loss2(Tensor pred, Tensor target, float alpha) -> (Tensor loss, Tensor dpred)
     pof::bn_lrelu_pool_backward(Tensor y, Tensor dz, Tensor gamma, Tensor beta, Tensor mean, Tensor invstd,
         float negative_slope, bool pool, bool bias_grad, int groups=1) -> (Tensor, Tensor, Tensor, Tensor)
+    pof::bn_sync_stats(Tensor y, int groups=1) -> Tensor stat
+    pof::bn_sync_apply(Tensor y, Tensor stat, Tensor gamma, Tensor beta, Tensor(a!)? running_mean,
+        Tensor(b!)? running_var, float momentum, float eps, float negative_slope, int pool, int groups=1)
+        -> (Tensor z, Tensor mean, Tensor invstd)
+    pof::bn_sync_backward_reduce(Tensor y, Tensor dz, Tensor gamma, Tensor beta, Tensor mean, Tensor invstd,
+        float negative_slope, int pool, int groups=1) -> (Tensor red, Tensor dgamma, Tensor dbeta)
+    pof::bn_sync_backward_apply(Tensor y, Tensor dz, Tensor gamma, Tensor beta, Tensor mean, Tensor invstd, Tensor red,
+        Tensor stat, float negative_slope, int pool, bool bias_grad, int groups=1) -> (Tensor dy, Tensor dbias)
 """
 from typing import Optional, Tuple
 
 import torch
 
+from . import dist as _dist
 from . import ops
 
 # ------------------------------------------------------------------------------------------------- A9
@@ -356,25 +365,115 @@ def _(y, dz, gamma, beta, mean, invstd, negative_slope, bias_grad, groups=1):
             gamma.new_empty((gamma.shape[0] if bias_grad else 0,)))
 
 
+# ---- global-batch ("sync") form of the tail, SURVEY 8(e): the same passes cut at the per-channel sums
+@_direct("bn_sync_stats", mutates_args=(), device_types="cuda")
+def bn_sync_stats(y: torch.Tensor, groups: int = 1) -> torch.Tensor:
+    return ops.bn_sync_forward_stats(y.contiguous(), groups=groups)
+
+
+@bn_sync_stats.register_fake
+def _(y, groups=1):
+    return y.new_empty((groups * (2 * y.shape[1] + 1),), dtype=torch.float64)
+
+
+@_direct("bn_sync_apply", mutates_args=("running_mean", "running_var"), device_types="cuda")
+def bn_sync_apply(y: torch.Tensor, stat: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                  running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], momentum: float,
+                  eps: float, negative_slope: float, pool: int, groups: int = 1
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """pool: 0 none | 1 pairs | 2 the whole row (z [S, C])."""
+    z, mean, invstd = ops.bn_sync_forward_apply(y.contiguous(), stat, gamma.contiguous(), beta.contiguous(),
+                                                running_mean, running_var, momentum, eps, negative_slope, pool,
+                                                groups=groups)
+    return z, mean, invstd
+
+
+@bn_sync_apply.register_fake
+def _(y, stat, gamma, beta, running_mean, running_var, momentum, eps, negative_slope, pool, groups=1):
+    S, C, L = y.shape
+    z = y.new_empty((S, C)) if pool == 2 else y.new_empty((S, C, L // 2 if pool else L))
+    return z, y.new_empty((groups * C,)), y.new_empty((groups * C,))
+
+
+@_direct("bn_sync_backward_reduce", mutates_args=(), device_types="cuda")
+def bn_sync_backward_reduce(y: torch.Tensor, dz: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                            mean: torch.Tensor, invstd: torch.Tensor, negative_slope: float, pool: int,
+                            groups: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    red, dgamma, dbeta = ops.bn_sync_backward_reduce(y, dz.contiguous().float(), gamma.contiguous(), beta.contiguous(),
+                                                     mean, invstd, negative_slope, pool, groups=groups)
+    return red, dgamma, dbeta
+
+
+@bn_sync_backward_reduce.register_fake
+def _(y, dz, gamma, beta, mean, invstd, negative_slope, pool, groups=1):
+    return (y.new_empty((groups * 2 * y.shape[1],), dtype=torch.float64), torch.empty_like(gamma),
+            torch.empty_like(beta))
+
+
+@_direct("bn_sync_backward_apply", mutates_args=(), device_types="cuda")
+def bn_sync_backward_apply(y: torch.Tensor, dz: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                           mean: torch.Tensor, invstd: torch.Tensor, red: torch.Tensor, stat: torch.Tensor,
+                           negative_slope: float, pool: int, bias_grad: bool, groups: int = 1
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    res = ops.bn_sync_backward_apply(y, dz.contiguous().float(), gamma.contiguous(), beta.contiguous(), mean, invstd,
+                                     red, stat, negative_slope, pool, bias_grad=bias_grad, groups=groups)
+    if bias_grad:
+        return res
+    return res, gamma.new_empty((0,))
+
+
+@bn_sync_backward_apply.register_fake
+def _(y, dz, gamma, beta, mean, invstd, red, stat, negative_slope, pool, bias_grad, groups=1):
+    return torch.empty_like(y), gamma.new_empty((gamma.shape[0] if bias_grad else 0,))
+
+
+def _sync_tail_forward(y, gamma, beta, running_mean, running_var, momentum, eps, negative_slope, pool, groups):
+    """stats -> all-reduce -> apply: (z, mean, invstd, stat); `stat` holds the global count the backward pass divides by."""
+    stat = _dist.all_reduce_sum_f64(_K.bn_sync_stats(y, groups))
+    z, mean, invstd = _K.bn_sync_apply(y, stat, gamma, beta, running_mean, running_var, momentum, eps, negative_slope,
+                                       int(pool), groups)
+    return z, mean, invstd, stat
+
+
+def _sync_tail_backward(y, g_z, gamma, beta, mean, invstd, stat, negative_slope, pool, bias_grad, groups):
+    """reduce -> all-reduce -> apply: (dy, dgamma, dbeta, dbias); dgamma / dbeta / dbias are this rank's share."""
+    red, dgamma, dbeta = _K.bn_sync_backward_reduce(y, g_z, gamma, beta, mean, invstd, negative_slope, int(pool), groups)
+    _dist.all_reduce_sum_f64(red)
+    dy, db = _K.bn_sync_backward_apply(y, g_z, gamma, beta, mean, invstd, red, stat, negative_slope, int(pool),
+                                       bias_grad, groups)
+    return dy, dgamma, dbeta, db
+
+
 class BnLreluPool(torch.autograd.Function):
     """Autograd wrapper of pof::bn_lrelu_pool.  The operator updates the running statistics in place, and the
     dispatcher only accepts autograd formulas for functional operators -- hence a Function around the two ops
-    (both still visible to torch.compile through their fake kernels)."""
+    (both still visible to torch.compile through their fake kernels).  ``sync``: the global-batch form, one small
+    all-reduce in each direction (a process group must be initialised)."""
 
     @staticmethod
-    def forward(ctx, y, gamma, beta, running_mean, running_var, momentum, eps, negative_slope, pool):
-        z, mean, invstd = _K.bn_lrelu_pool(y, gamma, beta, running_mean, running_var, momentum, eps,
-                                                      negative_slope, pool)
-        ctx.save_for_backward(y, gamma, beta, mean, invstd)
-        ctx.negative_slope, ctx.pool = negative_slope, pool
+    def forward(ctx, y, gamma, beta, running_mean, running_var, momentum, eps, negative_slope, pool, sync=False):
+        if sync:
+            z, mean, invstd, stat = _sync_tail_forward(y, gamma, beta, running_mean, running_var, momentum, eps,
+                                                       negative_slope, pool, 1)
+            ctx.save_for_backward(y, gamma, beta, mean, invstd, stat)
+        else:
+            z, mean, invstd = _K.bn_lrelu_pool(y, gamma, beta, running_mean, running_var, momentum, eps,
+                                                          negative_slope, pool)
+            ctx.save_for_backward(y, gamma, beta, mean, invstd)
+        ctx.negative_slope, ctx.pool, ctx.sync = negative_slope, pool, sync
         return z
 
     @staticmethod
     def backward(ctx, g_z):
+        if ctx.sync:
+            y, gamma, beta, mean, invstd, stat = ctx.saved_tensors
+            dy, dgamma, dbeta, _ = _sync_tail_backward(y, g_z, gamma, beta, mean, invstd, stat, ctx.negative_slope,
+                                                       ctx.pool, False, 1)
+            return dy, dgamma, dbeta, None, None, None, None, None, None, None
         y, gamma, beta, mean, invstd = ctx.saved_tensors
         dy, dgamma, dbeta, _ = _K.bn_lrelu_pool_backward(y, g_z, gamma, beta, mean, invstd,
                                                                     ctx.negative_slope, ctx.pool, False)
-        return dy, dgamma, dbeta, None, None, None, None, None, None
+        return dy, dgamma, dbeta, None, None, None, None, None, None, None
 
 
 def _bn_train_args(bn, groups=1, shape=None):
@@ -397,9 +496,13 @@ def _bn_train_args(bn, groups=1, shape=None):
 def bn_lrelu_pool_train(y, bn, negative_slope=0.1, pool=False):
     """Training-mode tail of a trunk unit on the fused kernels: z = max_pool1d?(leaky_relu(bn(y))) for a
     ``torch.nn.BatchNorm1d`` in training mode, with its running statistics and batch counter updated as the
-    module itself would."""
+    module itself would.  A ``dist.SyncBatchNorm1d`` under an initialised process group takes the global-batch
+    form (``pool`` = 2 there: the maximum over the whole row)."""
     rm, rv, momentum, eps = _bn_train_args(bn, 1, y.shape)
-    return BnLreluPool.apply(y, bn.weight, bn.bias, rm, rv, momentum, eps, float(negative_slope), bool(pool))
+    if _dist.sync_bn_active(bn):
+        return BnLreluPool.apply(y.contiguous(), bn.weight, bn.bias, rm, rv, momentum, eps, float(negative_slope),
+                                 int(pool), True)
+    return BnLreluPool.apply(y, bn.weight, bn.bias, rm, rv, momentum, eps, float(negative_slope), bool(pool), False)
 
 
 @_direct("conv3_wgrad", mutates_args=(), device_types="cuda")
@@ -583,41 +686,52 @@ class TrunkUnitTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, momentum, eps, negative_slope, pool,
-                groups):
+                groups, sync=False):
         co = weight.shape[0]
         wt, wd = _weight_layouts(weight, ctx.needs_input_grad[0])
         shift = bias.detach() if bias is not None else _const(co, 0.0, weight)
         y = _K.conv3_bn_lrelu(x, wt, _const(co, 1.0, weight), shift, False, 1.0)
-        z, mean, invstd = _K.bn_lrelu_pool(y, gamma, beta, running_mean, running_var, momentum, eps,
-                                                      negative_slope, pool, groups)
-        ctx.save_for_backward(x, weight, y, gamma, beta, mean, invstd, wd)
+        if sync:    # global-batch statistics: the tail's split form around one all-reduce
+            z, mean, invstd, stat = _sync_tail_forward(y, gamma, beta, running_mean, running_var, momentum, eps,
+                                                       negative_slope, pool, groups)
+            ctx.save_for_backward(x, weight, y, gamma, beta, mean, invstd, wd, stat)
+        else:
+            z, mean, invstd = _K.bn_lrelu_pool(y, gamma, beta, running_mean, running_var, momentum, eps,
+                                                          negative_slope, pool, groups)
+            ctx.save_for_backward(x, weight, y, gamma, beta, mean, invstd, wd)
         ctx.has_bias, ctx.negative_slope, ctx.pool, ctx.groups = bias is not None, negative_slope, pool, groups
+        ctx.sync = sync
         return z
 
     @staticmethod
     def backward(ctx, g_z):
-        x, weight, y, gamma, beta, mean, invstd, wd = ctx.saved_tensors
+        x, weight, y, gamma, beta, mean, invstd, wd = ctx.saved_tensors[:8]
         co, ci, _ = weight.shape
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        dy, dgamma, dbeta, db = _K.bn_lrelu_pool_backward(y, g_z, gamma, beta, mean, invstd,
-                                                                     ctx.negative_slope, ctx.pool, want_db, ctx.groups)
+        if ctx.sync:
+            dy, dgamma, dbeta, db = _sync_tail_backward(y, g_z, gamma, beta, mean, invstd, ctx.saved_tensors[8],
+                                                        ctx.negative_slope, ctx.pool, want_db, ctx.groups)
+        else:
+            dy, dgamma, dbeta, db = _K.bn_lrelu_pool_backward(y, g_z, gamma, beta, mean, invstd,
+                                                                         ctx.negative_slope, ctx.pool, want_db, ctx.groups)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _K.conv3_bn_lrelu(dy, wd, _const(ci, 1.0, weight), _const(ci, 0.0, weight), False, 1.0)
         dw = None
         if ctx.needs_input_grad[1]:
             dw = _weight_grad(x, dy, weight)
-        return dx, dw, (db if want_db else None), dgamma, dbeta, None, None, None, None, None, None, None
+        return dx, dw, (db if want_db else None), dgamma, dbeta, None, None, None, None, None, None, None, None
 
 
 def trunk_unit_train(x, conv, bn, negative_slope=0.1, pool=False, groups=1):
     """``max_pool1d?(leaky_relu(bn(conv(x))))`` for a trunk unit's modules in training mode (see TrunkUnitTrain).
     ``groups`` > 1: x holds that many equally long batches one after the other (the scans of a window); each is
     normalised with its own batch statistics and the module's running statistics see them in order -- the result
-    of sending the batches through the unit one by one, in one launch per pass."""
+    of sending the batches through the unit one by one, in one launch per pass.  A ``dist.SyncBatchNorm1d`` under an
+    initialised process group takes the batch statistics over all ranks."""
     rm, rv, momentum, eps = _bn_train_args(bn, groups, (x.shape[0], conv.out_channels, x.shape[2]))
     return TrunkUnitTrain.apply(x.contiguous(), conv.weight, conv.bias, bn.weight, bn.bias, rm, rv, momentum, eps,
-                                float(negative_slope), bool(pool), int(groups))
+                                float(negative_slope), bool(pool), int(groups), _dist.sync_bn_active(bn))
 
 
 class ConvUnitTrain(torch.autograd.Function):
@@ -639,29 +753,40 @@ class ConvUnitTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, momentum, eps, negative_slope, stride,
-                groups, rowmax=False):
+                groups, rowmax=False, sync=False):
         co, ci, k = weight.shape
         wt = weight.detach().permute(2, 1, 0).contiguous()
         shift = bias.detach() if bias is not None else _const(co, 0.0, weight)
         y = _K.conv1d_bn_lrelu(x, wt, _const(co, 1.0, weight), shift, stride, 1.0)
-        if rowmax:      # z [S, Co] = max over the positions, taken inside the tail's apply pass
+        stat = None
+        if sync:        # global-batch statistics: the tail's split form around one all-reduce
+            z, mean, invstd, stat = _sync_tail_forward(y, gamma, beta, running_mean, running_var, momentum, eps,
+                                                       negative_slope, 2 if rowmax else 0, groups)
+        elif rowmax:    # z [S, Co] = max over the positions, taken inside the tail's apply pass
             z, mean, invstd = _K.bn_lrelu_rowmax(y, gamma, beta, running_mean, running_var, momentum, eps,
                                                             negative_slope, groups)
         else:
             z, mean, invstd = _K.bn_lrelu_pool(y, gamma, beta, running_mean, running_var, momentum, eps,
                                                           negative_slope, False, groups)
-        ctx.save_for_backward(x, weight, y, gamma, beta, mean, invstd)
+        if sync:
+            ctx.save_for_backward(x, weight, y, gamma, beta, mean, invstd, stat)
+        else:
+            ctx.save_for_backward(x, weight, y, gamma, beta, mean, invstd)
         ctx.has_bias, ctx.negative_slope, ctx.stride, ctx.groups = bias is not None, negative_slope, stride, groups
-        ctx.rowmax = rowmax
+        ctx.rowmax, ctx.sync = rowmax, sync
         return z
 
     @staticmethod
     def backward(ctx, g_z):
-        x, weight, y, gamma, beta, mean, invstd = ctx.saved_tensors
+        x, weight, y, gamma, beta, mean, invstd = ctx.saved_tensors[:7]
         co, ci, k = weight.shape
         stride = ctx.stride
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.rowmax:
+        if ctx.sync:
+            dy, dgamma, dbeta, db = _sync_tail_backward(y, g_z.contiguous(), gamma, beta, mean, invstd,
+                                                        ctx.saved_tensors[7], ctx.negative_slope,
+                                                        2 if ctx.rowmax else 0, want_db, ctx.groups)
+        elif ctx.rowmax:
             dy, dgamma, dbeta, db = _K.bn_lrelu_rowmax_backward(y, g_z.contiguous(), gamma, beta, mean, invstd,
                                                                            ctx.negative_slope, want_db, ctx.groups)
         else:
@@ -696,7 +821,7 @@ class ConvUnitTrain(torch.autograd.Function):
                 w3 = weight.new_empty((co, ci, 3))
                 ge, go = _weight_grad(xe, dy, w3), _weight_grad(xo, dy, w3)
                 dw = torch.stack((go[:, :, 0], ge[:, :, 1], go[:, :, 1]), dim=2)
-        return dx, dw, (db if want_db else None), dgamma, dbeta, None, None, None, None, None, None, None, None
+        return dx, dw, (db if want_db else None), dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
 def conv_unit_train(x, conv, bn, negative_slope, groups=1, rowmax=False):
@@ -708,7 +833,8 @@ def conv_unit_train(x, conv, bn, negative_slope, groups=1, rowmax=False):
     lo = (x.shape[2] + conv.stride[0] - 1) // conv.stride[0]
     rm, rv, momentum, eps = _bn_train_args(bn, groups, (x.shape[0], conv.out_channels, lo))
     return ConvUnitTrain.apply(x.contiguous().float(), conv.weight, conv.bias, bn.weight, bn.bias, rm, rv, momentum, eps,
-                               float(negative_slope), int(conv.stride[0]), int(groups), bool(rowmax))
+                               float(negative_slope), int(conv.stride[0]), int(groups), bool(rowmax),
+                               _dist.sync_bn_active(bn))
 
 
 def conv_unit_train_supported(conv, length, channels_ok=True):
