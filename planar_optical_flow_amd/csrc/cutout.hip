@@ -34,6 +34,10 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxWin = 256;        // window-table entries per workgroup (phase A: one lane each)
 constexpr int kMaxT = 16;           // scans per window
+// float32 value path: a lerp with a range at or beyond this among its taps is redone with the float64 sequence.  Below
+// it the float32 lerp is within 2^-23 * 64 = 7.6e-6 of the exact value (ratio and result rounded once each), inside
+// the path's bound
+constexpr float kF32ValueMax = 64.0f;
 
 struct CutArgs {
     const float *scans;
@@ -459,6 +463,22 @@ __global__ __launch_bounds__(kThreads, POF_CUTOUT_MINWG) void cutout_kernel(CutA
         for (int tt = 0; tt < tcount; ++tt) {
             const int roff = (row_off + tt) * rstride + rbase;
             float res[KV];
+            // both taps of sample u.  LDSMODE 1: one LDS access (adjacent words).  At lo = N-1 the second tap is the
+            // next row's first element (or the zeroed pad word after the last row): only idx == N-1 exactly gets
+            // there in range, with ratio 0, and 0 * finite = 0
+            // byte address = (lo << 2) + row base: one v_lshl_add_u32, both taps from one ds_read2_b32
+            auto taps = [&](int u, float &vlo, float &vhi) {
+                if (LDSMODE == 1) {
+                    const float *tap = reinterpret_cast<const float *>(
+                        reinterpret_cast<const unsigned char *>(s_rows) + ((lo[u] << 2) + (roff << 2)));
+                    vlo = tap[0];
+                    vhi = tap[1];
+                } else {
+                    vlo = fetch(roff + lo[u]);
+                    vhi = fetch(roff + min(lo[u] + 1, N - 1));
+                }
+            };
+            float vmax = 0.0f;      // VMODE 2: the largest |range| among this lane's taps
 #pragma unroll
             for (int u = 0; u < KV; ++u) {
                 float y;
@@ -468,20 +488,9 @@ __global__ __launch_bounds__(kThreads, POF_CUTOUT_MINWG) void cutout_kernel(CutA
                     y = (float)(ct - dd);
                 } else {
                     float vlo, vhi;
-                    if (LDSMODE == 1) {
-                        // both taps with one LDS access (adjacent words).  At lo = N-1 the second tap is the
-                        // next row's first element (or the zeroed pad word after the last row): only
-                        // idx == N-1 exactly gets there in range, with ratio 0, and 0 * finite = 0
-                        // byte address = (lo << 2) + row base: one v_lshl_add_u32, both taps from one ds_read2_b32
-                        const float *tap = reinterpret_cast<const float *>(
-                            reinterpret_cast<const unsigned char *>(s_rows) + ((lo[u] << 2) + (roff << 2)));
-                        vlo = tap[0];
-                        vhi = tap[1];
-                    } else {
-                        vlo = fetch(roff + lo[u]);
-                        vhi = fetch(roff + min(lo[u] + 1, N - 1));
-                    }
+                    taps(u, vlo, vhi);
                     if (VMODE == 2) {
+                        vmax = fmaxf(vmax, fmaxf(fabsf(vlo), fabsf(vhi)));
                         float v = fmaf((float)ratio[u], vhi - vlo, vlo);
                         const float df = (float)dd;  // exact: a float32 value
                         if (a.centered) v = a.depth_pow2 ? (v - df) * a.rdepth_f32 : __fdiv_rn(v - df, a.depth_f32);
@@ -495,6 +504,19 @@ __global__ __launch_bounds__(kThreads, POF_CUTOUT_MINWG) void cutout_kernel(CutA
                 // out-of-FOV padding
                 y = __builtin_amdgcn_fmed3f(y, ylo, yhi);
                 res[u] = (!FULL && outb[u]) ? ypad : y;
+            }
+            if (VMODE == 2 && !PAIR && __builtin_expect(vmax >= kF32ValueMax, 0)) {
+                // a range beyond any sensor's (a corrupt or sentinel beam) among the taps: float32 arithmetic no
+                // longer resolves 1e-5 of the output there, so those samples are redone with the exact sequence
+#pragma unroll
+                for (int u = 0; u < KV; ++u) {
+                    float vlo, vhi;
+                    taps(u, vlo, vhi);
+                    if (!(fmaxf(fabsf(vlo), fabsf(vhi)) >= kF32ValueMax) || (!FULL && outb[u])) continue;
+                    const double ie = frac_index(a0, step, kd0 + (double)u, phi0, dphi, rdphi);
+                    const double ct = (double)vlo + __builtin_amdgcn_fract(ie) * (double)(vhi - vlo);
+                    res[u] = __builtin_amdgcn_fmed3f(finish_value<0>(a, ct, dd), ylo, yhi);
+                }
             }
             const int o_el = out_off + tt * P + k0;
             if (out_tile16) {   // uniform: float16 storage, 2 bytes per sample (8 samples = one 16-byte store)

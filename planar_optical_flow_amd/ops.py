@@ -413,7 +413,8 @@ def cutout(scans, tab, stride=1, centered=True, fixed=False, window_width=1.66, 
            num_cutout_pts=48, padding_val=29.99, area_mode=False, out=None, return_debug=False,
            exact_values=True, out_dtype=torch.float32, workspace=None):
     """A8 for a batch: scans [B,T,N] float32 -> [B, ceil(N/stride), T, P] float32.
-    exact_values=False selects the float32 value path (exact indices, values within 1e-5);
+    exact_values=False selects the float32 value path (exact indices, values within 1e-5; samples that meet a
+    range of 64 m or more are computed with the exact path's float64 sequence);
     out_dtype=torch.float16 stores the result as float16 (BASELINE config 5).
     workspace: optional caller-owned int32 tensor of >= min(B, 65535) elements (the per-sample area maxima); a
     caller that captures this call in a hipGraph passes one it allocated BEFORE the capture, so that the graph

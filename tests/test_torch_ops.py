@@ -204,6 +204,28 @@ def test_bn_lrelu_rowmax_matches_torch(S, C, L, groups):
     dyt, _, dbt = ops.bn_lrelu_pool_backward(yt, torch.ones(2, 4, device="cuda"), torch.ones(4, device="cuda"),
                                              torch.zeros(4, device="cuda"), mt, it, pool=2)
     assert torch.equal(dbt, torch.full((4,), 2.0, device="cuda"))
+
+    def tie_referee(dz):        # float64 on the CPU: torch.max over a dimension routes a tie to the first maximum
+        y64t = yt.double().cpu().requires_grad_(True)
+        u = torch.nn.functional.batch_norm(y64t, None, None, torch.ones(4, dtype=torch.float64),
+                                           torch.zeros(4, dtype=torch.float64), True, 0.1, 1e-5)
+        torch.max(torch.nn.functional.leaky_relu(u, 0.1), 2)[0].backward(dz.double().cpu())
+        return y64t.grad
+    want_t = tie_referee(torch.ones(2, 4))
+    assert float((dyt.double().cpu() - want_t).abs().max()) <= 1e-4 * max(float(want_t.abs().max()), 1.0)
+    # dy of a row follows the dz of that row, and of no other: with the dz of row (0, 2) changed, the channels that
+    # do not share its batch statistics keep their bits, and the whole change of that row's own gradient -- beyond
+    # the mean terms, which positions 3 and 6 (equal xhat) share -- lands on position 3, the first maximum
+    dz2 = torch.ones(2, 4, device="cuda")
+    dz2[0, 2] = 3.0
+    dyt2, _, dbt2 = ops.bn_lrelu_pool_backward(yt, dz2, torch.ones(4, device="cuda"), torch.zeros(4, device="cuda"),
+                                               mt, it, pool=2)
+    want_t2 = tie_referee(dz2)
+    assert float((dyt2.double().cpu() - want_t2).abs().max()) <= 1e-4 * max(float(want_t2.abs().max()), 1.0)
+    assert torch.equal(dyt2[:, [0, 1, 3]], dyt[:, [0, 1, 3]]) and not torch.equal(dyt2[0, 2], dyt[0, 2])
+    assert dbt2.tolist() == [2.0, 2.0, 4.0, 2.0]
+    moved = (dyt2 - dyt)[0, 2].double()
+    assert abs(float(moved[3] - moved[6]) - 2.0 * float(it[2])) <= 1e-4 * 2.0 * float(it[2])
     assert not ops.bn_lrelu_pool_supported(4, 4, 12, pool=2) and ops.bn_lrelu_pool_supported(4, 4, 16, pool=2)
     with pytest.raises(ValueError):
         ops.bn_lrelu_pool_forward(torch.zeros(4, 4, 12, device="cuda"), torch.ones(4, device="cuda"),
