@@ -429,6 +429,17 @@ int pof_conv3_bn_lrelu(const float *x, const float *wt, const float *scale, cons
                        int S, int Ci, int Co, int L, int pool, double negative_slope, float *out,
                        pof_stream_t stream);
 
+/* Float16 STORAGE through the inference trunk (BASELINE config 5)   src/depracted/model/dr_spaam.py:8-19, :86-92
+ * pof_conv3_bn_lrelu with x [S][Ci][L] and out [S][Co][pool ? L/2 : L] as IEEE half.  Weights, scale and
+ * shift stay float32 and so does every product and sum, on the same kernel form, sequence chunks and
+ * summation order as the float32 call of that shape (pof_conv1d_plan): the result is
+ * pof_conv3_bn_lrelu on the widened input, rounded once to nearest even (after the pooled maximum),
+ * bit for bit -- overflow to +-inf, float16 subnormals kept on input and output.  Same shape rules and
+ * return codes.  Alignment: none required beyond 2 bytes. */
+int pof_conv3_bn_lrelu_f16(const void *x_f16, const float *wt, const float *scale, const float *shift,
+                           int S, int Ci, int Co, int L, int pool, double negative_slope, void *out_f16,
+                           pof_stream_t stream);
+
 /* The same layer with kernel_size 1 or 3 (padding kernel_size / 2) and stride 1 or 2 (round 3): the units of the
  * Prototype flow network -- Conv1d(k = 3, stride 2 | 1) / Conv1d(k = 1) + BatchNorm(eval) + LeakyReLU --
  * src/depracted/model/prototype.py:6-25, 38-45.  wt [kernel_size][Ci][Co]; out [S][Co][Lc] with
@@ -459,6 +470,12 @@ int pof_conv1d_plan(int S, int Ci, int Co, int L, int kernel_size, int stride, i
 int pof_drow_heads(const float *feat, int S, int C, int L, const float *w_cls, const float *b_cls,
                    int n_cls, const float *w_reg, const float *b_reg, float *pred_cls,
                    float *pred_reg, pof_stream_t stream);
+
+/* The same heads on feat [S][C][L] as IEEE half (float16 storage of the trunk, src/depracted/model/dr_spaam.py:104-121):
+ * widened exactly as it is read, sums and outputs float32 -- the bits of pof_drow_heads on the widened feat. */
+int pof_drow_heads_f16(const void *feat_f16, int S, int C, int L, const float *w_cls, const float *b_cls,
+                       int n_cls, const float *w_reg, const float *b_reg, float *pred_cls,
+                       float *pred_reg, pof_stream_t stream);
 
 /* ----------------------------------------------------------------------
  * N2 trunk unit tail, training                  src/depracted/model/dr_spaam.py:8-19, :86-92
@@ -541,6 +558,14 @@ int pof_bn_sync_backward_apply(const float *y, const float *dz, long long S, int
 int pof_conv3_first_two(const float *x, const float *l1, double slope1, const float *wt, const float *scale,
                         const float *shift, int S, int C1, int Co, int L, int pool, double negative_slope,
                         float *out, pof_stream_t stream);
+
+/* pof_conv3_first_two in float16 storage (dr_spaam.py:86-92, conv_block_1[0] and [1]): x [S][L] is the
+ * float16 cutout (pof_cutout_f16), out [S][Co][pool ? L/2 : L] half; l1, wt, scale and shift float32.
+ * Equal to pof_conv3_first_two on the widened cutout, rounded once to nearest even, bit for bit; same
+ * shape rules and return codes.  There is no mixed in / out form. */
+int pof_conv3_first_two_f16(const void *x_f16, const float *l1, double slope1, const float *wt,
+                            const float *scale, const float *shift, int S, int C1, int Co, int L, int pool,
+                            double negative_slope, void *out_f16, pof_stream_t stream);
 
 /* ----------------------------------------------------------------------
  * N2 trunk convolution, weight gradient         src/depracted/model/dr_spaam.py:8-19

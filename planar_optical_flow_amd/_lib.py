@@ -59,6 +59,7 @@ SIGNATURES = {
     "pof_associate_odometry": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
     "pof_rotate_iou": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p]),
     "pof_conv3_bn_lrelu": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p]),
+    "pof_conv3_bn_lrelu_f16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p]),
     "pof_conv1d_bn_lrelu": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _p]),
     "pof_conv1d_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "pof_bn_lrelu_pool_workspace_bytes": (_sz, [_ll, _i, _i, _i]),
@@ -71,11 +72,13 @@ SIGNATURES = {
     "pof_conv3_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pof_conv3_wgrad": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "pof_conv3_first_two": (_i, [_p, _p, _d, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p]),
+    "pof_conv3_first_two_f16": (_i, [_p, _p, _d, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p]),
     "pof_regression_loss2": (_i, [_p, _p, _ll, _i, _d, _p, _p, _p]),
     "pof_linear_bias": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
     "pof_conv1d_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "pof_conv1d_wgrad": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "pof_drow_heads": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "pof_drow_heads_f16": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     "pof_segment_inputs": (_i, [_p, _i, _i, _p, _p, _i, _d, _i, _i, C.c_uint32, _p, _p, _p, _p]),
     "pof_segment_resample": (_i, [_p, _i, _p, _i, _i, _p, _p, _d, _i, C.c_uint32, _p, _p, _p]),
     "pof_polar_grid": (_i, [_p, _i, _i, _i, _d, _d, _d, _d, _i, _p, _p]),

@@ -2,6 +2,9 @@
 //   y = max_pool1d?( LeakyReLU_0.1( BatchNorm_eval( Conv1d(k = 3, pad = 1)(x) ) ), 2 )
 // (src/depracted/model/dr_spaam.py:8-19 `_conv3x3`, :86-92 `_forward_conv`) on S short
 // sequences at once: x [S][Ci][L] -> out [S][Co][L or L/2], float32.
+// Storage type T = float or _Float16 for x / out (the trunk's k = 3, stride 1 forms; weights, scale / shift and
+// every product and sum stay float32): a float16 converts to float32 exactly, so the float16 form equals the
+// float32 form on the same values, its output rounded once to nearest even.
 //
 // 450 x T x B sequences of 56 / 28 / 14 / 7 points: MIOpen falls to its naive / im2col paths
 // on these shapes (6 TFLOP/s end to end).  Here the layer is an implicit GEMM on the float32
@@ -31,12 +34,13 @@ constexpr int kCvRows = 3 * kCvCC;   // K rows per chunk (tap-major), kernel wid
 constexpr long long kCvFillWorkgroups = 256;    // one workgroup = one wave per SIMD on each of the 256 CUs
 using f32x16 = float __attribute__((ext_vector_type(16)));
 
+template <typename T>
 struct ConvArgs {
-    const float *x;       // [S][Ci][L]
+    const T *x;           // [S][Ci][L]
     const float *wt;      // [3][Ci][Co]
     const float *scale;   // [Co]
     const float *shift;   // [Co]
-    float *out;           // [S][Co][Lout]
+    T *out;               // [S][Co][Lout]
     int S, Ci, Co, L, pool;
     int Lc;               // positions the convolution produces per sequence: L (stride 1), (L + 1) / 2 (stride 2)
     float slope;
@@ -54,8 +58,8 @@ struct ConvArgs {
 //   0 <= slope <= 1, the pooled pair on adjacent lanes through one DPP move, stores as uniform base + 32-bit
 //   offset.  (The first version did two global loads, a 64-bit multiply-add, a select chain and a
 //   ds_bpermute per output: ~1300 vector instructions per wave, 8 % of a 128 -> 128 layer.)
-template <int CT>
-__device__ __forceinline__ void conv_epilogue(const ConvArgs &a, const f32x16 (&acc)[CT], const float *s_scale,
+template <int CT, typename T>
+__device__ __forceinline__ void conv_epilogue(const ConvArgs<T> &a, const f32x16 (&acc)[CT], const float *s_scale,
                                               const float *s_shift, int co0, int seq, int l, int h, bool col_ok)
 {
     const int Lout = a.pool ? a.Lc / 2 : a.Lc;
@@ -83,8 +87,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &a, const f32x16 (&
                 }
                 const int co = co0 + cl + j;
                 if (writer && (tile_full || co < a.Co)) {
-                    if (small) a.out[(unsigned)(obase + (long long)co * Lout)] = y;
-                    else a.out[obase + (long long)co * Lout] = y;
+                    // (float16 storage: the one rounding, to nearest even, after the float32 max of the pooled pair)
+                    if (small) a.out[(unsigned)(obase + (long long)co * Lout)] = (T)y;
+                    else a.out[obase + (long long)co * Lout] = (T)y;
                 }
             }
         }
@@ -96,8 +101,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &a, const f32x16 (&
 // FUSE1: the DR-SPAAM trunk's first layer (1 -> 64, 0.3 ms of pure 1 GB write at B = 32, read back by the second
 // layer) is folded into the second: the B operand of channel c is three FMAs, a multiply and a max on the lane's five
 // input values instead of a global load -- a few hundred vector instructions per wave in the shadow of its MFMAs.
-template <int CT, int KW, int STRIDE, bool FUSE1 = false>
-__global__ __launch_bounds__(64 * kCvWaves, 4) void conv1d_kernel(ConvArgs a)
+template <int CT, int KW, int STRIDE, bool FUSE1 = false, typename T = float>
+__global__ __launch_bounds__(64 * kCvWaves, 4) void conv1d_kernel(ConvArgs<T> a)
 {
     static_assert(!FUSE1 || (KW == 3 && STRIDE == 1), "the fused first layer is a k = 3, stride 1 convolution");
     // input channels per LDS weight chunk: 4 x 3 taps = 12 K rows, or 16 x 1 tap -- the point-wise form would otherwise
@@ -139,11 +144,11 @@ __global__ __launch_bounds__(64 * kCvWaves, 4) void conv1d_kernel(ConvArgs a)
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
             const int q = l + j - 2;
-            xs[j] = (col_ok && q >= 0 && q < a.L) ? a.x[(long long)seq * a.L + q] : 0.0f;
+            xs[j] = (col_ok && q >= 0 && q < a.L) ? (float)a.x[(long long)seq * a.L + q] : 0.0f;
         }
         __syncthreads();                               // s_l1 is read by the first load_x below
     }
-    // 32-bit element offsets of x[seq][h][l + tap - 1] relative to the (uniform) channel row base:
+    // 32-bit offsets of x[seq][h][l + tap - 1] relative to the (uniform) channel row base:
     // border / tail lanes point at a valid neighbour and are zeroed after the load
     // (BYTE offsets: SGPR base + zero-extended 32-bit VGPR offset is the global_load saddr form,
     // which needs no 64-bit address registers per load)
@@ -153,8 +158,8 @@ __global__ __launch_bounds__(64 * kCvWaves, 4) void conv1d_kernel(ConvArgs a)
     for (int tap = 0; tap < KW; ++tap) {
         // a tap outside the sequence points at the lane's own centre element (always inside: l * STRIDE < L) and is
         // zeroed after the load
-        off_0[tap] = (base_off + (tap_ok[tap] ? tap - kPad : 0)) * 4u;
-        off_h[tap] = off_0[tap] + (unsigned)(h * a.L) * 4u;
+        off_0[tap] = (base_off + (tap_ok[tap] ? tap - kPad : 0)) * (unsigned)sizeof(T);
+        off_h[tap] = off_0[tap] + (unsigned)(h * a.L) * (unsigned)sizeof(T);
     }
     const int nchunk = (a.Ci + CC - 1) / CC;
 
@@ -201,8 +206,10 @@ __global__ __launch_bounds__(64 * kCvWaves, 4) void conv1d_kernel(ConvArgs a)
             if (e4 < kRows * COG / 4) reinterpret_cast<F4V *>(&s_w[buf][0][0])[e4] = wreg[q];
         }
     };
-    // activation operands of one chunk: 3 taps x NP channel pairs, uniform row base + lane offset
-    float xb[2][KW][NP];
+    // activation operands of one chunk: 3 taps x NP channel pairs, uniform row base + lane offset; kept in the storage
+    // type and widened in front of their MFMA, so that no conversion waits for a load that is still in flight
+    using XB = std::conditional_t<FUSE1, float, T>;
+    XB xb[2][KW][NP];
     auto load_x = [&](int set, int ci0) {
         const int cc = min(CC, a.Ci - ci0);
         if constexpr (FUSE1) {
@@ -225,7 +232,7 @@ __global__ __launch_bounds__(64 * kCvWaves, 4) void conv1d_kernel(ConvArgs a)
                 const int c2 = min(2 * p, cc - 1);                               // uniform
                 const char *rowp = reinterpret_cast<const char *>(a.x + (long long)(ci0 + c2) * a.L);  // uniform base
                 const bool pair = 2 * p + 1 < cc;                                // uniform: the odd channel exists
-                xb[set][tap][p] = *reinterpret_cast<const float *>(rowp + (pair ? off_h[tap] : off_0[tap]));
+                xb[set][tap][p] = *reinterpret_cast<const T *>(rowp + (pair ? off_h[tap] : off_0[tap]));
             }
     };
 
@@ -267,7 +274,7 @@ __global__ __launch_bounds__(64 * kCvWaves, 4) void conv1d_kernel(ConvArgs a)
             }
             __builtin_amdgcn_sched_barrier(0);
             const bool ok = tap_ok[tap] && (2 * p + h < cc);
-            const float bv = ok ? xb[SET][tap][p] : 0.0f;
+            const float bv = ok ? (float)xb[SET][tap][p] : 0.0f;
 #pragma unroll
             for (int t = 0; t < CT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[t], bv, acc[t], 0, 0, 0);
             if constexpr (FUSE1) {
@@ -289,7 +296,7 @@ __global__ __launch_bounds__(64 * kCvWaves, 4) void conv1d_kernel(ConvArgs a)
         chunk(std::integral_constant<int, 0>{}, ch);
         if (ch + 1 < nchunk) chunk(std::integral_constant<int, 1>{}, ch + 1);
     }
-    conv_epilogue<CT>(a, acc, s_scale, s_shift, co0, seq, l, h, col_ok);
+    conv_epilogue<CT, T>(a, acc, s_scale, s_shift, co0, seq, l, h, col_ok);
 }
 
 // ---- split-K form for small launches (streaming inference: one scan per call) -------------------------
@@ -301,8 +308,8 @@ __global__ __launch_bounds__(64 * kCvWaves, 4) void conv1d_kernel(ConvArgs a)
 // region (no workgroup barrier inside the loop), and the four partial accumulators meet in LDS at the end,
 // summed in wave order by wave 0, which runs the epilogue.  Four times the workgroups, a quarter of the
 // serial chain.  (Summation order differs from conv3_kernel; exact on integer data, deterministic.)
-template <int CT>
-__global__ __launch_bounds__(64 * kCvWaves, 2) void conv3_splitk_kernel(ConvArgs a)
+template <int CT, typename T = float>
+__global__ __launch_bounds__(64 * kCvWaves, 2) void conv3_splitk_kernel(ConvArgs<T> a)
 {
     constexpr int COG = 32 * CT;
     constexpr int NP = kCvCC / 2;
@@ -328,8 +335,8 @@ __global__ __launch_bounds__(64 * kCvWaves, 2) void conv3_splitk_kernel(ConvArgs
     unsigned off_h[3], off_0[3];
 #pragma unroll
     for (int tap = 0; tap < 3; ++tap) {
-        off_0[tap] = (base_off + (tap_ok[tap] ? tap - 1 : 0)) * 4u;
-        off_h[tap] = off_0[tap] + (unsigned)(h * a.L) * 4u;
+        off_0[tap] = (base_off + (tap_ok[tap] ? tap - 1 : 0)) * (unsigned)sizeof(T);
+        off_h[tap] = off_0[tap] + (unsigned)(h * a.L) * (unsigned)sizeof(T);
     }
     const int nchunk = (a.Ci + kCvCC - 1) / kCvCC;
     const int per = (nchunk + kCvWaves - 1) / kCvWaves;
@@ -375,7 +382,7 @@ __global__ __launch_bounds__(64 * kCvWaves, 2) void conv3_splitk_kernel(ConvArgs
             if (e4 < kCvRows * COG / 4) reinterpret_cast<F4V *>(&s_w[wave][buf][0][0])[e4] = wreg[q];
         }
     };
-    float xb[2][3][NP];
+    T xb[2][3][NP];
     auto load_x = [&](int set, int ci0) {
         const int cc = min(kCvCC, a.Ci - ci0);
 #pragma unroll
@@ -385,7 +392,7 @@ __global__ __launch_bounds__(64 * kCvWaves, 2) void conv3_splitk_kernel(ConvArgs
                 const int c2 = min(2 * p, cc - 1);
                 const char *rowp = reinterpret_cast<const char *>(a.x + (long long)(ci0 + c2) * a.L);
                 const bool pair = 2 * p + 1 < cc;
-                xb[set][tap][p] = *reinterpret_cast<const float *>(rowp + (pair ? off_h[tap] : off_0[tap]));
+                xb[set][tap][p] = *reinterpret_cast<const T *>(rowp + (pair ? off_h[tap] : off_0[tap]));
             }
     };
 
@@ -414,7 +421,7 @@ __global__ __launch_bounds__(64 * kCvWaves, 2) void conv3_splitk_kernel(ConvArgs
 #pragma unroll
             for (int t = 0; t < CT; ++t) a_cur[t] = s_w[wave][SET][tap * kCvCC + 2 * p + h][t * 32 + r];
             const bool ok = tap_ok[tap] && (2 * p + h < cc);
-            const float bv = ok ? xb[SET][tap][p] : 0.0f;
+            const float bv = ok ? (float)xb[SET][tap][p] : 0.0f;
 #pragma unroll
             for (int t = 0; t < CT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[t], bv, acc[t], 0, 0, 0);
         }
@@ -439,23 +446,25 @@ __global__ __launch_bounds__(64 * kCvWaves, 2) void conv3_splitk_kernel(ConvArgs
         for (int t = 0; t < CT; ++t)
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) acc[t][reg] += s_acc[w][t * 16 + reg][lane];
-    conv_epilogue<CT>(a, acc, s_scale, s_shift, co0, seq, l, h, col_ok);
+    conv_epilogue<CT, T>(a, acc, s_scale, s_shift, co0, seq, l, h, col_ok);
 }
 
 }  // namespace
 
 namespace {
 
-template <int KW, int STRIDE, bool FUSE1 = false>
-void launch_conv1d(const ConvArgs &a, dim3 grid, int ct, hipStream_t s)
+template <int KW, int STRIDE, bool FUSE1 = false, typename T = float>
+void launch_conv1d(const ConvArgs<T> &a, dim3 grid, int ct, hipStream_t s)
 {
-    if (ct == 1) conv1d_kernel<1, KW, STRIDE, FUSE1><<<grid, 64 * kCvWaves, 0, s>>>(a);
-    else if (ct == 2) conv1d_kernel<2, KW, STRIDE, FUSE1><<<grid, 64 * kCvWaves, 0, s>>>(a);
-    else conv1d_kernel<4, KW, STRIDE, FUSE1><<<grid, 64 * kCvWaves, 0, s>>>(a);
+    if (ct == 1) conv1d_kernel<1, KW, STRIDE, FUSE1, T><<<grid, 64 * kCvWaves, 0, s>>>(a);
+    else if (ct == 2) conv1d_kernel<2, KW, STRIDE, FUSE1, T><<<grid, 64 * kCvWaves, 0, s>>>(a);
+    else conv1d_kernel<4, KW, STRIDE, FUSE1, T><<<grid, 64 * kCvWaves, 0, s>>>(a);
 }
 
 // Shape checks and sequence chunking of one call (host arithmetic only, shared with pof_conv1d_plan).
 // 32-bit byte offsets per lane inside one launch: sequences go in chunks of < 2^30 input elements
+// (neither this nor conv_form looks at the storage type: a float16 call takes the form, the chunks and so the
+// summation order of the float32 call of its shape)
 int conv_shape(int S, int Ci, int Co, int L, int kernel, int stride, int pool, bool fused, int *Lc, int *Lout,
                int *s_max)
 {
@@ -521,12 +530,14 @@ int conv_form(int S, int Ci, int Co, int Lc, int kernel, int stride, bool fused,
 }
 
 // l1 != nullptr: x is the single-channel input [S][L] and the Ci input channels of this (k = 3, stride 1) convolution
-// are the first layer's outputs, computed in the kernel (ConvArgs::l1)
-int conv1d_bn_lrelu(const float *x, const float *wt, const float *scale, const float *shift, int S, int Ci, int Co,
-                    int L, int kernel, int stride, int pool, double negative_slope, float *out, pof_stream_t stream,
+// are the first layer's outputs, computed in the kernel (ConvArgs::l1).  T = _Float16: kernel 3, stride 1 only
+template <typename T>
+int conv1d_bn_lrelu(const T *x, const float *wt, const float *scale, const float *shift, int S, int Ci, int Co,
+                    int L, int kernel, int stride, int pool, double negative_slope, T *out, pof_stream_t stream,
                     const float *l1 = nullptr, double slope1 = 0.0)
 {
     if (!x || !wt || !scale || !shift || !out) return POF_E_BADARG;
+    if (!std::is_same_v<T, float> && (kernel != 3 || stride != 1)) return POF_E_SHAPE;
     int Lc, Lout, s_max;
     const int rc = conv_shape(S, Ci, Co, L, kernel, stride, pool, l1 != nullptr, &Lc, &Lout, &s_max);
     if (rc != POF_OK) return rc;
@@ -535,7 +546,7 @@ int conv1d_bn_lrelu(const float *x, const float *wt, const float *scale, const f
     const long long per_seq = (long long)Ci * L;
     hipStream_t s = pof_stream(stream);
     for (int s0 = 0; s0 < S; s0 += s_max) {
-        ConvArgs a;
+        ConvArgs<T> a;
         a.S = std::min(s_max, S - s0);
         a.x = x + (long long)s0 * per_seq; a.wt = wt; a.scale = scale; a.shift = shift;
         a.out = out + (long long)s0 * Co * Lout;
@@ -547,13 +558,16 @@ int conv1d_bn_lrelu(const float *x, const float *wt, const float *scale, const f
         if (frc != POF_OK) return frc;
         const dim3 grid((unsigned)f.gx, (Co + 32 * f.ct - 1) / (32 * f.ct));
         if (f.splitk) {
-            if (f.ct == 1) conv3_splitk_kernel<1><<<grid, 64 * kCvWaves, 0, s>>>(a);
-            else conv3_splitk_kernel<2><<<grid, 64 * kCvWaves, 0, s>>>(a);
-        } else {
-            if (l1) launch_conv1d<3, 1, true>(a, grid, f.ct, s);
-            else if (kernel == 1) launch_conv1d<1, 1>(a, grid, f.ct, s);
+            if (f.ct == 1) conv3_splitk_kernel<1, T><<<grid, 64 * kCvWaves, 0, s>>>(a);
+            else conv3_splitk_kernel<2, T><<<grid, 64 * kCvWaves, 0, s>>>(a);
+        } else if (l1) {
+            launch_conv1d<3, 1, true, T>(a, grid, f.ct, s);
+        } else if constexpr (std::is_same_v<T, float>) {
+            if (kernel == 1) launch_conv1d<1, 1>(a, grid, f.ct, s);
             else if (stride == 2) launch_conv1d<3, 2>(a, grid, f.ct, s);
             else launch_conv1d<3, 1>(a, grid, f.ct, s);
+        } else {
+            launch_conv1d<3, 1, false, T>(a, grid, f.ct, s);
         }
         POF_CHECK_LAUNCH();
     }
@@ -577,6 +591,25 @@ extern "C" int pof_conv3_first_two(const float *x, const float *l1, double slope
     POF_CLEAR_STALE_ERROR();
     if (!l1) return POF_E_BADARG;
     return conv1d_bn_lrelu(x, wt, scale, shift, S, C1, Co, L, 3, 1, pool, negative_slope, out, stream, l1, slope1);
+}
+
+extern "C" int pof_conv3_bn_lrelu_f16(const void *x_f16, const float *wt, const float *scale, const float *shift,
+                                      int S, int Ci, int Co, int L, int pool, double negative_slope, void *out_f16,
+                                      pof_stream_t stream)
+{
+    POF_CLEAR_STALE_ERROR();
+    return conv1d_bn_lrelu(static_cast<const _Float16 *>(x_f16), wt, scale, shift, S, Ci, Co, L, 3, 1, pool,
+                           negative_slope, static_cast<_Float16 *>(out_f16), stream);
+}
+
+extern "C" int pof_conv3_first_two_f16(const void *x_f16, const float *l1, double slope1, const float *wt,
+                                       const float *scale, const float *shift, int S, int C1, int Co, int L, int pool,
+                                       double negative_slope, void *out_f16, pof_stream_t stream)
+{
+    POF_CLEAR_STALE_ERROR();
+    if (!l1) return POF_E_BADARG;
+    return conv1d_bn_lrelu(static_cast<const _Float16 *>(x_f16), wt, scale, shift, S, C1, Co, L, 3, 1, pool,
+                           negative_slope, static_cast<_Float16 *>(out_f16), stream, l1, slope1);
 }
 
 extern "C" int pof_conv1d_bn_lrelu(const float *x, const float *wt, const float *scale, const float *shift,

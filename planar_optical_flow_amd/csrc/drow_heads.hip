@@ -6,6 +6,7 @@
 //
 // feat [S][C][L] float32 -> pred_cls [S][n_cls], pred_reg [S][2].  One wave per sequence: a lane owns channels
 // lane, lane + 64, ... (their L values are contiguous), the per-output dot products are wave sums.
+// T = _Float16: feat in float16 storage, widened (exactly) as it is read; sums and outputs stay float32.
 #include "pof_common.h"
 
 namespace {
@@ -13,7 +14,8 @@ namespace {
 constexpr int kHeadWaves = 4;
 constexpr int kHeadMaxOut = 8;
 
-__global__ __launch_bounds__(64 * kHeadWaves) void drow_heads_kernel(const float *__restrict__ feat, int S, int C, int L,
+template <typename T>
+__global__ __launch_bounds__(64 * kHeadWaves) void drow_heads_kernel(const T *__restrict__ feat, int S, int C, int L,
                                                                      const float *__restrict__ w_cls,
                                                                      const float *__restrict__ b_cls, int n_cls,
                                                                      const float *__restrict__ w_reg,
@@ -29,9 +31,9 @@ __global__ __launch_bounds__(64 * kHeadWaves) void drow_heads_kernel(const float
     for (int o = 0; o < kHeadMaxOut; ++o) acc[o] = 0.0f;
     const float inv = 1.0f / (float)L;
     for (int c = lane; c < C; c += 64) {
-        const float *p = feat + ((long long)s * C + c) * L;
+        const T *p = feat + ((long long)s * C + c) * L;
         float sum = 0.0f;
-        for (int l = 0; l < L; ++l) sum += p[l];
+        for (int l = 0; l < L; ++l) sum += (float)p[l];
         const float m = sum * inv;
 #pragma unroll
         for (int o = 0; o < kHeadMaxOut; ++o)
@@ -48,6 +50,20 @@ __global__ __launch_bounds__(64 * kHeadWaves) void drow_heads_kernel(const float
     }
 }
 
+template <typename T>
+int heads_entry(const T *feat, int S, int C, int L, const float *w_cls, const float *b_cls, int n_cls,
+                const float *w_reg, const float *b_reg, float *pred_cls, float *pred_reg, pof_stream_t stream)
+{
+    if (!feat || !w_cls || !b_cls || !w_reg || !b_reg || !pred_cls || !pred_reg) return POF_E_BADARG;
+    if (S < 0 || C < 1 || L < 1 || n_cls < 1) return POF_E_BADARG;
+    if (n_cls + 2 > kHeadMaxOut) return POF_E_SHAPE;
+    if (S == 0) return POF_OK;
+    drow_heads_kernel<T><<<(S + kHeadWaves - 1) / kHeadWaves, 64 * kHeadWaves, 0, pof_stream(stream)>>>(
+        feat, S, C, L, w_cls, b_cls, n_cls, w_reg, b_reg, pred_cls, pred_reg);
+    POF_CHECK_LAUNCH();
+    return POF_OK;
+}
+
 }  // namespace
 
 extern "C" int pof_drow_heads(const float *feat, int S, int C, int L, const float *w_cls, const float *b_cls, int n_cls,
@@ -55,12 +71,14 @@ extern "C" int pof_drow_heads(const float *feat, int S, int C, int L, const floa
                               pof_stream_t stream)
 {
     POF_CLEAR_STALE_ERROR();
-    if (!feat || !w_cls || !b_cls || !w_reg || !b_reg || !pred_cls || !pred_reg) return POF_E_BADARG;
-    if (S < 0 || C < 1 || L < 1 || n_cls < 1) return POF_E_BADARG;
-    if (n_cls + 2 > kHeadMaxOut) return POF_E_SHAPE;
-    if (S == 0) return POF_OK;
-    drow_heads_kernel<<<(S + kHeadWaves - 1) / kHeadWaves, 64 * kHeadWaves, 0, pof_stream(stream)>>>(
-        feat, S, C, L, w_cls, b_cls, n_cls, w_reg, b_reg, pred_cls, pred_reg);
-    POF_CHECK_LAUNCH();
-    return POF_OK;
+    return heads_entry(feat, S, C, L, w_cls, b_cls, n_cls, w_reg, b_reg, pred_cls, pred_reg, stream);
+}
+
+extern "C" int pof_drow_heads_f16(const void *feat_f16, int S, int C, int L, const float *w_cls, const float *b_cls,
+                                  int n_cls, const float *w_reg, const float *b_reg, float *pred_cls, float *pred_reg,
+                                  pof_stream_t stream)
+{
+    POF_CLEAR_STALE_ERROR();
+    return heads_entry(static_cast<const _Float16 *>(feat_f16), S, C, L, w_cls, b_cls, n_cls, w_reg, b_reg, pred_cls,
+                       pred_reg, stream);
 }

@@ -461,8 +461,11 @@ def cutout(scans, tab, stride=1, centered=True, fixed=False, window_width=1.66, 
 
 def conv3_bn_lrelu(x, wt, scale, shift, pool=False, negative_slope=0.1, out=None):
     """N2 trunk layer (inference): x [S,Ci,L] f32, wt [3,Ci,Co] f32 (conv weight transposed), scale/shift [Co]
-    (folded BatchNorm + bias) -> [S, Co, L//2 if pool else L]."""
-    x = _dev(x, torch.float32, "x")
+    (folded BatchNorm + bias) -> [S, Co, L//2 if pool else L].  x in float16 storage (BASELINE config 5): out is
+    float16 as well -- the float32 layer on the same values, rounded once."""
+    half = isinstance(x, torch.Tensor) and x.dtype == torch.float16
+    act = torch.float16 if half else torch.float32
+    x = _dev(x, act, "x")
     wt = _dev(wt, torch.float32, "wt")
     scale = _dev(scale, torch.float32, "scale")
     shift = _dev(shift, torch.float32, "shift")
@@ -474,12 +477,12 @@ def conv3_bn_lrelu(x, wt, scale, shift, pool=False, negative_slope=0.1, out=None
         raise ValueError("scale / shift must have Co entries")
     Lout = L // 2 if pool else L
     if out is None:
-        out = torch.empty((S, Co, Lout), dtype=torch.float32, device=x.device)
+        out = torch.empty((S, Co, Lout), dtype=act, device=x.device)
     else:
-        _dev(out, torch.float32, "out")
+        _dev(out, act, "out")
     if S > 0:
         with torch.cuda.device(x.device):
-            _lib.call("pof_conv3_bn_lrelu", _ptr(x), _ptr(wt), _ptr(scale), _ptr(shift), S, Ci, Co, L,
+            _lib.call("pof_conv3_bn_lrelu_f16" if half else "pof_conv3_bn_lrelu", _ptr(x), _ptr(wt), _ptr(scale), _ptr(shift), S, Ci, Co, L,
                       int(bool(pool)), float(negative_slope), _ptr(out), _stream())
     return out
 
@@ -487,8 +490,11 @@ def conv3_bn_lrelu(x, wt, scale, shift, pool=False, negative_slope=0.1, out=None
 def conv3_first_two(x, l1, wt, scale, shift, slope1=0.1, pool=False, negative_slope=0.1, out=None):
     """The trunk's first two units in one launch (inference): x [S,L] or [S,1,L] f32 (single-channel cutouts), l1 [C1,4]
     f32 = the first unit as {a0, a1, a2, b} per channel (taps x folded BatchNorm scale, shift), wt [3,C1,Co] /
-    scale / shift [Co] = the second unit -> [S, Co, L//2 if pool else L]."""
-    x = _dev(x, torch.float32, "x")
+    scale / shift [Co] = the second unit -> [S, Co, L//2 if pool else L].  A float16 cutout (cutout(out_dtype=float16))
+    gives a float16 out: the float32 call on the same values, rounded once."""
+    half = isinstance(x, torch.Tensor) and x.dtype == torch.float16
+    act = torch.float16 if half else torch.float32
+    x = _dev(x, act, "x")
     if x.dim() == 3 and x.shape[1] == 1:
         x = x.view(x.shape[0], x.shape[2])
     if x.dim() != 2:
@@ -509,12 +515,12 @@ def conv3_first_two(x, l1, wt, scale, shift, slope1=0.1, pool=False, negative_sl
     if pool and L % 2:
         raise ValueError("pooled output needs an even L")
     if out is None:
-        out = torch.empty((S, Co, L // 2 if pool else L), dtype=torch.float32, device=x.device)
+        out = torch.empty((S, Co, L // 2 if pool else L), dtype=act, device=x.device)
     else:
-        _dev(out, torch.float32, "out")
+        _dev(out, act, "out")
     if S > 0:
         with torch.cuda.device(x.device):
-            _lib.call("pof_conv3_first_two", _ptr(x), _ptr(l1), float(slope1), _ptr(wt), _ptr(scale), _ptr(shift), S, C1, Co,
+            _lib.call("pof_conv3_first_two_f16" if half else "pof_conv3_first_two", _ptr(x), _ptr(l1), float(slope1), _ptr(wt), _ptr(scale), _ptr(shift), S, C1, Co,
                       L, int(bool(pool)), float(negative_slope), _ptr(out), _stream())
     return out
 
@@ -559,8 +565,9 @@ def conv1d_plan(S, Ci, Co, L, kernel_size=3, stride=1, pool=False, fused_first=F
 
 def drow_heads(feat, w_cls, b_cls, w_reg, b_reg):
     """N2 heads (inference): feat [S,C,L] f32, w_cls [n_cls,C], w_reg [2,C] -> (pred_cls [S,n_cls], pred_reg [S,2]):
-    mean over positions + both 1x1 convolutions in one launch."""
-    feat = _dev(feat, torch.float32, "feat")
+    mean over positions + both 1x1 convolutions in one launch.  feat may be in float16 storage; outputs are float32."""
+    half = isinstance(feat, torch.Tensor) and feat.dtype == torch.float16
+    feat = _dev(feat, torch.float16 if half else torch.float32, "feat")
     S, C, L = feat.shape
     w_cls = _dev(w_cls.reshape(-1, C), torch.float32, "w_cls")
     w_reg = _dev(w_reg.reshape(-1, C), torch.float32, "w_reg")
@@ -572,7 +579,7 @@ def drow_heads(feat, w_cls, b_cls, w_reg, b_reg):
     pred_reg = torch.empty((S, 2), dtype=torch.float32, device=feat.device)
     if S > 0:
         with torch.cuda.device(feat.device):
-            _lib.call("pof_drow_heads", _ptr(feat), S, C, L, _ptr(w_cls), _ptr(b_cls), n_cls, _ptr(w_reg), _ptr(b_reg),
+            _lib.call("pof_drow_heads_f16" if half else "pof_drow_heads", _ptr(feat), S, C, L, _ptr(w_cls), _ptr(b_cls), n_cls, _ptr(w_reg), _ptr(b_reg),
                       _ptr(pred_cls), _ptr(pred_reg), _stream())
     return pred_cls, pred_reg
 

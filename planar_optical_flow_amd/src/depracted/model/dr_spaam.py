@@ -28,9 +28,11 @@ class _WindowedAttention:
     autograd formula and fake kernel registered with torch.library, so autograd and torch.compile see one op)."""
 
     @staticmethod
-    def apply(emb_x, emb_t, x, tmpl, alpha, window):
+    def apply(emb_x, emb_t, x, tmpl, alpha, window, storage=torch.float32):
+        """storage=torch.float16 (inference only): x / tmpl go to ``pof_spatial_attention_f16`` un-widened and the
+        fused template comes back float16; the embeddings and the similarities stay float32."""
         out, band, _ = torch.ops.pof.spatial_attention(emb_x.contiguous().float(), emb_t.contiguous().float(),
-                                                       x.contiguous().float(), tmpl.contiguous().float(),
+                                                       x.contiguous().to(storage), tmpl.contiguous().to(storage),
                                                        float(alpha), int(window))
         return out, band
 
@@ -61,11 +63,25 @@ class _SpatialAttention(nn.Module):
                                                   act.negative_slope)
         return act(bn(torch.nn.functional.linear(flat, conv.weight.reshape(conv.out_channels, -1), conv.bias)))
 
-    def fold_for_inference(self, enable=True):
+    embed_slab = 4096    # rows per float32 copy of float16 features in front of the embedding GEMM (59 MB at 256 x 14)
+
+    def _embed_rows(self, flat):
+        """``_embed`` of feature rows [R, C*P] in either storage type -> float32 [R, 128].  Float16 rows are widened
+        in slabs of ``embed_slab`` rows, so the float32 copy the library GEMM needs stays small: the arithmetic is
+        the float32 path's on the same values (a float16-input GEMM would be another summation)."""
+        if flat.dtype != torch.float16:
+            return self._embed(flat)
+        return torch.cat([self._embed(flat[r0:r0 + self.embed_slab].float())
+                          for r0 in range(0, max(flat.shape[0], 1), self.embed_slab)])
+
+    def fold_for_inference(self, enable=True, storage=torch.float32):
         """Fold the embedding's BatchNorm (running statistics) into its weight and bias.  Call after loading a
-        checkpoint (``DROW.fuse_for_inference`` does); ``train()`` drops the folded copy."""
+        checkpoint (``DROW.fuse_for_inference`` does); ``train()`` drops the folded copy.  ``storage``: the type the
+        features and the template are kept in on the folded inference route (float16: DESIGN 3.6)."""
         self._folded = None
+        self._storage = torch.float32
         if enable:
+            self._storage = storage
             conv, bn = self.conv[0], self.conv[1]
             with torch.no_grad():
                 scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
@@ -77,12 +93,20 @@ class _SpatialAttention(nn.Module):
     def train(self, mode=True):
         if mode:
             self._folded = None
+            self._storage = torch.float32
         return super().train(mode)
 
     def forward(self, x, x_template):
         """x, x_template [B, n_cutout, n_channel, n_pts] -> (fused template of the
         same shape, pre-softmax window similarities [B, n_cutout, window])."""
         B, N, C, P = x.shape
+        if getattr(self, "_storage", torch.float32) == torch.float16 and getattr(self, "_folded", None) is not None \
+                and not self.training and x.is_cuda and not torch.is_grad_enabled():
+            # float16 storage: the features stay float16 through the gate; only the embedding GEMM sees float32 rows
+            x, x_template = x.contiguous().half(), x_template.contiguous().half()
+            emb_x = self._embed_rows(x.view(B * N, C * P)).view(B, N, 128)
+            emb_t = self._embed_rows(x_template.view(B * N, C * P)).view(B, N, 128)
+            return _WindowedAttention.apply(emb_x, emb_t, x, x_template, self._alpha, self._window_size, torch.float16)
         emb_x, emb_t = self._embed(x.reshape(B * N, C * P)).view(B, N, 128), \
             self._embed(x_template.reshape(B * N, C * P)).view(B, N, 128)
         out, band = _WindowedAttention.apply(emb_x, emb_t, x, x_template, self._alpha, self._window_size)
@@ -141,12 +165,18 @@ class DROW(nn.Module):
         _init_weights(self)
 
     # ---- inference on the HIP trunk kernels ------------------------------------------------
-    def fuse_for_inference(self, enable=True):
+    def fuse_for_inference(self, enable=True, storage=torch.float32):
         """Fold every conv3 + BatchNorm (running statistics) + bias of the four trunk blocks into
         (transposed weight, scale, shift) triples for ``pof_conv3_bn_lrelu``.  Call after loading a
         checkpoint and after ``.cuda()``; eval-mode forwards then run the trunk as float32-MFMA
-        implicit GEMMs instead of MIOpen convolutions.  (Training mode has its own HIP route, _run_block_train.)"""
+        implicit GEMMs instead of MIOpen convolutions.  (Training mode has its own HIP route, _run_block_train.)
+        ``storage=torch.float16`` keeps every activation between the cutout and the heads -- trunk layers, the
+        gate's template -- in float16 (half the footprint); the arithmetic, the folded parameters and the outputs
+        stay float32, every stored tensor is rounded once."""
+        if storage not in (torch.float32, torch.float16):
+            raise ValueError("storage must be torch.float32 or torch.float16")
         self._fused = None
+        self._storage = torch.float32
         if not enable:
             if getattr(self, "gate", None) is not None:
                 self.gate.fold_for_inference(False)
@@ -167,9 +197,10 @@ class DROW(nn.Module):
             if wt0.shape[1] == 1 and wt0.shape[2] <= 128:
                 fused["first_unit_table"] = torch.cat((wt0[:, 0, :].t() * sc0[:, None], sh0[:, None]), dim=1).contiguous()
         self._fused = fused
+        self._storage = storage
         gate = getattr(self, "gate", None)
         if gate is not None:
-            gate.fold_for_inference(True)
+            gate.fold_for_inference(True, storage)
         return self
 
     def train(self, mode=True):
@@ -177,6 +208,7 @@ class DROW(nn.Module):
         running statistics are about to change, so ``fuse_for_inference()`` has to be called again."""
         if mode:
             self._fused = None
+            self._storage = torch.float32
         return super().train(mode)
 
     def _slope(self, name, i):
@@ -190,7 +222,8 @@ class DROW(nn.Module):
         CPU: the plain torch modules."""
         fused = getattr(self, "_fused", None)
         if fused is not None and not self.training and x.is_cuda and not torch.is_grad_enabled():
-            x = x.contiguous().float()
+            # the storage type of fuse_for_inference(): float32, or float16 (no-op for a float16 cutout)
+            x = x.contiguous().to(getattr(self, "_storage", torch.float32))
             layers = fused[name]
 
             table = fused.get("first_unit_table") if name == "conv_block_1" and getattr(self, "fuse_first_unit", True) else None
@@ -312,6 +345,9 @@ class DROW(nn.Module):
         return out.view(B, N, T, out.shape[-2], out.shape[-1])
 
     def _fuse_cutout(self, x):
+        if x.dtype == torch.float16 and getattr(self, "_fused", None) is not None \
+                and getattr(self, "_storage", torch.float32) == torch.float16:
+            return torch.sum(x, dim=2, dtype=torch.float32).half()     # float32 sum, one rounding
         return torch.sum(x, dim=2)
 
     def _forward_fused_cutout(self, x):
@@ -324,7 +360,8 @@ class DROW(nn.Module):
         if getattr(self, "_fused", None) is not None and not self.training and out.is_cuda \
                 and not torch.is_grad_enabled() and self.conv_cls.out_channels <= 6:
             # inference after fuse_for_inference(): mean + both heads in one launch (pof_drow_heads)
-            pred_cls, pred_reg = ops.drow_heads(out.contiguous().float(), self.conv_cls.weight, self.conv_cls.bias,
+            pred_cls, pred_reg = ops.drow_heads(out.contiguous().to(getattr(self, "_storage", torch.float32)),
+                                                self.conv_cls.weight, self.conv_cls.bias,
                                                 self.conv_reg.weight, self.conv_reg.bias)
             return pred_cls.view(B, N, -1), pred_reg.view(B, N, 2)
         feat = out.mean(dim=-1)

@@ -32,6 +32,7 @@ class StreamingDetector:
                  nms_min_dist=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
+        self._refuse_float16(model)
         self.model = model.to(device).eval()
         # The captured graph bakes in the addresses of the folded trunk parameters (model._fused).  The detector
         # therefore (i) does not re-fuse a model that is already fused -- that would free the tensors another
@@ -58,6 +59,12 @@ class StreamingDetector:
         self._have_template = False
         self.feat_fused = self.pred_cls = self.pred_reg = None
 
+    @staticmethod
+    def _refuse_float16(model):
+        if getattr(model, "_fused", None) is not None and getattr(model, "_storage", torch.float32) != torch.float32:
+            raise ValueError("StreamingDetector keeps float32 storage: the model was fused with storage=%s -- "
+                             "call model.fuse_for_inference() (float32) first" % model._storage)
+
     def reset(self):
         self._have_template = False
 
@@ -68,6 +75,7 @@ class StreamingDetector:
             self.model.eval()
         if getattr(self.model, "_fused", None) is None:
             self.model.fuse_for_inference()
+        self._refuse_float16(self.model)
         if self.model._fused is not self._fused_ref:
             self._fused_ref = self.model._fused
             self._graph = None

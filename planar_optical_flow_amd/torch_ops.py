@@ -184,6 +184,7 @@ def conv3_bn_lrelu(x: torch.Tensor, wt: torch.Tensor, scale: torch.Tensor, shift
 @conv3_bn_lrelu.register_fake
 def _(x, wt, scale, shift, pool, negative_slope):
     S, _, L = x.shape
+    # x's storage type: float32, or float16 (pof_conv3_bn_lrelu_f16)
     return x.new_empty((S, wt.shape[2], L // 2 if pool else L))
 
 

@@ -1,11 +1,17 @@
 """DR-SPAAM forward (BASELINE config 3 shape): cutout -> SpatialDROW on the device.  Under rocprofv3
---kernel-trace --stats this shows how the time splits between the MIOpen trunks and the HIP kernels."""
+--kernel-trace --stats this shows how the time splits between the MIOpen trunks and the HIP kernels.
+    python tools/bench_drspaam.py [B] [hip|torch|torch-find|train...] [--storage=float32|float16]
+--storage=float16 (hip mode): float16 cutout and fuse_for_inference(storage=torch.float16); one storage type per
+process.  The hip mode also prints the forward in HIP-event time and the peak allocation of the timed forwards."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from planar_optical_flow_amd import ops, synth
 from planar_optical_flow_amd.src.depracted.model.dr_spaam import SpatialDROW
 
+STORAGE = [a.split("=", 1)[1] for a in sys.argv if a.startswith("--storage=")]
+sys.argv = [a for a in sys.argv if not a.startswith("--storage=")]
+ACT = {"float32": torch.float32, "float16": torch.float16}[STORAGE[0] if STORAGE else "float32"]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 mode = sys.argv[2] if len(sys.argv) > 2 else "hip"      # hip | torch | torch-find
 if mode == "torch-find":
@@ -13,14 +19,16 @@ if mode == "torch-find":
 torch.manual_seed(3)
 m = SpatialDROW(num_scans=5, num_pts=56, alpha=0.5, window_size=11, pedestrian_only=True).cuda().eval()
 if mode == "hip":
-    m.fuse_for_inference()
+    m.fuse_for_inference(storage=ACT)
+elif ACT != torch.float32:
+    sys.exit("--storage=float16 needs the hip mode")
 sb = synth.make_batch(seed=3, B=B, T=5)
 scans = torch.from_numpy(sb.scans).cuda()
 tab = ops.phi_table()
 kw = dict(fixed=True, centered=True, window_width=1.0, window_depth=0.5, num_cutout_pts=56, padding_val=29.99,
           area_mode=True)
 def step():
-    x = ops.cutout(scans, tab, **kw)
+    x = ops.cutout(scans, tab, out_dtype=ACT, **kw)
     with torch.no_grad():
         return m(x)
 if mode.startswith("train"):
@@ -32,6 +40,18 @@ for _ in range(5): step()
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / 5
 print("DR-SPAAM forward B=%d [%s]: %.2f ms/step  %.0f scans/s" % (B, mode, dt * 1e3, B / dt), flush=True)
+if mode == "hip":
+    out = None
+    torch.cuda.synchronize(); torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+    held = torch.cuda.memory_allocated()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(5): out = step()
+    e1.record(); torch.cuda.synchronize()
+    print("DR-SPAAM forward B=%d [hip, storage %s]: %.3f ms/step (HIP events, 5 steps)  peak allocated %.1f MB "
+          "(%.1f MB held before the step)  outputs finite: %s"
+          % (B, ACT, e0.elapsed_time(e1) / 5, torch.cuda.max_memory_allocated() / 1e6, held / 1e6,
+             all(bool(torch.isfinite(o).all()) for o in out)), flush=True)
 if mode in ("train", "train-miopen", "train-modules", "train-libconv"):
     # one optimisation-style step: forward in training mode (BatchNorm batch statistics) + backward
     m.train()
