@@ -355,6 +355,18 @@ int pof_spatial_attention_plan(int B, int N, int F, int *forward_segment, int *b
  *   src/depracted/model/adaboost_person_det.py:71-90 (cuts), :102-210 (features)
  * ranges [B][N] float32.  seg_id [B][N] int32 (segment index of every point),
  * num_seg [B] int32, feat [B][max_seg][16] float64 (columns: see DESIGN.md).
+ *
+ * max_seg is the number of rows per scan of feat / ref_feat, not a limit on the segmentation.  For a scan
+ * with more segments than max_seg:
+ *   - num_seg is the true number of segments and seg_id labels every point of the scan, as without a limit;
+ *   - feat rows [0, max_seg) are exactly the rows an unlimited call writes (the last one ends at its own
+ *     cut, and its jump_next goes to the segment that got no row); nothing is written at or past row max_seg;
+ *   - num_kept counts the kept segments (more than two points) among the first max_seg, and ref_feat holds
+ *     their rows [0, num_kept): the rows the reference computes from a kept list cut to those segments, so
+ *     column 4 is NaN wherever kept[min(q+1, 3)] lies beyond the cut.  Rows from num_kept on are not written.
+ * A row the kernel does not write keeps what the caller put there.
+ * Coincident points (a run of range 0) leave the normal equations singular; the fit columns then hold the
+ * minimum-norm solution the reference's pinv returns (0 for a run of range 0), not NaN.
  * ---------------------------------------------------------------------- */
 int pof_segment_features(const float *ranges, const double *tab, int B, int N, double jump_dist,
                          int max_seg, int32_t *seg_id, int32_t *num_seg, double *feat,

@@ -12,7 +12,8 @@
 // moments, lane 0 stores).  Centring the points first makes A^T A block diagonal
 // ([[4Suu,4Suv,0],[4Suv,4Svv,0],[0,0,n]]), so the 3x3 circle solve reduces to one
 // well-conditioned 2x2 solve plus a division; the result equals pinv(A) b for any segment
-// with full column rank.  The per-axis median of the reference's "median deviation" is a
+// with full column rank, and for coincident points (a run of range 0) the minimum-norm solution
+// pinv returns there is written out.  The per-axis median of the reference's "median deviation" is a
 // rank selection inside the wave (each lane ranks its points against the segment in LDS).
 //
 // Two outputs:
@@ -228,18 +229,35 @@ __global__ __launch_bounds__(kThreads) void segment_kernel(SegArgs a)
         // the two solves (every lane holds the reduced moments)
         double k = nan, bb = nan, resid = nan, xc = nan, yc = nan, rc = nan;
         if (n >= 3) {
-            // line y = k x + b: 2x2 normal equations in centred coordinates
-            k = suv / suu;
-            bb = my - k * mx;
+            // line y = k x + b: 2x2 normal equations in centred coordinates.  Suu == 0 (every x equal: a run of
+            // range 0, whose points coincide) leaves [x 1] with rank 1; the reference's pinv then returns the
+            // minimum-norm solution (mx, 1) my / (mx^2 + 1), not the NaN of 0 / 0.
+            if (suu == 0.0) {
+                const double w = mx * mx + 1.0;
+                k = mx * my / w;
+                bb = my / w;
+            } else {
+                k = suv / suu;
+                bb = my - k * mx;
+            }
             const double nrm = sqrt(k * k + 1.0);
             resid = (k / nrm) * sumx + (-1.0 / nrm) * sumy - (double)n * fabs(bb / nrm);
             // circle: [[Suu,Suv],[Suv,Svv]] (uc,vc) = 0.5 (Suz,Svz); c' = -Sz/n
-            const double det = suu * svv - suv * suv;
-            const double uc = 0.5 * (suz * svv - svz * suv) / det;
-            const double vc = 0.5 * (svz * suu - suz * suv) / det;
-            rc = sqrt(uc * uc + vc * vc + sz / (double)n);
-            xc = uc + mx;
-            yc = vc + my;
+            if (sz == 0.0) {
+                // coincident points: every row of A is (-2mx, -2my, 1) =: a, and pinv(A) rhs = a rhs / |a|^2 with
+                // rhs = -(mx^2 + my^2) -- all zeros for a run of range 0, as the reference computes
+                const double q = mx * mx + my * my, w = 4.0 * q + 1.0;
+                xc = 2.0 * mx * q / w;
+                yc = 2.0 * my * q / w;
+                rc = sqrt(xc * xc + yc * yc + q / w);
+            } else {
+                const double det = suu * svv - suv * suv;
+                const double uc = 0.5 * (suz * svv - svz * suv) / det;
+                const double vc = 0.5 * (svz * suu - suz * suv) / det;
+                rc = sqrt(uc * uc + vc * vc + sz / (double)n);
+                xc = uc + mx;
+                yc = vc + my;
+            }
         }
         // pass 3: quantities that need the fit / the mean edge length
         double bstd = nan, scc = nan;
