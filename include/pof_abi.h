@@ -351,6 +351,37 @@ int pof_spatial_attention_backward_fused(const float *emb_x, const float *emb_t,
 int pof_spatial_attention_plan(int B, int N, int F, int *forward_segment, int *backward_segment);
 
 /* ------------------------------------------------------------------------
+ * A10 the gate's embedding, inference           src/depracted/model/dr_spaam.py:137-147, :166-171
+ * Conv1d(n_channel -> E, kernel_size = n_pts) + BatchNorm1d(eval) + LeakyReLU over whole cutouts,
+ * i.e. the dense product with the BatchNorm folded into w and bias:
+ *   emb[r][e] = lrelu( sum_k src[r][k] * w[e][k] + bias[e] ),  src in {x, tmpl}
+ * x, tmpl [R][K] (K = n_channel * n_pts, contiguous rows), w [E][K] float32 (the folded conv weight as
+ * fold_for_inference keeps it), bias [E], emb_x / emb_t [R][E] float32.  tmpl and emb_t may both be NULL
+ * (one source).  Both sources go in one launch and share w; no workspace, no memset, no atomics.
+ * Shapes: K % 8 == 0, E % 32 == 0, 32 <= E <= 256, R >= 1 (POF_E_SHAPE; sizes < 1 POF_E_BADARG).
+ * Alignment: x, tmpl, w, emb_x, emb_t 16-byte aligned, there is no fallback: POF_E_SHAPE otherwise.
+ * Every product and sum is float32 on v_mfma_f32_32x32x2_f32, in ONE order for every R and both
+ * kernel forms (pof_attn_embed_plan), so a row's result does not depend on the rows it is batched with:
+ *   - k in chunks of 8, chunk c on chain c % 4; a chain starts at +0 and takes its chunks in ascending
+ *     order, inside a chunk k = 8c + {0, 4, 1, 5, 2, 6, 3, 7}, each step p = fmaf(src[r][k], w[e][k], p);
+ *   - s = ((p0 + p1) + p2) + p3;  v = s + bias[e];  emb = v >= 0 ? v : v * (float)negative_slope.
+ * ---------------------------------------------------------------------- */
+int pof_attn_embed(const float *x, const float *tmpl, long long R, int K, int E, const float *w,
+                   const float *bias, double negative_slope, float *emb_x, float *emb_t, pof_stream_t stream);
+
+/* The same on rows stored as IEEE half (float16 storage): a row element is widened in front
+ * of its MFMA (exact), so the result is pof_attn_embed on the widened rows, bit for bit.  Same shape
+ * and alignment rules, same return codes. */
+int pof_attn_embed_f16(const void *x_f16, const void *tmpl_f16, long long R, int K, int E, const float *w,
+                       const float *bias, double negative_slope, float *emb_x, float *emb_t, pof_stream_t stream);
+
+/* No device work (no HIP call).  form = 0 for R < 8192: one workgroup per 32 x 32 output tile whose
+ * four waves are the four chains and meet in LDS; form = 1 for R >= 8192: one wave per 64 rows x 32
+ * columns that carries the four chains of both row tiles in registers.  Same bits either way.
+ * POF_E_BADARG for a NULL form or sizes < 1, POF_E_SHAPE for what the launcher refuses as a shape. */
+int pof_attn_embed_plan(long long R, int K, int E, int *form);
+
+/* ------------------------------------------------------------------------
  * A13 jump-distance segmentation + per-segment least squares
  *   src/depracted/model/adaboost_person_det.py:71-90 (cuts), :102-210 (features)
  * ranges [B][N] float32.  seg_id [B][N] int32 (segment index of every point),

@@ -53,6 +53,9 @@ SIGNATURES = {
     "pof_spatial_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p]),
     "pof_spatial_attention": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _p, _p, _p, _p]),
     "pof_spatial_attention_plan": (_i, [_i, _i, _i, _p, _p]),
+    "pof_attn_embed": (_i, [_p, _p, _ll, _i, _i, _p, _p, _d, _p, _p, _p]),
+    "pof_attn_embed_f16": (_i, [_p, _p, _ll, _i, _i, _p, _p, _d, _p, _p, _p]),
+    "pof_attn_embed_plan": (_i, [_ll, _i, _i, _p]),
     "pof_segment_features": (_i, [_p, _p, _i, _i, _d, _i, _p, _p, _p, _p]),
     "pof_segment_features_ex": (_i, [_p, _p, _p, _i, _i, _d, _p, _p, _p, _d, _i, _p, _p, _p, _p, _p, _p]),
     "pof_gather_windows": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),

@@ -997,6 +997,48 @@ def spatial_attention_plan(B, N, F):
     return fwd.value, bwd.value
 
 
+def attn_embed(x, tmpl, weight, bias, negative_slope=0.1):
+    """A10, the gate's embedding on the folded inference route: x [R, K] (or [..., K]-shaped rows flattened by the
+    caller) float32 or float16 storage, tmpl like x or None, weight [E, K] / bias [E] float32 (Conv1d + BatchNorm folded,
+    ``_SpatialAttention.fold_for_inference``) -> (emb_x, emb_t | None) float32 [R, E] = LeakyReLU(rows @ weight.T + bias),
+    both sources in one launch.  K % 8 == 0, E in 32, 64, .. 256, R >= 1.  One documented summation order
+    (include/pof_abi.h): a row's bits do not depend on R, on the slot or on the storage type."""
+    half = isinstance(x, torch.Tensor) and x.dtype == torch.float16
+    act = torch.float16 if half else torch.float32
+    x = _dev(x, act, "x")
+    if tmpl is not None:
+        tmpl = _dev(tmpl, act, "tmpl")
+    weight = _dev(weight, torch.float32, "weight")
+    bias = _dev(bias, torch.float32, "bias")
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
+        raise ValueError("x must be [R, K] and weight [E, K]")
+    if tmpl is not None and tmpl.shape != x.shape:
+        raise ValueError("tmpl must have x's shape")
+    R, K = x.shape
+    E = weight.shape[0]
+    if bias.numel() != E:
+        raise ValueError("bias must have E entries")
+    if R < 1 or K % 8 or E % 32 or not 32 <= E <= 256:
+        raise ValueError("attn_embed: needs R >= 1, K %% 8 == 0 and E in 32, 64, .. 256 (R=%d K=%d E=%d)" % (R, K, E))
+    x = _aligned16(x)                # 16-byte operand rows: views at an offset go through a copy
+    tmpl = None if tmpl is None else _aligned16(tmpl)
+    weight = _aligned16(weight)
+    emb_x = torch.empty((R, E), dtype=torch.float32, device=x.device)
+    emb_t = None if tmpl is None else torch.empty((R, E), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.call("pof_attn_embed_f16" if half else "pof_attn_embed", _ptr(x), _ptr(tmpl), R, K, E, _ptr(weight),
+                  _ptr(bias), float(negative_slope), _ptr(emb_x), _ptr(emb_t), _stream())
+    return emb_x, emb_t
+
+
+def attn_embed_plan(R, K, E):
+    """Host-only: the kernel form attn_embed launches for R rows per source (0: four waves split K and meet in LDS,
+    1: one wave carries the four chains of 64 rows).  No device work."""
+    form = C.c_int(-1)
+    _lib.call("pof_attn_embed_plan", int(R), int(K), int(E), C.byref(form))
+    return form.value
+
+
 def band_correlation_backward(feat1, feat2, g_out, kernel_size=3, max_displacement=5):
     """Gradients of band_correlation wrt feat1 / feat2."""
     feat1 = _dev(feat1, torch.float32, "feat1")

@@ -74,14 +74,20 @@ class _SpatialAttention(nn.Module):
         return torch.cat([self._embed(flat[r0:r0 + self.embed_slab].float())
                           for r0 in range(0, max(flat.shape[0], 1), self.embed_slab)])
 
-    def fold_for_inference(self, enable=True, storage=torch.float32):
+    def fold_for_inference(self, enable=True, storage=torch.float32, embed="library"):
         """Fold the embedding's BatchNorm (running statistics) into its weight and bias.  Call after loading a
         checkpoint (``DROW.fuse_for_inference`` does); ``train()`` drops the folded copy.  ``storage``: the type the
-        features and the template are kept in on the folded inference route (float16: DESIGN 3.6)."""
+        features and the template are kept in on the folded inference route (float16: DESIGN 3.6).  ``embed``:
+        "library" issues the embedding as the library GEMM + LeakyReLU, "hip" as one ``ops.attn_embed`` launch for x
+        and the template, in either storage type."""
+        if embed not in ("library", "hip"):
+            raise ValueError('embed must be "library" or "hip"')
         self._folded = None
         self._storage = torch.float32
+        self._embed_route = "library"
         if enable:
             self._storage = storage
+            self._embed_route = embed
             conv, bn = self.conv[0], self.conv[1]
             with torch.no_grad():
                 scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
@@ -94,12 +100,24 @@ class _SpatialAttention(nn.Module):
         if mode:
             self._folded = None
             self._storage = torch.float32
+            self._embed_route = "library"
         return super().train(mode)
 
     def forward(self, x, x_template):
         """x, x_template [B, n_cutout, n_channel, n_pts] -> (fused template of the
         same shape, pre-softmax window similarities [B, n_cutout, window])."""
         B, N, C, P = x.shape
+        if getattr(self, "_embed_route", "library") == "hip" and getattr(self, "_folded", None) is not None \
+                and not self.training and x.is_cuda and not torch.is_grad_enabled():
+            # the embedding on the HIP kernel: x and the template in one launch, float16 rows un-widened
+            storage = getattr(self, "_storage", torch.float32)
+            x, x_template = x.contiguous().to(storage), x_template.contiguous().to(storage)
+            embed = torch.ops.pof.attn_embed if torch.compiler.is_compiling() else ops.attn_embed
+            emb_x, emb_t = embed(x.view(B * N, C * P), x_template.view(B * N, C * P), self._folded[0], self._folded[1],
+                                 float(self.conv[2].negative_slope))
+            E = emb_x.shape[1]
+            return _WindowedAttention.apply(emb_x.view(B, N, E), emb_t.view(B, N, E), x, x_template, self._alpha,
+                                            self._window_size, storage)
         if getattr(self, "_storage", torch.float32) == torch.float16 and getattr(self, "_folded", None) is not None \
                 and not self.training and x.is_cuda and not torch.is_grad_enabled():
             # float16 storage: the features stay float16 through the gate; only the embedding GEMM sees float32 rows
@@ -165,18 +183,22 @@ class DROW(nn.Module):
         _init_weights(self)
 
     # ---- inference on the HIP trunk kernels ------------------------------------------------
-    def fuse_for_inference(self, enable=True, storage=torch.float32):
+    def fuse_for_inference(self, enable=True, storage=torch.float32, embed="library"):
         """Fold every conv3 + BatchNorm (running statistics) + bias of the four trunk blocks into
         (transposed weight, scale, shift) triples for ``pof_conv3_bn_lrelu``.  Call after loading a
         checkpoint and after ``.cuda()``; eval-mode forwards then run the trunk as float32-MFMA
         implicit GEMMs instead of MIOpen convolutions.  (Training mode has its own HIP route, _run_block_train.)
         ``storage=torch.float16`` keeps every activation between the cutout and the heads -- trunk layers, the
         gate's template -- in float16 (half the footprint); the arithmetic, the folded parameters and the outputs
-        stay float32, every stored tensor is rounded once."""
+        stay float32, every stored tensor is rounded once.  ``embed="hip"`` (models with a gate): the
+        gate's embedding on ``ops.attn_embed`` instead of the library GEMM."""
         if storage not in (torch.float32, torch.float16):
             raise ValueError("storage must be torch.float32 or torch.float16")
+        if embed not in ("library", "hip"):
+            raise ValueError('embed must be "library" or "hip"')
         self._fused = None
         self._storage = torch.float32
+        self._embed_route = "library"
         if not enable:
             if getattr(self, "gate", None) is not None:
                 self.gate.fold_for_inference(False)
@@ -198,9 +220,10 @@ class DROW(nn.Module):
                 fused["first_unit_table"] = torch.cat((wt0[:, 0, :].t() * sc0[:, None], sh0[:, None]), dim=1).contiguous()
         self._fused = fused
         self._storage = storage
+        self._embed_route = embed
         gate = getattr(self, "gate", None)
         if gate is not None:
-            gate.fold_for_inference(True, storage)
+            gate.fold_for_inference(True, storage, embed)
         return self
 
     def train(self, mode=True):
@@ -209,6 +232,7 @@ class DROW(nn.Module):
         if mode:
             self._fused = None
             self._storage = torch.float32
+            self._embed_route = "library"
         return super().train(mode)
 
     def _slope(self, name, i):

@@ -8,6 +8,8 @@ the outputs in fixed device buffers, captures the steady-state step once and rep
 issues one graph launch per scan instead of thirty kernel launches.  Measured on MI355X
 (tools/bench_stream.py): the replay takes 0.57-0.60 ms per scan at one sensor and 2.11 ms at eight; the eager
 step is host-bound at one sensor and took 0.60 to 2.35 ms on different boxes.  Outputs are bit-identical to the eager step.
+A model fused with ``embed="hip"`` has its gate embedding as one HIP node for the scan and the template, and may keep
+float16 storage (float16 cutout and template).
 """
 import torch
 
@@ -20,7 +22,9 @@ _DEFAULT_CUTOUT = dict(fixed=True, centered=True, window_width=1.0, window_depth
 class StreamingDetector:
     """``det = StreamingDetector(model)``; ``pred_cls, pred_reg = det(scan)`` per incoming scan.
 
-    model: an eval-mode ``SpatialDROW`` on the GPU (``fuse_for_inference()`` is applied).  scan: [N] or [B, N]
+    model: an eval-mode ``SpatialDROW`` on the GPU (``fuse_for_inference()`` is applied unless the model is fused
+    already; a model fused with ``storage=torch.float16, embed="hip"`` streams with a float16 cutout and a float16
+    template, the outputs stay float32; float16 storage with the library embedding is refused).  scan: [N] or [B, N]
     ranges (B independent sensors advance in lock-step).  The returned tensors are the detector's fixed output
     buffers -- valid until the next call; ``.clone()`` to keep them.  ``feat_fused`` (the window similarities
     of the last step, input of the flow head) and ``template`` are attributes.  ``reset()`` forgets the
@@ -42,6 +46,7 @@ class StreamingDetector:
         if getattr(self.model, "_fused", None) is None:
             self.model.fuse_for_inference()
         self._fused_ref = self.model._fused
+        self._route = self._fuse_route()
         self.kw = dict(_DEFAULT_CUTOUT if cutout_kwargs is None else cutout_kwargs)
         self.B, self.N = int(batch), int(num_pts)
         dev = next(self.model.parameters()).device
@@ -61,9 +66,16 @@ class StreamingDetector:
 
     @staticmethod
     def _refuse_float16(model):
-        if getattr(model, "_fused", None) is not None and getattr(model, "_storage", torch.float32) != torch.float32:
+        """Float16 storage streams only with the HIP embedding (fuse_for_inference(storage=float16, embed="hip")):
+        the library embedding needs float32 rows, i.e. a widened copy of the scan's features and of the template per
+        step."""
+        if getattr(model, "_fused", None) is not None and getattr(model, "_storage", torch.float32) != torch.float32 \
+                and getattr(model, "_embed_route", "library") != "hip":
             raise ValueError("StreamingDetector keeps float32 storage: the model was fused with storage=%s -- "
                              "call model.fuse_for_inference() (float32) first" % model._storage)
+
+    def _fuse_route(self):
+        return (getattr(self.model, "_storage", torch.float32), getattr(self.model, "_embed_route", "library"))
 
     def reset(self):
         self._have_template = False
@@ -76,13 +88,17 @@ class StreamingDetector:
         if getattr(self.model, "_fused", None) is None:
             self.model.fuse_for_inference()
         self._refuse_float16(self.model)
-        if self.model._fused is not self._fused_ref:
+        if self.model._fused is not self._fused_ref or self._fuse_route() != self._route:
+            if self._fuse_route()[0] != self._route[0] and self.template is not None:
+                # another storage type: the running template goes on in that type (a new buffer; the graph is dropped)
+                self.template = self.template.to(self._fuse_route()[0])
             self._fused_ref = self.model._fused
+            self._route = self._fuse_route()
             self._graph = None
 
     # one step on the static buffers; `first` = no template yet
     def _step(self, first):
-        x = ops.cutout(self._scan, self.tab, workspace=self._cut_ws, **self.kw)
+        x = ops.cutout(self._scan, self.tab, workspace=self._cut_ws, out_dtype=self._route[0], **self.kw)
         with torch.no_grad():
             cls, reg, tmpl, fused = self.model(x, testing=True, fea_template=None if first else self.template)
             if self._nms is not None:

@@ -12,6 +12,8 @@ without running a kernel, and an ``opcheck``-able schema.  Device kernels only: 
         -> (Tensor out, Tensor band, Tensor prob)
     pof::spatial_attention_backward(Tensor emb_x, Tensor emb_t, Tensor tmpl, Tensor prob, Tensor g_out,
         Tensor? g_band, float alpha, int window) -> (Tensor, Tensor, Tensor, Tensor)
+    pof::attn_embed(Tensor x, Tensor? tmpl, Tensor weight, Tensor bias, float negative_slope)
+        -> (Tensor emb_x, Tensor emb_t)   (emb_t has no rows when tmpl is None)
     pof::cutout(Tensor scans, Tensor tab, int stride, bool centered, bool fixed, float window_width,
         float window_depth, int num_cutout_pts, float padding_val, bool area_mode, bool half_out) -> Tensor
     pof::conv3_bn_lrelu(Tensor x, Tensor wt, Tensor scale, Tensor shift, bool pool, float negative_slope) -> Tensor
@@ -154,6 +156,22 @@ def _attn_backward(ctx, g_out, g_band, g_prob):
 
 
 spatial_attention.register_autograd(_attn_backward, setup_context=_attn_setup)
+
+
+@torch.library.custom_op("pof::attn_embed", mutates_args=(), device_types="cuda")
+def attn_embed(x: torch.Tensor, tmpl: Optional[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor,
+               negative_slope: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The gate's embedding of x and the template in one node (inference only: no autograd formula)."""
+    emb_x, emb_t = ops.attn_embed(x.contiguous(), None if tmpl is None else tmpl.contiguous(), weight, bias,
+                                  negative_slope)
+    return emb_x, emb_x.new_empty((0, emb_x.shape[1])) if emb_t is None else emb_t
+
+
+@attn_embed.register_fake
+def _(x, tmpl, weight, bias, negative_slope):
+    R, E = x.shape[0], weight.shape[0]
+    return (x.new_empty((R, E), dtype=torch.float32),
+            x.new_empty((0 if tmpl is None else R, E), dtype=torch.float32))
 
 
 # ------------------------------------------------------------------------------------------------- A8

@@ -1,4 +1,6 @@
-"""Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay."""
+"""Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16]
+--embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template)."""
 import faulthandler, os, sys, time
 faulthandler.dump_traceback_later(90, exit=True)       # a stuck step reports where it is instead of hanging the box
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -7,8 +9,12 @@ from planar_optical_flow_amd import synth
 from planar_optical_flow_amd.streaming import StreamingDetector
 from planar_optical_flow_amd.src.depracted.model.dr_spaam import SpatialDROW
 
+EMBED = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--embed=")] or ["library"])[0]
+STORAGE = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--storage=")] or ["float32"])[0]
+sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage="))]
 torch.manual_seed(3)
 model = SpatialDROW(num_scans=5, num_pts=56, alpha=0.5, window_size=11, pedestrian_only=True).cuda().eval()
+model.fuse_for_inference(storage={"float32": torch.float32, "float16": torch.float16}[STORAGE], embed=EMBED)
 for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
     scans = torch.from_numpy(synth.make_batch(seed=9, B=B, T=40).scans).cuda()     # [B, 40, 450]
     res = {}
@@ -25,5 +31,5 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
         torch.cuda.synchronize()
         res[graph] = ((time.perf_counter() - t0) / 32 * 1e3, outs)
     same = all(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) for a, b in zip(res[False][1], res[True][1]))
-    print("streaming step B=%d: eager %.3f ms, hipGraph replay %.3f ms per scan (identical outputs: %s)"
-          % (B, res[False][0], res[True][0], same), flush=True)
+    print("streaming step B=%d [embed %s, storage %s]: eager %.3f ms, hipGraph replay %.3f ms per scan (identical outputs: %s)"
+          % (B, EMBED, STORAGE, res[False][0], res[True][0], same), flush=True)
