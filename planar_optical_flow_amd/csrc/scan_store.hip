@@ -47,11 +47,14 @@ __global__ __launch_bounds__(256) void gather_windows_kernel(const float *scans_
     }
 }
 
-// first-minimum argmin of |t[k] - t_ref| (float32) over k in [lo, hi)
+constexpr int kNoOdom = 0x7fffffff;   // wave_argmin_time found no candidate
+
+// first-minimum argmin of |t[k] - t_ref| (float32) over k in [lo, hi); kNoOdom when the range is empty or no
+// difference is finite (all NaN or infinite)
 __device__ __forceinline__ int wave_argmin_time(const float *t, int lo, int hi, float t_ref, int lane)
 {
     float best = INFINITY;
-    int bidx = 0x7fffffff;
+    int bidx = kNoOdom;
     for (int k = lo + lane; k < hi; k += 64) {
         const float d = fabsf(t[k] - t_ref);
         if (d < best) {  // strictly smaller: keeps the earliest index this lane saw
@@ -83,13 +86,15 @@ __global__ __launch_bounds__(256) void associate_odometry_kernel(const float *sc
     const int lo = odom_lo[b], hi = odom_hi[b];
     const int i1 = wave_argmin_time(odoms_t, lo, hi, scans_t[row_cur[b]], lane);
     const int i0 = wave_argmin_time(odoms_t, lo, hi, scans_t[row_prev[b]], lane);
+    // a sample without a candidate (the reference's np.argmin raises on it) gets NaN odometry and index -1: nothing
+    // is read through the sentinel
     if (lane < 3) {
-        odom1[3 * b + lane] = (double)odoms[3 * (long long)i1 + lane];
-        odom0[3 * b + lane] = (double)odoms[3 * (long long)i0 + lane];
+        odom1[3 * b + lane] = i1 == kNoOdom ? NAN : (double)odoms[3 * (long long)i1 + lane];
+        odom0[3 * b + lane] = i0 == kNoOdom ? NAN : (double)odoms[3 * (long long)i0 + lane];
     }
     if (lane == 0) {
-        if (idx1) idx1[b] = i1 - lo;
-        if (idx0) idx0[b] = i0 - lo;
+        if (idx1) idx1[b] = i1 == kNoOdom ? -1 : i1 - lo;
+        if (idx0) idx0[b] = i0 == kNoOdom ? -1 : i0 - lo;
     }
 }
 

@@ -27,6 +27,13 @@ class DROWDeviceDataset:
         """sequences: list of dict(scans_ns, scans_t, scans, odoms_t, odoms, dets_ns, dets_wc, dets_wa,
         dets_wp) with the reference's per-file arrays."""
         self.num_scans, self.scan_stride, self.distance = num_scans, scan_stride, 5
+        sequences = list(sequences)
+        for k, seq in enumerate(sequences):
+            # the reference fails on such a sequence too (np.argmin of an empty |odoms_t - t|); refused here, before
+            # anything touches the device: the association kernel has no odometry row to return for its samples
+            # (the static-scene filter below drops such a sequence whole)
+            if not drop_static and len(seq["scans"]) > 0 and len(seq["odoms"]) == 0:
+                raise ValueError("sequence %s has scans and no odometry rows" % seq.get("name", str(k)))
         self.device = torch.device(device)
         self.pre = DROWBatchPreprocessor(cutout_kwargs=cutout_kwargs, pedestrian_only=pedestrian_only,
                                          device=device)
