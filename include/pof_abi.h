@@ -267,6 +267,30 @@ int pof_nms_predicted_center(const float *ranges, const double *tab, const doubl
                              void *workspace, size_t workspace_bytes, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N5 per-person flow in the world frame
+ *   depracted_scripts/infer_person_flow.py:134-157, src/utils/viz_utils.py:556-575 (plot_person_flow_fixed_pose)
+ * One scan per batch entry, one launch.  Inputs: flow_canonical [B][N][2] float32 (a flow net's output), the
+ * NMS results instance_mask [B][N], num_det [B], det_xy [B][N][2], det_cls [B][N], and per scan the sensor pose
+ * as the reference holds it: rot [B][4] = _phi_to_rotation_matrix(odom1[2]) (src/utils/utils.py:601-606, float32,
+ * row-major), trans [B][2] = odom1[:2], flow_trans [B][2] = (odom1 - odom0)[:2].
+ * Per point:  flow_global [B][N][2] float32 = canonical_to_global_flow_torch (utils.py:92-105; the bits of
+ *   pof_rotate_flow);  flow_world [B][N][2] float64 = np.matmul(flow_global, rot.T) + flow_trans, the product in
+ *   float32 as fmaf(g1, Rt[1][c], g0 * Rt[0][c]);  rgb [B][N][3] float64 = flow_to_hsv(flow_world) (utils.py:574-584).
+ * Per detection k < num_det[b] (instance id k + 1; ids outside [1, num_det[b]] are ignored, num_det is clamped to
+ *   [0, N]):  det_count [B][N] int32 = its points;  det_flow [B][N][2], det_rgb [B][N][3] = np.mean of flow_world /
+ *   rgb over them, summed in ascending point index with float64 adds (deterministic; count 0 -> NaN);
+ *   det_xy_world [B][N][2] = fma(d1, Rt[1][c], d0 * Rt[0][c]) + trans (np.matmul(dets_xy, rot.T) + odom1[:2]);
+ *   det_valid [B][N] uint8 = det_cls >= cls_thresh (the reference draws dets_cls[j] < cls_thresh black).
+ *   Rows k >= num_det[b] of the five per-detection outputs are written as zeros.
+ * N <= 4096 (POF_E_SHAPE beyond, as for the NMS); one wave per scan up to N = 512.
+ * ---------------------------------------------------------------------- */
+int pof_person_flow(const float *flow_canonical, const double *tab, const int32_t *instance_mask,
+                    const int32_t *num_det, const double *det_xy, const double *det_cls, const float *rot,
+                    const double *trans, const double *flow_trans, double cls_thresh, int B, int N,
+                    float *flow_global, double *flow_world, double *rgb, double *det_xy_world, double *det_flow,
+                    double *det_rgb, int32_t *det_count, uint8_t *det_valid, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

@@ -1,0 +1,221 @@
+// N5: per-person flow in the world frame (depracted_scripts/infer_person_flow.py:134-157,
+// src/utils/viz_utils.py:556-575 plot_person_flow_fixed_pose), one launch per batch.
+//
+// Per point i of scan b:
+//   1. g  = canonical_to_global_flow_torch(flow_canonical)      float32, pof_rotate_flow_point (== pof_rotate_flow)
+//   2. w32[c] = fmaf(g1, Rt[1][c], g0 * Rt[0][c]),  Rt = rot[b]^T   float32: the order in which sgemm evaluates
+//      np.matmul(pred_flow, odom_rot.T) for three rows and more;  w[c] = (double)w32[c] + flow_trans[b][c]
+//   3. rgb = flow_to_hsv(w) (src/utils/utils.py:574-584): hypot / atan2 as pof_xy_to_rphi, then the arithmetic of
+//      colorsys.hsv_to_rgb with value 1; saturation 0 is exactly white.
+// Per detection k < num_det[b] (instance id k + 1): the count of its points, the float64 means of w and rgb over
+// them, the world centre fma(d1, Rt[1][c], d0 * Rt[0][c]) + trans[b][c] and cls >= cls_thresh.  Rows k >= num_det[b]
+// are zeros.  A detection without points (a later kept centre took them all) has count 0 and NaN means, like
+// np.mean of an empty selection.
+//
+// The sums are SEQUENTIAL IN POINT ORDER with plain float64 adds: no atomics, nothing that depends on scheduling, so
+// a result is the same bits in every run and in a graph replay.  A workgroup stages (id, wx, wy, r, g, b) of up to
+// kChunk points in LDS; thread t owns the instances t, t + THREADS, ... (kSlots accumulators in registers); every
+// thread then walks the staged points in index order.  All lanes read the same LDS address each step -- a broadcast,
+// no bank conflict -- and the instance id is wave-uniform, so picking the accumulator is a scalar branch and only
+// the owning lane adds.  A wave none of whose lanes owns the id skips the point.
+//   N <= 512:  one wave per scan (THREADS = 64, 8 slots), wave-level ordering only, as nms_wave_kernel;
+//   N <= 4096: 512 threads per scan, points in chunks of 512 between workgroup barriers, same point order.
+// Latency bound like the NMS it follows; reported in microseconds.
+#include <cmath>
+
+#include "pof_common.h"
+
+namespace {
+
+constexpr int kChunk = 512;        // points staged in LDS at a time
+constexpr int kSlots = 8;          // instances per thread
+constexpr int kWaveMaxN = 64 * kSlots;
+constexpr int kGroupThreads = 512;
+constexpr int kGroupMaxN = kGroupThreads * kSlots;
+
+struct PersonFlowArgs {
+    const float *flow_canonical;
+    const double *tab;
+    const int32_t *instance_mask, *num_det;
+    const double *det_xy, *det_cls;
+    const float *rot;
+    const double *trans, *flow_trans;
+    double cls_thresh;
+    int N;
+    float *flow_global;
+    double *flow_world, *rgb, *det_xy_world, *det_flow, *det_rgb;
+    int32_t *det_count;
+    uint8_t *det_valid;
+};
+
+// flow_to_hsv for one vector (the arithmetic of utils.flow_to_hsv / colorsys.hsv_to_rgb, value 1)
+__device__ __forceinline__ void flow_colour(double wx, double wy, double &cr, double &cg, double &cb)
+{
+    const double r = hypot(wx, wy), phi = atan2(wy, wx);
+    const double h = (phi + 2.0 * M_PI) / M_PI / 2;
+    const double sat = (r > 0.1 ? 0.1 : r) / 0.1;             // np.minimum keeps a NaN
+    const double h6 = h * 6.0;
+    // int(): truncation; h is in [0.5, 1.5].  A NaN flow has no sector: NumPy's cast gives INT64_MIN, whose
+    // remainder by 6 (Python's sign convention) is 4 -- stated here, the C++ cast of a NaN is undefined
+    const long long sector = h6 != h6 ? 4 : (long long)h6;
+    const double f = h6 - (double)sector;
+    const double v = 1.0;
+    const double p = v * (1.0 - sat), q = v * (1.0 - sat * f), t = v * (1.0 - sat * (1.0 - f));
+    switch ((int)(((sector % 6) + 6) % 6)) {
+        case 0: cr = v; cg = t; cb = p; break;
+        case 1: cr = q; cg = v; cb = p; break;
+        case 2: cr = p; cg = v; cb = t; break;
+        case 3: cr = p; cg = q; cb = v; break;
+        case 4: cr = t; cg = p; cb = v; break;
+        default: cr = v; cg = p; cb = q; break;
+    }
+    if (sat == 0.0) cr = cg = cb = v;
+}
+
+template <int THREADS>
+__device__ __forceinline__ void person_flow_order()
+{
+    if (THREADS == 64) {
+        // same-wave LDS hand-off (nms_lds_order): the hardware keeps a wave's LDS operations in order
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void person_flow_kernel(PersonFlowArgs a)
+{
+    __shared__ double s_v[5][kChunk];       // wx, wy, r, g, b of the staged points
+    __shared__ int s_id[kChunk];
+    const int N = a.N, b = blockIdx.x, tid = threadIdx.x;
+    const long long row = (long long)b * N;
+    int nd = a.num_det[b];
+    nd = nd < 0 ? 0 : (nd > N ? N : nd);
+    const float *R = a.rot + 4 * (long long)b;                 // rot[b] row-major; Rt[r][c] = R[2 c + r]
+    const float r00 = R[0], r01 = R[1], r10 = R[2], r11 = R[3];
+    const double ftx = a.flow_trans[2 * b], fty = a.flow_trans[2 * b + 1];
+
+    double acc[kSlots][5];
+    int cnt[kSlots];
+#pragma unroll
+    for (int c = 0; c < kSlots; ++c) {
+        cnt[c] = 0;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) acc[c][j] = 0.0;
+    }
+    // the wave that holds thread (k % THREADS) owns instance k
+    const int my_wave = tid >> 6;
+
+    for (int base = 0; base < N; base += kChunk) {
+        const int n = N - base < kChunk ? N - base : kChunk;
+        for (int j = tid; j < n; j += THREADS) {
+            const int i = base + j;
+            const long long p = row + i;
+            float g0, g1;
+            pof_rotate_flow_point<float>(a.tab[N + 2 * i], a.tab[N + 2 * i + 1], a.flow_canonical[2 * p],
+                                         a.flow_canonical[2 * p + 1], 0, g0, g1);
+            a.flow_global[2 * p] = g0;
+            a.flow_global[2 * p + 1] = g1;
+            const double wx = (double)fmaf(g1, r01, g0 * r00) + ftx;
+            const double wy = (double)fmaf(g1, r11, g0 * r10) + fty;
+            a.flow_world[2 * p] = wx;
+            a.flow_world[2 * p + 1] = wy;
+            double cr, cg, cb;
+            flow_colour(wx, wy, cr, cg, cb);
+            a.rgb[3 * p] = cr;
+            a.rgb[3 * p + 1] = cg;
+            a.rgb[3 * p + 2] = cb;
+            s_v[0][j] = wx;
+            s_v[1][j] = wy;
+            s_v[2][j] = cr;
+            s_v[3][j] = cg;
+            s_v[4][j] = cb;
+            s_id[j] = a.instance_mask[p];
+        }
+        person_flow_order<THREADS>();
+        for (int j = 0; j < n; ++j) {
+            // every lane reads the same address: the id is wave-uniform, so it can live in a scalar register
+            const int k = __builtin_amdgcn_readfirstlane(s_id[j]) - 1;
+            if (k < 0 || k >= nd) continue;                    // id 0 (no centre) and ids beyond num_det
+            const int owner = k % THREADS, slot = k / THREADS;
+            if ((owner >> 6) != my_wave) continue;
+            const double v0 = s_v[0][j], v1 = s_v[1][j], v2 = s_v[2][j], v3 = s_v[3][j], v4 = s_v[4][j];
+#pragma unroll
+            for (int c = 0; c < kSlots; ++c) {
+                if (c == slot && tid == owner) {
+                    acc[c][0] += v0;
+                    acc[c][1] += v1;
+                    acc[c][2] += v2;
+                    acc[c][3] += v3;
+                    acc[c][4] += v4;
+                    ++cnt[c];
+                }
+            }
+        }
+        person_flow_order<THREADS>();                          // the next chunk overwrites the staged points
+    }
+
+    const double tx = a.trans[2 * b], ty = a.trans[2 * b + 1];
+#pragma unroll
+    for (int c = 0; c < kSlots; ++c) {
+        const int k = tid + THREADS * c;
+        if (k >= N) continue;
+        const long long q = row + k;
+        double ox = 0.0, oy = 0.0, f[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        int count = 0;
+        uint8_t valid = 0;
+        if (k < nd) {
+            const double d0 = a.det_xy[2 * q], d1 = a.det_xy[2 * q + 1];
+            ox = fma(d1, (double)r01, d0 * (double)r00) + tx;
+            oy = fma(d1, (double)r11, d0 * (double)r10) + ty;
+            count = cnt[c];
+            const double m = (double)count;                    // 0 / 0 -> NaN, like np.mean of nothing
+#pragma unroll
+            for (int j = 0; j < 5; ++j) f[j] = acc[c][j] / m;
+            valid = a.det_cls[q] >= a.cls_thresh ? 1 : 0;
+        }
+        a.det_xy_world[2 * q] = ox;
+        a.det_xy_world[2 * q + 1] = oy;
+        a.det_flow[2 * q] = f[0];
+        a.det_flow[2 * q + 1] = f[1];
+        a.det_rgb[3 * q] = f[2];
+        a.det_rgb[3 * q + 1] = f[3];
+        a.det_rgb[3 * q + 2] = f[4];
+        a.det_count[q] = count;
+        a.det_valid[q] = valid;
+    }
+}
+
+}  // namespace
+
+extern "C" int pof_person_flow(const float *flow_canonical, const double *tab, const int32_t *instance_mask,
+                               const int32_t *num_det, const double *det_xy, const double *det_cls,
+                               const float *rot, const double *trans, const double *flow_trans,
+                               double cls_thresh, int B, int N, float *flow_global, double *flow_world,
+                               double *rgb, double *det_xy_world, double *det_flow, double *det_rgb,
+                               int32_t *det_count, uint8_t *det_valid, pof_stream_t stream)
+{
+    POF_CLEAR_STALE_ERROR();
+    if (!flow_canonical || !tab || !instance_mask || !num_det || !det_xy || !det_cls || !rot || !trans ||
+        !flow_trans || !flow_global || !flow_world || !rgb || !det_xy_world || !det_flow || !det_rgb ||
+        !det_count || !det_valid)
+        return POF_E_BADARG;
+    if (B < 0 || N < 1) return POF_E_BADARG;
+    if (N > kGroupMaxN) return POF_E_SHAPE;                    // the limit of pof_nms_predicted_center
+    if (B == 0) return POF_OK;
+    PersonFlowArgs a;
+    a.flow_canonical = flow_canonical; a.tab = tab; a.instance_mask = instance_mask; a.num_det = num_det;
+    a.det_xy = det_xy; a.det_cls = det_cls; a.rot = rot; a.trans = trans; a.flow_trans = flow_trans;
+    a.cls_thresh = cls_thresh; a.N = N;
+    a.flow_global = flow_global; a.flow_world = flow_world; a.rgb = rgb; a.det_xy_world = det_xy_world;
+    a.det_flow = det_flow; a.det_rgb = det_rgb; a.det_count = det_count; a.det_valid = det_valid;
+    if (N <= kWaveMaxN)
+        person_flow_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a);
+    else
+        person_flow_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a);
+    POF_CHECK_LAUNCH();
+    return POF_OK;
+}

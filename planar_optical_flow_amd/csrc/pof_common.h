@@ -40,6 +40,26 @@ __device__ __forceinline__ double pof_div_const(double x, double c, double rc)
     return fma(r, rc, q);
 }
 
+// A4: one flow vector between the scanner frame and the canonical frame of a scan point whose angle has cosine c
+// and sine s (src/utils/utils.py:62-105).  Evaluated in float64 and rounded to T once; to_canonical = 0 is
+// canonical_to_global_flow.  pof_rotate_flow and pof_person_flow both go through here, so they agree bit for bit.
+template <typename T>
+__device__ __forceinline__ void pof_rotate_flow_point(double c, double s, T fx_in, T fy_in, int to_canonical,
+                                                      T &ox, T &oy)
+{
+    const double fx = (double)fx_in, fy = (double)fy_in;
+    double gx, gy;
+    if (to_canonical) {
+        gx = c * fx + (-s) * fy;
+        gy = s * fx + c * fy;
+    } else {
+        gx = c * fx + s * fy;
+        gy = (-s) * fx + c * fy;
+    }
+    ox = (T)gx;
+    oy = (T)gy;
+}
+
 __device__ __forceinline__ double wave_max_f64(double v)
 {
 #pragma unroll

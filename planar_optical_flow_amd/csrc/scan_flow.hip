@@ -1259,18 +1259,10 @@ __global__ void rotate_flow_kernel(const T *in, T *out, const double *tab, long 
     long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= total) return;
     int i = (int)(p % N);
-    double c = tab[N + 2 * i], s = tab[N + 2 * i + 1];
-    double fx = (double)in[2 * p], fy = (double)in[2 * p + 1];
-    double gx, gy;
-    if (to_canonical) {
-        gx = c * fx + (-s) * fy;
-        gy = s * fx + c * fy;
-    } else {
-        gx = c * fx + s * fy;
-        gy = (-s) * fx + c * fy;
-    }
-    out[2 * p] = (T)gx;
-    out[2 * p + 1] = (T)gy;
+    T gx, gy;
+    pof_rotate_flow_point<T>(tab[N + 2 * i], tab[N + 2 * i + 1], in[2 * p], in[2 * p + 1], to_canonical, gx, gy);
+    out[2 * p] = gx;
+    out[2 * p + 1] = gy;
 }
 
 // ---- A5 ---------------------------------------------------------------------

@@ -5,6 +5,7 @@ validates shapes/dtypes on the host before a kernel sees them and launches on
 torch's current HIP stream.  No CPU fallback exists: a missing library or a CPU
 tensor raises.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -914,6 +915,74 @@ def nms_predicted_center(ranges, tab, pred_cls, pred_reg, min_dist=0.5):
                   float(min_dist), B, N, _ptr(det_xy), _ptr(det_cls), _ptr(num), _ptr(inst), None, 0,
                   _stream())
     return det_xy, det_cls, num, inst
+
+
+PersonFlow = collections.namedtuple("PersonFlow", ("flow_global", "flow_world", "rgb", "det_xy_world", "det_flow",
+                                                    "det_rgb", "det_count", "det_valid"))
+_PERSON_FLOW_OUT = (("flow_global", torch.float32, 2), ("flow_world", torch.float64, 2), ("rgb", torch.float64, 3),
+                    ("det_xy_world", torch.float64, 2), ("det_flow", torch.float64, 2), ("det_rgb", torch.float64, 3),
+                    ("det_count", torch.int32, 0), ("det_valid", torch.uint8, 0))
+
+
+def person_flow_buffers(B, N, device="cuda"):
+    """The eight outputs of ``person_flow`` for B scans of N points, zero-filled, as its ``out=`` (allocate once,
+    before a graph capture)."""
+    return PersonFlow(*(torch.zeros((B, N) + ((w,) if w else ()), dtype=dt, device=device)
+                        for _, dt, w in _PERSON_FLOW_OUT))
+
+
+def person_flow(flow_canonical, tab, instance_mask, num_det, det_xy, det_cls, rot=None, trans=None, flow_trans=None,
+                cls_thresh=0.5, out=None):
+    """N5: per-person flow in the world frame, one launch per batch (depracted_scripts/infer_person_flow.py:134-157).
+
+    flow_canonical [B,N,2] f32 (a flow net's output); instance_mask [B,N] i32, num_det [B] i32, det_xy [B,N,2] f64,
+    det_cls [B,N] f64 as ``nms_predicted_center`` returns them.  Sensor pose per scan: rot [B,2,2] (or [B,4]) f32 =
+    ``_phi_to_rotation_matrix(odom1[2])``, trans [B,2] f64 = ``odom1[:2]``, flow_trans [B,2] f64 =
+    ``(odom1 - odom0)[:2]``; the defaults (identity / zeros) leave everything in the scanner frame.
+    -> ``PersonFlow``: flow_global [B,N,2] f32, flow_world [B,N,2] f64, rgb [B,N,3] f64 per point; det_xy_world
+    [B,N,2], det_flow [B,N,2], det_rgb [B,N,3] f64, det_count [B,N] i32, det_valid [B,N] u8 per detection (rows
+    >= num_det[b] are zeros; a detection without points has count 0 and NaN means).  The per-detection means are
+    sequential float64 sums in point order: the same bits in every run.  ``out``: a ``PersonFlow`` of preallocated
+    tensors (``person_flow_buffers``)."""
+    flow_canonical = _dev(flow_canonical, torch.float32, "flow_canonical")
+    if flow_canonical.dim() != 3 or flow_canonical.shape[-1] != 2:
+        raise ValueError("flow_canonical must be [B,N,2]")
+    B, N = flow_canonical.shape[:2]
+    dev = flow_canonical.device
+    tab = _dev(tab, torch.float64, "tab")
+    instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
+    num_det = _dev(num_det, torch.int32, "num_det")
+    det_xy = _dev(det_xy, torch.float64, "det_xy")
+    det_cls = _dev(det_cls, torch.float64, "det_cls")
+    if tab.numel() != 3 * N:
+        raise ValueError("flow_canonical must be [B,N,2] matching the angle table")
+    if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_xy.shape) != (B, N, 2) or \
+            tuple(det_cls.shape) != (B, N):
+        raise ValueError("instance_mask and det_cls must be [B,N], num_det [B] and det_xy [B,N,2]")
+    if rot is None:
+        rot = torch.eye(2, dtype=torch.float32, device=dev).repeat(B, 1, 1)
+    rot = _dev(rot, torch.float32, "rot")
+    if tuple(rot.shape) not in ((B, 2, 2), (B, 4)):
+        raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
+    pose = []
+    for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
+        t = torch.zeros((B, 2), dtype=torch.float64, device=dev) if t is None else _dev(t, torch.float64, name)
+        if tuple(t.shape) != (B, 2):
+            raise ValueError("%s must be [B,2]" % name)
+        pose.append(t)
+    if out is None:
+        out = person_flow_buffers(B, N, dev)
+    else:
+        out = PersonFlow(*out)
+        for (name, dt, w), t in zip(_PERSON_FLOW_OUT, out):
+            _dev(t, dt, "out." + name)
+            if tuple(t.shape) != (B, N) + ((w,) if w else ()):
+                raise ValueError("out.%s has the wrong shape" % name)
+    with torch.cuda.device(dev):
+        _lib.call("pof_person_flow", _ptr(flow_canonical), _ptr(tab), _ptr(instance_mask), _ptr(num_det), _ptr(det_xy),
+                  _ptr(det_cls), _ptr(rot), _ptr(pose[0]), _ptr(pose[1]), float(cls_thresh), B, N,
+                  *[_ptr(t) for t in out], _stream())
+    return out
 
 
 def flow_errors(pred, target, mask=None):

@@ -302,6 +302,51 @@ def flow_to_hsv(flow):
     return np.where((sat == 0.0)[..., None], v[..., None], rgb)
 
 
+def person_flow(scan, scan_phi, pred_cls, pred_reg, pred_flow, odom1=None, odom0=None, min_dist=0.5, cls_thresh=0.5):
+    """The per-person result of depracted_scripts/infer_person_flow.py:134-157 for one scan: the centre NMS, then
+    in ONE launch the scanner-frame flow (``canonical_to_global_flow_torch``), its world-frame form
+    ``np.matmul(flow, odom_rot.T) + (odom1 - odom0)[:2]``, the colour code and, per detection, the world centre
+    ``np.matmul(dets_xy, odom_rot.T) + odom1[:2]`` and the mean flow / mean colour of its points.
+
+    scan [N], pred_cls [N,1] (sigmoid scores), pred_reg [N,2], pred_flow [N,2] canonical (cast to float32, the flow
+    nets' type); odom1 / odom0: the sensor's world (x, y, phi) at this scan and at the previous one.  Without odom1
+    everything stays in the scanner frame, without odom0 no translation is added to the flow.
+    -> dict: dets_xy_world [M,2], dets_cls [M,1], person_flow [M,2], person_rgb [M,3], count [M], valid [M] (bool:
+    ``dets_cls >= cls_thresh``, the detections the reference draws with an arrow), instance_mask [N], flow_world
+    [N,2], rgb [N,3].  A detection whose points all went to later detections has count 0 and NaN means."""
+    pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
+    assert pc.ndim == 2 and pc.shape[1] == 1
+    tab = _table_for(scan_phi)
+    xy, dc, num, inst = ops.nms_predicted_center(
+        _to_dev(scan, torch.float32).reshape(1, -1), tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
+        _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), min_dist)
+    rot, trans, flow_trans = _pose_terms(None if odom1 is None else np.asarray(odom1, dtype=np.float64)[None],
+                                         None if odom0 is None else np.asarray(odom0, dtype=np.float64)[None])
+    out = ops.person_flow(_to_dev(pred_flow, torch.float32).reshape(1, -1, 2), tab, inst, num, xy, dc,
+                          _to_dev(rot, torch.float32), _to_dev(trans, torch.float64),
+                          _to_dev(flow_trans, torch.float64), cls_thresh)
+    m = int(num[0].item())
+    host = lambda t: t[0].cpu().numpy()
+    return {"dets_xy_world": host(out.det_xy_world)[:m], "dets_cls": host(dc)[:m].reshape(-1, 1).astype(pc.dtype),
+            "person_flow": host(out.det_flow)[:m], "person_rgb": host(out.det_rgb)[:m],
+            "count": host(out.det_count)[:m], "valid": host(out.det_valid)[:m].astype(bool),
+            "instance_mask": host(inst), "flow_world": host(out.flow_world), "rgb": host(out.rgb)}
+
+
+def _pose_terms(odom1, odom0=None, batch=1):
+    """Host side of ``person_flow`` for B sensors at once: (rot [B,2,2] float32, trans [B,2], flow_trans [B,2]) of the
+    poses odom1 [B,3] = (x, y, phi) and the previous ones odom0, as infer_person_flow.py:114-117,145-146 forms them
+    (rot[b] has the bits of ``_phi_to_rotation_matrix(odom1[b, 2])``).  None: identity / zeros for `batch` sensors."""
+    if odom1 is None:
+        return np.tile(np.eye(2, dtype=np.float32), (batch, 1, 1)), np.zeros((batch, 2)), np.zeros((batch, 2))
+    odom1 = np.asarray(odom1, dtype=np.float64).reshape(-1, 3)
+    c, s = np.cos(odom1[:, 2]), np.sin(odom1[:, 2])
+    rot = np.stack([c, -s, s, c], axis=1).astype(np.float32).reshape(-1, 2, 2)
+    flow_trans = np.zeros((len(odom1), 2)) if odom0 is None else \
+        (odom1 - np.asarray(odom0, dtype=np.float64).reshape(-1, 3))[:, :2]
+    return rot, odom1[:, :2].copy(), flow_trans
+
+
 def data_augmentation(sample_dict):
     """:129-144.  Host-side random left-right flip (uses the global NumPy RNG like
     the reference)."""

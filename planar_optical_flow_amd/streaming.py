@@ -10,7 +10,11 @@ issues one graph launch per scan instead of thirty kernel launches.  Measured on
 step is host-bound at one sensor and took 0.60 to 2.35 ms on different boxes.  Outputs are bit-identical to the eager step.
 A model fused with ``embed="hip"`` has its gate embedding as one HIP node for the scan and the template, and may keep
 float16 storage (float16 cutout and template).
+With a ``flow_model`` the step ends in the per-person flow (``ops.person_flow``): a flow net on the previous
+and the current scan, then one launch that turns its output, the NMS masks and the sensor pose into one world-frame
+flow vector and colour per detection -- still one replay per scan, nothing per point crosses to the host.
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -30,10 +34,17 @@ class StreamingDetector:
     of the last step, input of the flow head) and ``template`` are attributes.  ``reset()`` forgets the
     template, as at the start of a sequence.  ``graph=False`` runs the same step eagerly (reference for
     tests and timing).  With ``nms_min_dist`` (one-logit models) the greedy centre NMS of
-    ``utils.nms_predicted_center`` runs inside the same step and ``detections()`` returns its result."""
+    ``utils.nms_predicted_center`` runs inside the same step and ``detections()`` returns its result.
+
+    ``flow_model`` (needs ``nms_min_dist``): an eval-mode module mapping (previous scan [B,N,1], scan [B,N,1]) to a
+    canonical flow [B,N,2], e.g. a fused ``Prototype``.  The detector keeps the previous scan and runs the flow
+    model and ``ops.person_flow`` as the tail of the step; ``det(scan, pose=(x, y, phi))`` ([3] or [B,3], the
+    sensor's world pose at this scan; none = scanner frame) supplies the frame, and ``person_flow()`` returns the
+    per-person result from the second scan of a sequence on.  ``cls_thresh`` is the score from which a detection
+    counts as valid."""
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
-                 nms_min_dist=None):
+                 nms_min_dist=None, flow_model=None, cls_thresh=0.5):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -63,6 +74,24 @@ class StreamingDetector:
         self.template = None            # fixed buffer once the first scan has been seen
         self._have_template = False
         self.feat_fused = self.pred_cls = self.pred_reg = None
+        self._flow_model = None
+        if flow_model is not None:
+            if self._nms is None:
+                raise ValueError("flow_model needs nms_min_dist: the per-person flow is aggregated over the NMS masks")
+            self._flow_model = flow_model.to(dev).eval()
+            self._cls_thresh = float(cls_thresh)
+            # everything the tail of the step touches is allocated here, before any capture
+            self._prev_scan = torch.zeros((self.B, self.N, 1), dtype=torch.float32, device=dev)
+            self._pf_out = ops.person_flow_buffers(self.B, self.N, dev)
+            # trans | flow_trans | rot of every sensor in one buffer: one small copy per scan from a pinned staging
+            # buffer allocated once (an event keeps the host from refilling it while its last copy is in flight)
+            self._pose_dev = torch.zeros(self.B * 48, dtype=torch.uint8, device=dev)
+            self._pose_trans, self._pose_flow_trans, self._pose_rot = self._pose_views(self._pose_dev)
+            self._pose_host = torch.zeros(self.B * 48, dtype=torch.uint8).pin_memory()
+            self._pose_host_np = tuple(v.numpy() for v in self._pose_views(self._pose_host))
+            self._pose_copied = torch.cuda.Event()
+            self._prev_pose = None
+            self._have_prev = self._have_flow = False
 
     @staticmethod
     def _refuse_float16(model):
@@ -79,6 +108,9 @@ class StreamingDetector:
 
     def reset(self):
         self._have_template = False
+        if self._flow_model is not None:
+            self._prev_pose = None
+            self._have_prev = self._have_flow = False
 
     def _ensure_fused(self):
         """The model was re-fused (new checkpoint) or left eval mode since the last step: fuse again if needed
@@ -108,6 +140,35 @@ class StreamingDetector:
                 self._dets = ops.nms_predicted_center(self._scan[:, 0], self.tab, conf, reg.double().contiguous(), self._nms)
         return cls, reg, tmpl, fused
 
+    # tail of a step with a flow model: flow net on (previous, current) scan, then the per-person launch.  Same
+    # stream as the step, so a capture stays one linear chain; writes only the fixed output buffers.
+    def _flow_tail(self):
+        with torch.no_grad():
+            flow = self._flow_model(self._prev_scan, self._scan.view(self.B, self.N, 1))
+            xy, conf, num, inst = self._dets
+            ops.person_flow(flow.float().contiguous(), self.tab, inst, num, xy, conf, self._pose_rot, self._pose_trans,
+                            self._pose_flow_trans, self._cls_thresh, out=self._pf_out)
+
+    def _pose_views(self, buf):
+        nb = self.B
+        return (buf[:16 * nb].view(torch.float64).view(nb, 2), buf[16 * nb:32 * nb].view(torch.float64).view(nb, 2),
+                buf[32 * nb:].view(torch.float32).view(nb, 2, 2))
+
+    def _set_pose(self, pose):
+        """Pose terms of this scan, formed on the host as utils.person_flow forms them, into the fixed device buffers."""
+        from .src.utils.utils import _pose_terms
+        cur = None
+        if pose is not None:
+            cur = np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose, dtype=np.float64)
+            cur = np.broadcast_to(cur.reshape(-1, 3), (self.B, 3)).copy()
+        terms = _pose_terms(cur, self._prev_pose if cur is not None else None, batch=self.B)
+        self._prev_pose = cur
+        self._pose_copied.synchronize()               # the staging buffer's previous copy has left it
+        for dst, src in zip(self._pose_host_np, (terms[1], terms[2], terms[0])):
+            dst[...] = src
+        self._pose_dev.copy_(self._pose_host, non_blocking=True)
+        self._pose_copied.record()
+
     def _store_template(self, tmpl):
         if self.template is None:
             self.template = tmpl.clone()              # allocated once: the captured graph holds its address
@@ -120,16 +181,26 @@ class StreamingDetector:
         with torch.cuda.stream(side):                 # warm-up off the capture: library handles, lazy inits
             for _ in range(2):
                 self._step(False)
+                if self._flow_model is not None:
+                    self._flow_tail()             # reads the previous scan, writes only the output buffers
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             cls, reg, tmpl, fused = self._step(False)
             self.template.copy_(tmpl)                 # feed the fused template back in place
+            if self._flow_model is not None:
+                self._flow_tail()
+                self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
         self._graph, self._out, self._graph_dets = g, (cls, reg, fused), self._dets
 
-    def __call__(self, scan):
+    def __call__(self, scan, pose=None):
         scan = torch.as_tensor(scan, dtype=torch.float32)
         self._ensure_fused()
+        replayed = False
+        if self._flow_model is not None:
+            self._set_pose(pose)
+        elif pose is not None:
+            raise ValueError("pose is only used with a flow_model")
         self._scan.copy_(scan.reshape(self.B, 1, self.N), non_blocking=True)
         if not self._have_template:                   # first scan of a sequence: eager, template = its own features
             cls, reg, tmpl, fused = self._step(True)
@@ -144,6 +215,13 @@ class StreamingDetector:
             self._graph.replay()
             cls, reg, fused = self._out
             self._dets = self._graph_dets
+            replayed = True
+        if self._flow_model is not None and not replayed:     # the captured step holds this tail itself
+            if self._have_prev:
+                self._flow_tail()
+            self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
+        if self._flow_model is not None:
+            self._have_flow, self._have_prev = self._have_prev, True
         self.pred_cls, self.pred_reg, self.feat_fused = cls, reg, fused
         return cls, reg
 
@@ -155,3 +233,19 @@ class StreamingDetector:
         xy, conf, num, inst = self._dets
         counts = num.cpu().numpy()
         return [(xy[b, :m].cpu().numpy(), conf[b, :m].cpu().numpy()) for b, m in enumerate(counts)], inst.cpu().numpy()
+
+    def person_flow(self):
+        """-> list (one dict per sensor) of the last step's per-person result, as ``utils.person_flow`` returns it
+        without the per-point entries: dets_xy_world [M,2], dets_cls [M], person_flow [M,2], person_rgb [M,3],
+        count [M], valid [M]; and the device-resident per-point outputs (``ops.PersonFlow``, valid until the next
+        call).  Needs ``flow_model`` and two scans of a sequence: the first one has no predecessor (the reference
+        skips that frame too).  Reads the counts back, i.e. synchronises."""
+        if self._flow_model is None or not self._have_flow:
+            raise RuntimeError("construct the detector with flow_model and feed it two scans of a sequence first")
+        _, conf, num, _ = self._dets
+        o = self._pf_out
+        host = lambda t, b, m: t[b, :m].cpu().numpy()
+        return [{"dets_xy_world": host(o.det_xy_world, b, m), "dets_cls": host(conf, b, m),
+                 "person_flow": host(o.det_flow, b, m), "person_rgb": host(o.det_rgb, b, m),
+                 "count": host(o.det_count, b, m), "valid": host(o.det_valid, b, m).astype(bool)}
+                for b, m in enumerate(num.cpu().numpy())], o

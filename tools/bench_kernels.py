@@ -1,5 +1,5 @@
 """Per-kernel timing on the GPU box (events on torch's current stream, which is the
-stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] ..."""
+stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -129,3 +129,27 @@ if "boost" in which:
     for n in (200, 2048):
         ms = timeit(lambda: det._search(Xd, Yd, idx[:n].contiguous(), n))
         print("stump search n=%d D=%d: %.3f ms incl. D2H of the %d results" % (n, D, ms, 5 * D))
+
+if "person" in which:
+    # N5: per-person flow next to the centre NMS it follows, 1024 scans x 450 points.  Predictions as in
+    # tests/golden/person_flow.npz (distinct sigmoid scores, regressions N(0, 0.3): about 105 detections per scan).
+    B, N = 1024, 450
+    rng = np.random.default_rng(1701)
+    tab = ops.phi_table()
+    scans = torch.from_numpy(synth.make_batch(seed=3, B=B, T=1).scans[:, 0].copy()).to(dev)
+    logit = np.stack([rng.permutation(N) for _ in range(B)]).astype(np.float64) / N * 8.0 - 4.0
+    cls = torch.from_numpy(1.0 / (1.0 + np.exp(-logit))).to(dev)
+    reg = torch.from_numpy(rng.normal(0, 0.3, (B, N, 2))).to(dev)
+    flow = torch.from_numpy(rng.normal(0, 0.06, (B, N, 2)).astype(np.float32)).to(dev)
+    ang = rng.uniform(-np.pi, np.pi, B)
+    rot = torch.from_numpy(np.stack([np.cos(ang), -np.sin(ang), np.sin(ang), np.cos(ang)], 1).astype(np.float32)).to(dev)
+    trans = torch.from_numpy(rng.uniform(40, 120, (B, 2))).to(dev)
+    ftr = torch.from_numpy(rng.normal(0, 0.05, (B, 2))).to(dev)
+    xy, dc, num, inst = ops.nms_predicted_center(scans, tab, cls, reg, 0.5)
+    out = ops.person_flow_buffers(B, N, dev)
+    for rep in range(3):                                   # alternating, to see the spread
+        ms_nms = timeit(lambda: ops.nms_predicted_center(scans, tab, cls, reg, 0.5), iters=50)
+        ms_pf = timeit(lambda: ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out), iters=50)
+        print("B=%d N=%d (%.0f detections per scan): centre NMS %.3f ms, person flow %.3f ms" %
+              (B, N, num.float().mean().item(), ms_nms, ms_pf))
+

@@ -1,6 +1,8 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16]
---embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template)."""
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff]
+--embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
+--nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
+Prototype or an elementwise scan difference as the flow model, a pose per scan."""
 import faulthandler, os, sys, time
 faulthandler.dump_traceback_later(90, exit=True)       # a stuck step reports where it is instead of hanging the box
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,7 +13,23 @@ from planar_optical_flow_amd.src.depracted.model.dr_spaam import SpatialDROW
 
 EMBED = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--embed=")] or ["library"])[0]
 STORAGE = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--storage=")] or ["float32"])[0]
-sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage="))]
+FLOW = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--flow=")] or [None])[0]
+NMS = 0.5 if (FLOW or "--nms" in sys.argv) else None
+sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms"))]
+
+
+class DiffFlow(torch.nn.Module):
+    def forward(self, prev, cur):
+        d = (cur - prev)[..., 0]
+        return torch.stack((d, 0.5 * d), dim=-1)
+
+
+flow_model = None
+if FLOW == "prototype":
+    from planar_optical_flow_amd.src.depracted.model.prototype import Prototype
+    flow_model = Prototype(in_channel=1, max_displacement=5).cuda().eval().fuse_for_inference()
+elif FLOW == "diff":
+    flow_model = DiffFlow()
 torch.manual_seed(3)
 model = SpatialDROW(num_scans=5, num_pts=56, alpha=0.5, window_size=11, pedestrian_only=True).cuda().eval()
 model.fuse_for_inference(storage={"float32": torch.float32, "float16": torch.float16}[STORAGE], embed=EMBED)
@@ -19,17 +37,19 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
     scans = torch.from_numpy(synth.make_batch(seed=9, B=B, T=40).scans).cuda()     # [B, 40, 450]
     res = {}
     for graph in (False, True):
-        det = StreamingDetector(model, batch=B, graph=graph)
+        det = StreamingDetector(model, batch=B, graph=graph, nms_min_dist=NMS, flow_model=flow_model)
+        poses = np.cumsum(np.random.default_rng(4).normal(0, 0.05, (40, B, 3)), axis=0)
+        step = (lambda t: det(scans[:, t], pose=poses[t])) if flow_model is not None else (lambda t: det(scans[:, t]))
         outs = []
         for t in range(8):
-            cls, reg = det(scans[:, t])
+            cls, reg = step(t)
             outs.append((cls.clone(), reg.clone()))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for t in range(8, 40):
-            det(scans[:, t])
+            step(t)
         torch.cuda.synchronize()
         res[graph] = ((time.perf_counter() - t0) / 32 * 1e3, outs)
     same = all(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) for a, b in zip(res[False][1], res[True][1]))
-    print("streaming step B=%d [embed %s, storage %s]: eager %.3f ms, hipGraph replay %.3f ms per scan (identical outputs: %s)"
-          % (B, EMBED, STORAGE, res[False][0], res[True][0], same), flush=True)
+    print("streaming step B=%d [embed %s, storage %s, nms %s, flow %s]: eager %.3f ms, hipGraph replay %.3f ms per scan (identical outputs: %s)"
+          % (B, EMBED, STORAGE, NMS, FLOW, res[False][0], res[True][0], same), flush=True)

@@ -325,6 +325,63 @@ def gen_gradients():
     np.savez_compressed(os.path.join(OUT, "gradients.npz"), **g)
 
 
+def gen_person_flow():
+    """N5: the per-person tail of depracted_scripts/infer_person_flow.py:134-157, driven through the reference's own
+    functions on seeded predictions: u.nms_predicted_center, u.canonical_to_global_flow_torch (float32),
+    u._phi_to_rotation_matrix, u.flow_to_hsv, and the script's np.matmul / np.mean lines.  Scores are distinct (the
+    reference's argsort is unstable on ties); some flow vectors are exactly zero."""
+    import src.utils.utils as u
+    from planar_optical_flow_amd import synth
+    rng = np.random.default_rng(1701)
+    B, N = 4, 450
+    phi = u.get_laser_phi()
+    scans = np.stack([synth.make_batch(seed=300 + b, B=1, T=1).scans[0, 0] for b in range(B)])
+    g = {k: [] for k in ("cls", "reg", "flow", "odom0", "odom1", "inst", "flow_global", "flow_world", "rgb")}
+    per_det = {k: [] for k in ("dets_xy", "dets_cls", "dets_xy_world", "det_flow", "det_rgb", "det_count")}
+    num = []
+    for b in range(B):
+        logit = rng.permutation(N).astype(np.float64) / N * 8.0 - 4.0 + rng.uniform(0, 1e-4)
+        pred_cls = (1.0 / (1.0 + np.exp(-logit))).reshape(N, 1)                  # distinct sigmoid scores
+        pred_reg = rng.normal(0, 0.3, (N, 2))
+        flow = rng.normal(0, 0.06, (N, 2)).astype(np.float32)
+        flow[rng.random(N) < 0.1] = 0.0
+        odom0 = np.array([rng.uniform(40, 80), rng.uniform(80, 120), rng.uniform(-np.pi, np.pi)])
+        odom1 = odom0 + np.array([rng.normal(0, 0.05), rng.normal(0, 0.05), rng.normal(0, 0.03)])
+        if b == 3:
+            odom1[:2] = odom0[:2]                                                # no translation: zero flow stays zero
+        pred_flow = u.canonical_to_global_flow_torch(torch.from_numpy(flow), phi).data.cpu().numpy()
+        dets_xy, dets_cls, instance_mask = u.nms_predicted_center(scans[b], phi, pred_cls, pred_reg)
+        odom_rot = u._phi_to_rotation_matrix(odom1[2])
+        dets_xy_world = np.matmul(dets_xy, odom_rot.T) + odom1[:2].reshape(1, 2)
+        pred_flow_world = np.matmul(pred_flow, odom_rot.T) + (odom1 - odom0)[:2].reshape(1, 2)
+        pred_flow_world_hsv = u.flow_to_hsv(pred_flow_world)
+        with np.errstate(all="ignore"), __import__("warnings").catch_warnings():
+            __import__("warnings").simplefilter("ignore")
+            for j in range(len(dets_xy)):
+                instance_ids = instance_mask == j + 1
+                per_det["det_flow"].append([np.mean(pred_flow_world[instance_ids, 0]),
+                                            np.mean(pred_flow_world[instance_ids, 1])])
+                per_det["det_rgb"].append(np.mean(pred_flow_world_hsv[instance_ids], axis=0))
+                per_det["det_count"].append(int(instance_ids.sum()))
+        per_det["dets_xy"].append(dets_xy), per_det["dets_cls"].append(dets_cls[:, 0])
+        per_det["dets_xy_world"].append(dets_xy_world)
+        num.append(len(dets_xy))
+        for k, v in (("cls", pred_cls), ("reg", pred_reg), ("flow", flow), ("odom0", odom0), ("odom1", odom1),
+                     ("inst", instance_mask), ("flow_global", pred_flow), ("flow_world", pred_flow_world),
+                     ("rgb", pred_flow_world_hsv)):
+            g[k].append(v)
+    out = {k: np.stack(v) for k, v in g.items()}
+    assert out["flow_global"].dtype == np.float32 and out["flow_world"].dtype == np.float64
+    out["scans"], out["num"] = scans, np.array(num, dtype=np.int32)
+    for k in ("dets_xy", "dets_cls", "dets_xy_world"):
+        out[k] = np.concatenate(per_det[k])
+    out["det_flow"], out["det_rgb"] = np.array(per_det["det_flow"]), np.array(per_det["det_rgb"])
+    out["det_count"] = np.array(per_det["det_count"], dtype=np.int32)
+    np.savez_compressed(os.path.join(OUT, "person_flow.npz"), **out)
+    print("person_flow.npz:", {k: v.shape for k, v in out.items()}, "empty detections:",
+          int((out["det_count"] == 0).sum()), os.path.getsize(os.path.join(OUT, "person_flow.npz")), "bytes")
+
+
 def main():
     _install_stubs()
     if "--only" in sys.argv:
@@ -843,6 +900,7 @@ def main():
     gen_cutout_dense()
     gen_cutout_indices()
     gen_gradients()
+    gen_person_flow()
 
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("wrote", sorted(os.listdir(OUT)), "total bytes", tot)
