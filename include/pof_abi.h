@@ -291,6 +291,42 @@ int pof_person_flow(const float *flow_canonical, const double *tab, const int32_
                     double *det_rgb, int32_t *det_count, uint8_t *det_valid, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N6 ego-motion from a flow field: the weighted least-squares inverse of
+ *   get_displacement_from_odometry(scan1_xy, odom0, odom1)   src/utils/utils.py:639-662
+ *   get_velocity_from_odometry(scan1_xy, odom0, odom1)       src/utils/utils.py:609-636
+ * One scan per batch entry, one launch.  Points p: xy [B][N][2] float64, or, when xy is NULL, ranges [B][N] float32
+ * placed by tab as rphi_to_xy does (r * cos, r * sin).  flow [B][N][2] float32 (flow_f64 = 0) or float64; with
+ * canonical != 0 it is first rotated to the scanner frame in its own type (the bits of pof_rotate_flow).  g = sign * f
+ * (sign = +-1; -1 for the reference's displacement, disp = p_now - p_prev), q = p + g.
+ * Base weight w0 = weight [B][N] float32 (NULL: 1), forced to 0 when the weight is not finite or <= 0, when ranges is
+ * given and r is not finite or >= max_range (the reference's valid mask is r < 20), when a flow or point component is
+ * not finite, and -- with instance_mask [B][N] -- when 1 <= id <= clamp(num_det[b], 0, N) and
+ * det_cls[b][id - 1] >= cls_thresh (pof_person_flow's det_valid: the point belongs to a person).
+ * model 0 (rigid, any angle): theta = atan2(S_x, S_dot), u = qm - R(theta) pm over the centred weighted moments;
+ * model 1 (linear twist g = t + omega * (-y, x)): omega = sum w (p'_x g'_y - p'_y g'_x) / S_pp, t = gm - omega (-pm_y, pm_x).
+ * A solve fails with fewer than two points of weight > 0 or S_pp not > 0.  huber_delta > 0 re-weights `iters` (0..16)
+ * times, w = w0 * (rho > delta ? delta / rho : 1) with rho the point's residual length.
+ * Outputs: motion [B][3] float64 = (theta, u_x, u_y) or (omega, t_x, t_y), NaN when a solve failed; count [B] int32 =
+ *   points with w0 > 0; rms [B] = sqrt(sum w rho^2 / W) of the last solve; ok [B] uint8; optional flow_residual
+ *   [B][N][2] float64 = the flow minus the fitted motion's flow at every point (scanner frame); optional weight_out
+ *   [B][N] float32 = the last solve's weights.
+ * Sums have a fixed order (no atomics): the same bits in every run, at every batch position, in a graph replay.
+ * N <= 4096 (POF_E_SHAPE beyond, as for the NMS); one wave per scan up to N = 512.
+ *
+ * pof_pose_advance composes a rigid motion (displacement convention) onto pose [B][3] = (x, y, phi), in place:
+ *   ok:  phi1 = phi0 + theta, t1 = t0 + R(phi0) u;  otherwise the pose stays.  It also writes (each may be NULL) what
+ *   pof_person_flow reads: rot [B][4] float32 of (cos phi1, -sin phi1, sin phi1, cos phi1), trans [B][2] = t1,
+ *   flow_trans [B][2] = t1 - t0 (zeros without ok).
+ * ---------------------------------------------------------------------- */
+int pof_ego_motion(const float *ranges, const double *xy, const double *tab, const void *flow, int flow_f64,
+                   int canonical, int sign, int model, const float *weight, const int32_t *instance_mask,
+                   const int32_t *num_det, const double *det_cls, double cls_thresh, double max_range,
+                   double huber_delta, int iters, int B, int N, double *motion, int32_t *count, double *rms,
+                   uint8_t *ok, double *flow_residual, float *weight_out, pof_stream_t stream);
+int pof_pose_advance(const double *motion, const uint8_t *ok, double *pose /* [B][3] in/out */, float *rot,
+                     double *trans, double *flow_trans, int B, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

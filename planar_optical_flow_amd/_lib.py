@@ -44,6 +44,9 @@ SIGNATURES = {
     "pof_nms_workspace_bytes": (_sz, [_i, _i]),
     "pof_nms_predicted_center": (_i, [_p, _p, _p, _p, _d, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "pof_person_flow": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _d, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pof_ego_motion": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _d, _d, _d, _i, _i, _i, _p, _p, _p, _p, _p,
+                            _p, _p]),
+    "pof_pose_advance": (_i, [_p, _p, _p, _p, _p, _p, _i, _p]),
     "pof_flow_errors": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "pof_band_correlation": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pof_band_correlation_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),

@@ -985,6 +985,118 @@ def person_flow(flow_canonical, tab, instance_mask, num_det, det_xy, det_cls, ro
     return out
 
 
+EgoMotion = collections.namedtuple("EgoMotion", ("motion", "count", "rms", "ok", "flow_residual", "weight"))
+_EGO_MOTION_OUT = (("motion", torch.float64), ("count", torch.int32), ("rms", torch.float64), ("ok", torch.uint8),
+                   ("flow_residual", torch.float64), ("weight", torch.float32))
+_EGO_MODELS = {"rigid": 0, "linear": 1}
+
+
+def _ego_motion_shapes(B, N):
+    return (B, 3), (B,), (B,), (B,), (B, N, 2), (B, N)
+
+
+def ego_motion_buffers(B, N, device="cuda"):
+    """The six outputs of ``ego_motion`` for B scans of N points, zero-filled, as its ``out=`` (allocate once, before
+    a graph capture)."""
+    return EgoMotion(*(torch.zeros(shape, dtype=dt, device=device)
+                       for (_, dt), shape in zip(_EGO_MOTION_OUT, _ego_motion_shapes(B, N))))
+
+
+def ego_motion(ranges, tab, flow, *, xy=None, canonical=True, sign=-1, model="rigid", weight=None, instance_mask=None,
+               num_det=None, det_cls=None, cls_thresh=0.5, max_range=20.0, huber_delta=0.0, iters=0, out=None):
+    """N6: the sensor's own motion from a flow field, one launch per batch -- the weighted least-squares inverse of
+    ``get_displacement_from_odometry`` / ``get_velocity_from_odometry`` (src/utils/utils.py:639-662, :609-636).
+
+    ranges [B,N] f32 (or None with ``xy`` [B,N,2] f64: exact points; with both, the ranges only gate), tab the angle
+    table (may be None with xy and ``canonical=False``), flow [B,N,2] f32 or f64, canonical or scanner frame.
+    ``sign``: q = p + sign * flow is where the point was (-1, the reference's displacement) or will be (+1).
+    ``model``: "rigid" -> motion = (theta, u_x, u_y) with q = R(theta) p + u, exact for any angle; "linear" -> motion =
+    (omega, t_x, t_y) with sign * flow = t + omega * (-y, x).  weight [B,N] f32 (<= 0 or not finite: excluded).  Points
+    with a range >= ``max_range`` or not finite, a flow that is not finite, or -- given the NMS results instance_mask
+    [B,N] i32, num_det [B] i32, det_cls [B,N] f64 -- a detection of score >= ``cls_thresh`` are excluded.
+    ``huber_delta`` > 0 re-weights ``iters`` (0..16) times by min(1, delta / residual).
+    -> ``EgoMotion``: motion [B,3] f64 (NaN when the fit failed: fewer than two points, or all at one place), count
+    [B] i32 points used, rms [B] f64, ok [B] u8, flow_residual [B,N,2] f64 (the flow with the sensor's motion taken
+    out, scanner frame), weight [B,N] f32 (the last solve's).  Fixed summation order: the same bits in every run.
+    ``out``: an ``EgoMotion`` of preallocated tensors (``ego_motion_buffers``)."""
+    if ranges is None and xy is None:
+        raise ValueError("ego_motion needs ranges or xy")
+    if sign not in (-1, 1):
+        raise ValueError("sign must be -1 or +1")
+    if model not in _EGO_MODELS:
+        raise ValueError("model must be 'rigid' or 'linear'")
+    if not 0 <= int(iters) <= 16:
+        raise ValueError("iters must be in [0, 16]")
+    if instance_mask is not None and (num_det is None or det_cls is None):
+        raise ValueError("instance_mask needs num_det and det_cls (the NMS results)")
+    if not isinstance(flow, torch.Tensor) or flow.dtype not in (torch.float32, torch.float64):
+        raise TypeError("flow must be a float32 or float64 tensor on the HIP device (no CPU path)")
+    flow = _dev(flow, flow.dtype, "flow")
+    if flow.dim() != 3 or flow.shape[-1] != 2:
+        raise ValueError("flow must be [B,N,2]")
+    B, N = flow.shape[:2]
+    dev = flow.device
+    if ranges is not None and tuple(_dev(ranges, torch.float32, "ranges").shape) != (B, N):
+        raise ValueError("ranges must be [B,N]")
+    if xy is not None and tuple(_dev(xy, torch.float64, "xy").shape) != (B, N, 2):
+        raise ValueError("xy must be [B,N,2]")
+    if tab is None:
+        if canonical or xy is None:
+            raise ValueError("the angle table is needed for a canonical flow and to place ranges")
+    elif _dev(tab, torch.float64, "tab").numel() != 3 * N:
+        raise ValueError("flow must be [B,N,2] matching the angle table")
+    if weight is not None and tuple(_dev(weight, torch.float32, "weight").shape) != (B, N):
+        raise ValueError("weight must be [B,N]")
+    if instance_mask is not None:
+        instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
+        num_det = _dev(num_det, torch.int32, "num_det")
+        det_cls = _dev(det_cls, torch.float64, "det_cls")
+        if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_cls.shape) != (B, N):
+            raise ValueError("instance_mask and det_cls must be [B,N] and num_det [B]")
+    else:
+        num_det = det_cls = None
+    if out is None:
+        out = ego_motion_buffers(B, N, dev)
+    else:
+        out = EgoMotion(*out)
+        for (name, dt), shape, t in zip(_EGO_MOTION_OUT, _ego_motion_shapes(B, N), out):
+            _dev(t, dt, "out." + name)
+            if tuple(t.shape) != shape:
+                raise ValueError("out.%s has the wrong shape" % name)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_ego_motion", _ptr(ranges), _ptr(xy), _ptr(tab), _ptr(flow), int(flow.dtype == torch.float64),
+                  int(bool(canonical)), int(sign), _EGO_MODELS[model], _ptr(weight), _ptr(instance_mask), _ptr(num_det),
+                  _ptr(det_cls), float(cls_thresh), float(max_range), float(huber_delta), int(iters), B, N,
+                  *[_ptr(t) for t in out], _stream())
+    return out
+
+
+def pose_advance(motion, ok, pose, rot=None, trans=None, flow_trans=None):
+    """Compose the rigid motion ``ego_motion`` fitted (``sign=-1``, displacement convention) onto pose [B,3] f64 =
+    (x, y, phi), IN PLACE: phi += theta, (x, y) += R(phi) u; a scan with ok = 0 keeps its pose.  Optionally writes the
+    pose terms ``person_flow`` reads: rot [B,2,2] (or [B,4]) f32, trans [B,2] f64 and flow_trans [B,2] f64 (the
+    translation of this step; zeros without ok).  -> pose."""
+    motion = _dev(motion, torch.float64, "motion")
+    ok = _dev(ok, torch.uint8, "ok")
+    pose = _dev(pose, torch.float64, "pose")
+    B = pose.shape[0] if pose.dim() == 2 else -1
+    if tuple(pose.shape) != (B, 3) or tuple(motion.shape) != (B, 3) or tuple(ok.shape) != (B,):
+        raise ValueError("motion and pose must be [B,3] and ok [B]")
+    if rot is not None and tuple(_dev(rot, torch.float32, "rot").shape) not in ((B, 2, 2), (B, 4)):
+        raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
+    for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
+        if t is not None and tuple(_dev(t, torch.float64, name).shape) != (B, 2):
+            raise ValueError("%s must be [B,2]" % name)
+    if B == 0:
+        return pose
+    with torch.cuda.device(pose.device):
+        _lib.call("pof_pose_advance", _ptr(motion), _ptr(ok), _ptr(pose), _ptr(rot), _ptr(trans), _ptr(flow_trans), B,
+                  _stream())
+    return pose
+
+
 def flow_errors(pred, target, mask=None):
     """A12 reductions: returns (epe_sum [B], aae_sum [B] radians, count [B]) float64."""
     pred = _dev(pred, torch.float32, "pred")

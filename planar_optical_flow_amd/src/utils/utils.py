@@ -200,6 +200,58 @@ def get_velocity_from_odometry(scan1_xy, odom0, odom1):
     return _flow_xy(ops.FLOW_VELOCITY, scan1_xy, odom0, odom1)
 
 
+# ------------------------------------------------------------------ N6: the two functions above, inverted
+def _fit_xy(scan1_xy, flow, sign, model, weight, huber_delta, iters):
+    xy = _to_dev(scan1_xy, torch.float64).reshape(1, -1, 2)
+    res = ops.ego_motion(None, None, _to_dev(flow, torch.float64).reshape(1, -1, 2), xy=xy, canonical=False, sign=sign,
+                         model=model, weight=None if weight is None else _to_dev(weight, torch.float32).reshape(1, -1),
+                         huber_delta=huber_delta, iters=iters)
+    return res.motion[0].cpu().numpy()
+
+
+def get_odometry_from_displacement(scan1_xy, disp, odom0, weight=None, huber_delta=0.0, iters=0):
+    """Inverse of ``get_displacement_from_odometry`` (:639-662): the rigid least-squares fit of scan1_xy ->
+    scan1_xy - disp, composed onto odom0 = (x, y, phi).  -> odom1 [3] (NaN where the fit fails: fewer than two points,
+    or all at one place).  weight [N], huber_delta, iters: as ``ops.ego_motion``."""
+    th, ux, uy = _fit_xy(scan1_xy, disp, -1, "rigid", weight, huber_delta, iters)
+    odom0 = np.asarray(odom0, dtype=np.float64)
+    c, s = np.cos(odom0[2]), np.sin(odom0[2])
+    return np.array([odom0[0] + (c * ux - s * uy), odom0[1] + (s * ux + c * uy), odom0[2] + th])
+
+
+def get_odometry_from_velocity(scan1_xy, v_dt, odom0, weight=None, huber_delta=0.0, iters=0):
+    """Inverse of ``get_velocity_from_odometry`` (:609-636): the linear fit v_dt = t + omega * (-y, x); the heading
+    changes by -omega and the position by -R(phi1) t.  -> odom1 [3]."""
+    om, tx, ty = _fit_xy(scan1_xy, v_dt, 1, "linear", weight, huber_delta, iters)
+    odom0 = np.asarray(odom0, dtype=np.float64)
+    phi1 = odom0[2] - om
+    c, s = np.cos(phi1), np.sin(phi1)
+    return np.array([odom0[0] - (c * tx - s * ty), odom0[1] - (s * tx + c * ty), phi1])
+
+
+def ego_motion(scan, scan_phi, pred_flow, pred_cls=None, pred_reg=None, min_dist=0.5, cls_thresh=0.5, max_range=20.0,
+               huber_delta=0.02, iters=4):
+    """The sensor's own motion between the previous scan and this one from a canonical flow field [N,2] (cast to
+    float32, the flow nets' type), as a displacement: a point now at p was at R(theta) p + u.  With pred_cls [N,1]
+    (sigmoid scores) and pred_reg [N,2] the centre NMS runs first and the points of detections with a score >=
+    cls_thresh stay out of the fit.  -> dict: motion [3] = (theta, u_x, u_y), ok (bool), count, rms, flow_residual
+    [N,2] (the scanner-frame flow with the sensor's motion taken out: a person's own motion)."""
+    tab = _table_for(scan_phi)
+    ranges = _to_dev(scan, torch.float32).reshape(1, -1)
+    gate = {}
+    if pred_cls is not None and pred_reg is not None:
+        pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
+        assert pc.ndim == 2 and pc.shape[1] == 1
+        _, dc, num, inst = ops.nms_predicted_center(ranges, tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
+                                                    _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), min_dist)
+        gate = dict(instance_mask=inst, num_det=num, det_cls=dc, cls_thresh=cls_thresh)
+    res = ops.ego_motion(ranges, tab, _to_dev(pred_flow, torch.float32).reshape(1, -1, 2), max_range=max_range,
+                         huber_delta=huber_delta, iters=iters, **gate)
+    host = lambda t: t[0].cpu().numpy()
+    return {"motion": host(res.motion), "ok": bool(res.ok[0].item()), "count": int(res.count[0].item()),
+            "rms": float(res.rms[0].item()), "flow_residual": host(res.flow_residual)}
+
+
 # ------------------------------------------------------------------ A6
 def _csr_one(dets, cls_ids):
     d = np.asarray(dets, dtype=np.float64).reshape(-1, 2)

@@ -13,6 +13,9 @@ float16 storage (float16 cutout and template).
 With a ``flow_model`` the step ends in the per-person flow (``ops.person_flow``): a flow net on the previous
 and the current scan, then one launch that turns its output, the NMS masks and the sensor pose into one world-frame
 flow vector and colour per detection -- still one replay per scan, nothing per point crosses to the host.
+With ``ego_motion`` the pose is not an input any more: ``ops.ego_motion`` fits the sensor's motion to the flow of the
+points that are not people, ``ops.pose_advance`` dead-reckons the pose on the device, and the per-person launch reads
+the pose terms it wrote -- two more nodes in the same linear chain, no host copy.
 """
 import numpy as np
 import torch
@@ -41,10 +44,16 @@ class StreamingDetector:
     model and ``ops.person_flow`` as the tail of the step; ``det(scan, pose=(x, y, phi))`` ([3] or [B,3], the
     sensor's world pose at this scan; none = scanner frame) supplies the frame, and ``person_flow()`` returns the
     per-person result from the second scan of a sequence on.  ``cls_thresh`` is the score from which a detection
-    counts as valid."""
+    counts as valid.
+
+    ``ego_motion`` (needs ``flow_model``): None, or a dict of ``huber_delta`` (0.02), ``iters`` (4), ``max_range``
+    (20.0) and ``cls_thresh`` (the detector's) for ``ops.ego_motion``.  The detector then takes no pose: the flow
+    model's output over the points outside this scan's confident detections gives the motion since the previous scan,
+    a [B,3] pose state on the device is advanced by it (``reset(pose=...)`` sets it, zeros by default), and the
+    per-person flow is in the frame of that dead-reckoned pose.  ``ego_motion()`` returns the fit and the pose."""
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
-                 nms_min_dist=None, flow_model=None, cls_thresh=0.5):
+                 nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -74,7 +83,9 @@ class StreamingDetector:
         self.template = None            # fixed buffer once the first scan has been seen
         self._have_template = False
         self.feat_fused = self.pred_cls = self.pred_reg = None
-        self._flow_model = None
+        self._flow_model = self._ego_kw = None
+        if ego_motion is not None and flow_model is None:
+            raise ValueError("ego_motion needs flow_model: the motion is fitted to the flow field")
         if flow_model is not None:
             if self._nms is None:
                 raise ValueError("flow_model needs nms_min_dist: the per-person flow is aggregated over the NMS masks")
@@ -92,6 +103,15 @@ class StreamingDetector:
             self._pose_copied = torch.cuda.Event()
             self._prev_pose = None
             self._have_prev = self._have_flow = False
+            if ego_motion is not None:
+                kw = dict(huber_delta=0.02, iters=4, max_range=20.0, cls_thresh=self._cls_thresh)
+                unknown = set(ego_motion) - set(kw)
+                if unknown:
+                    raise ValueError("unknown ego_motion settings: %s" % sorted(unknown))
+                kw.update(ego_motion)
+                self._ego_kw = kw
+                self._ego_out = ops.ego_motion_buffers(self.B, self.N, dev)
+                self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
 
     @staticmethod
     def _refuse_float16(model):
@@ -106,11 +126,20 @@ class StreamingDetector:
     def _fuse_route(self):
         return (getattr(self.model, "_storage", torch.float32), getattr(self.model, "_embed_route", "library"))
 
-    def reset(self):
+    def reset(self, pose=None):
+        """Forget the template (and the previous scan).  pose ([3] or [B,3], ego-motion detectors only): the pose the
+        dead reckoning starts from; zeros by default."""
+        if pose is not None and self._ego_kw is None:
+            raise ValueError("reset(pose=...) is only used with ego_motion")
         self._have_template = False
         if self._flow_model is not None:
             self._prev_pose = None
             self._have_prev = self._have_flow = False
+        if self._ego_kw is not None:
+            start = np.zeros((self.B, 3)) if pose is None else np.broadcast_to(
+                np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose,
+                           dtype=np.float64).reshape(-1, 3), (self.B, 3)).copy()
+            self._pose_state.copy_(torch.from_numpy(start))
 
     def _ensure_fused(self):
         """The model was re-fused (new checkpoint) or left eval mode since the last step: fuse again if needed
@@ -146,7 +175,15 @@ class StreamingDetector:
         with torch.no_grad():
             flow = self._flow_model(self._prev_scan, self._scan.view(self.B, self.N, 1))
             xy, conf, num, inst = self._dets
-            ops.person_flow(flow.float().contiguous(), self.tab, inst, num, xy, conf, self._pose_rot, self._pose_trans,
+            flow = flow.float().contiguous()
+            if self._ego_kw is not None:
+                # the sensor's motion from the flow outside this scan's confident detections, then the pose: the
+                # second launch writes the rot / trans / flow_trans buffers the per-person launch reads
+                ego = ops.ego_motion(self._scan[:, 0], self.tab, flow, instance_mask=inst, num_det=num, det_cls=conf,
+                                     out=self._ego_out, **self._ego_kw)
+                ops.pose_advance(ego.motion, ego.ok, self._pose_state, self._pose_rot, self._pose_trans,
+                                 self._pose_flow_trans)
+            ops.person_flow(flow, self.tab, inst, num, xy, conf, self._pose_rot, self._pose_trans,
                             self._pose_flow_trans, self._cls_thresh, out=self._pf_out)
 
     def _pose_views(self, buf):
@@ -179,10 +216,13 @@ class StreamingDetector:
         side = torch.cuda.Stream(device=self._scan.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                 # warm-up off the capture: library handles, lazy inits
+            pose = None if self._ego_kw is None else self._pose_state.clone()
             for _ in range(2):
                 self._step(False)
                 if self._flow_model is not None:
                     self._flow_tail()             # reads the previous scan, writes only the output buffers
+            if pose is not None:
+                self._pose_state.copy_(pose)      # ... and the pose state, which the warm-up must not advance
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -197,7 +237,10 @@ class StreamingDetector:
         scan = torch.as_tensor(scan, dtype=torch.float32)
         self._ensure_fused()
         replayed = False
-        if self._flow_model is not None:
+        if self._ego_kw is not None:
+            if pose is not None:
+                raise ValueError("an ego_motion detector takes no pose: it dead-reckons its own (reset(pose=...))")
+        elif self._flow_model is not None:
             self._set_pose(pose)
         elif pose is not None:
             raise ValueError("pose is only used with a flow_model")
@@ -249,3 +292,15 @@ class StreamingDetector:
                  "person_flow": host(o.det_flow, b, m), "person_rgb": host(o.det_rgb, b, m),
                  "count": host(o.det_count, b, m), "valid": host(o.det_valid, b, m).astype(bool)}
                 for b, m in enumerate(num.cpu().numpy())], o
+
+    def ego_motion(self):
+        """-> list (one dict per sensor) of the last step's fit: motion [3] = (theta, u_x, u_y) since the previous
+        scan, ok, count, rms, and pose [3], the dead-reckoned (x, y, phi) at this scan; and the device-resident
+        outputs (``ops.EgoMotion``, valid until the next call).  Needs ``ego_motion`` and two scans of a sequence.
+        Synchronises."""
+        if self._ego_kw is None or not self._have_flow:
+            raise RuntimeError("construct the detector with ego_motion and feed it two scans of a sequence first")
+        o = self._ego_out
+        motion, ok, count, rms, pose = (t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, self._pose_state))
+        return [{"motion": motion[b], "ok": bool(ok[b]), "count": int(count[b]), "rms": float(rms[b]), "pose": pose[b]}
+                for b in range(self.B)], o

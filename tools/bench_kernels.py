@@ -147,9 +147,15 @@ if "person" in which:
     ftr = torch.from_numpy(rng.normal(0, 0.05, (B, 2))).to(dev)
     xy, dc, num, inst = ops.nms_predicted_center(scans, tab, cls, reg, 0.5)
     out = ops.person_flow_buffers(B, N, dev)
+    # N6: the ego-motion fit on the same scans, flow and NMS results (the launch that sits between the two), plain
+    # and with four Huber re-weightings
+    ego_out = ops.ego_motion_buffers(B, N, dev)
+    ego = lambda iters: ops.ego_motion(scans, tab, flow, instance_mask=inst, num_det=num, det_cls=dc, huber_delta=0.02,
+                                       iters=iters, out=ego_out)
     for rep in range(3):                                   # alternating, to see the spread
         ms_nms = timeit(lambda: ops.nms_predicted_center(scans, tab, cls, reg, 0.5), iters=50)
         ms_pf = timeit(lambda: ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out), iters=50)
-        print("B=%d N=%d (%.0f detections per scan): centre NMS %.3f ms, person flow %.3f ms" %
-              (B, N, num.float().mean().item(), ms_nms, ms_pf))
+        ms_e0, ms_e4 = timeit(lambda: ego(0), iters=50), timeit(lambda: ego(4), iters=50)
+        print("B=%d N=%d (%.0f detections per scan): centre NMS %.3f ms, person flow %.3f ms, ego_motion %.3f ms "
+              "(iters=0) %.3f ms (iters=4)" % (B, N, num.float().mean().item(), ms_nms, ms_pf, ms_e0, ms_e4))
 
