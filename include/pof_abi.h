@@ -327,6 +327,47 @@ int pof_pose_advance(const double *motion, const uint8_t *ok, double *pose /* [B
                      double *trans, double *flow_trans, int B, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N7 person tracks: gated greedy nearest-neighbour association of a scan's detections with persistent tracks, and a
+ * constant-velocity Kalman filter per track whose time step is one scan.  The reference has no tracker; the
+ * specification is this comment (restated in float64 NumPy by tests/test_tracks.py).
+ * One sensor per batch entry, one launch.  Inputs, as pof_person_flow and the NMS write them: det_xy_world [B][N][2],
+ * det_flow [B][N][2] float64, det_valid [B][N] uint8, num_det [B] (clamped to [0, N]), instance_mask [B][N].
+ * State, in place, M = max_tracks slots per sensor: track_id [B][M] int32 (0 = free), track_state [B][M][4] float64 =
+ * (x, y, vx, vy) with the velocity in metres per scan, track_cov [B][M][3] float64 = (a, b, c) = position variance,
+ * position/velocity covariance, velocity variance (one 2x2 block for both axes: every noise is isotropic),
+ * track_hits / track_misses / track_age [B][M] int32, next_id [B] int32 (starts at 1).
+ * One step, float64, plain multiplies and adds in this order (no FMA):
+ *   1. every live slot:  x += vx, y += vy;  a <- (a + b) + (b + c), b <- b + c, c <- c + q;  age += 1
+ *   2. candidates: rows k < num_det with det_valid[k] != 0 and both centre components finite
+ *   3. cost(t, k) = dx dx + dy dy, dx = zx - x, dy = zy - y; a pair takes part while cost <= gate gate
+ *   4. repeatedly the pair of smallest cost among unassigned slots and candidates; ties go to the lower slot, then the
+ *      lower row; stop when no pair is inside the gate
+ *   5. matched slot:  s = a + r_pos, k1 = a / s, k2 = b / s, r = z - p;  p += k1 r, v += k2 r;
+ *        (a, b, c) <- (a - k1 a, b - k1 b, c - k2 b);
+ *      then, if both components of the row's det_flow f are finite:  s = c + r_vel, k1 = b / s, k2 = c / s, r = f - v;
+ *        p += k1 r, v += k2 r;  (a, b, c) <- (a - k1 b, b - k1 c, c - k2 c);
+ *      hits += 1, misses = 0
+ *   6. unmatched live slot: misses += 1; beyond max_misses the slot is freed and all its fields are zeroed
+ *   7. births: unmatched candidates in ascending row order, each into the lowest free slot (slots freed in 6 count):
+ *      id = next_id++, p = z, v = f if finite else 0, cov = (r_pos, 0, r_vel) if f was finite else (r_pos, 0, v0_var),
+ *      hits = 1, misses = 0, age = 0; with no free slot dropped += 1
+ * Outputs, overwritten every step: track_det [B][M] int32 = the detection row the slot was matched with or born from
+ *   in this step, else -1; track_confirmed [B][M] uint8 = live and hits >= min_hits; det_track [B][N] int32 = the
+ *   track id of each detection row or 0; point_track [B][N] int32 = det_track[instance - 1], 0 for instance ids
+ *   outside [1, num_det]; dropped [B] int32 = candidates that found no free slot in this step.
+ * One wave per sensor, no atomics: the same bits in every run, at every batch position and in a graph replay.
+ * max_tracks <= 256, N <= 4096 (POF_E_SHAPE beyond, nothing touched); every row may be a candidate (the candidate cap
+ * is N).  gate, q >= 0 and r_pos, r_vel, v0_var > 0, max_misses >= 0 (POF_E_BADARG otherwise).
+ * ---------------------------------------------------------------------- */
+int pof_track_update(const double *det_xy_world, const double *det_flow, const uint8_t *det_valid,
+                     const int32_t *num_det, const int32_t *instance_mask, int B, int N, int max_tracks,
+                     int32_t *track_id, double *track_state, double *track_cov, int32_t *track_hits,
+                     int32_t *track_misses, int32_t *track_age, int32_t *next_id, int32_t *track_det,
+                     uint8_t *track_confirmed, int32_t *det_track, int32_t *point_track, int32_t *dropped,
+                     double gate, double q, double r_pos, double r_vel, double v0_var, int max_misses, int min_hits,
+                     pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

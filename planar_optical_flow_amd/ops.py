@@ -1097,6 +1097,82 @@ def pose_advance(motion, ok, pose, rot=None, trans=None, flow_trans=None):
     return pose
 
 
+TrackState = collections.namedtuple("TrackState", ("track_id", "track_state", "track_cov", "track_hits", "track_misses",
+                                                    "track_age", "next_id", "track_det", "track_confirmed",
+                                                    "det_track", "point_track", "dropped"))
+# name, dtype, per ("M": slot, "N": detection row / point, "B": sensor), trailing width
+_TRACK_FIELDS = (("track_id", torch.int32, "M", 0), ("track_state", torch.float64, "M", 4),
+                 ("track_cov", torch.float64, "M", 3), ("track_hits", torch.int32, "M", 0),
+                 ("track_misses", torch.int32, "M", 0), ("track_age", torch.int32, "M", 0),
+                 ("next_id", torch.int32, "B", 0), ("track_det", torch.int32, "M", 0),
+                 ("track_confirmed", torch.uint8, "M", 0), ("det_track", torch.int32, "N", 0),
+                 ("point_track", torch.int32, "N", 0), ("dropped", torch.int32, "B", 0))
+_TRACK_PERSISTENT = ("track_id", "track_state", "track_cov", "track_hits", "track_misses", "track_age", "next_id")
+
+
+def _track_shape(per, w, B, M, N):
+    return ((B,) if per == "B" else (B, M if per == "M" else N)) + ((w,) if w else ())
+
+
+def track_buffers(B, max_tracks, N, device="cuda"):
+    """The state and the outputs of ``track_update`` for B sensors, ``max_tracks`` slots and N detection rows: a
+    ``TrackState`` of zeros with ``next_id`` = 1 (allocate once, before a graph capture)."""
+    state = TrackState(*(torch.zeros(_track_shape(per, w, B, int(max_tracks), N), dtype=dt, device=device)
+                         for _, dt, per, w in _TRACK_FIELDS))
+    state.next_id.fill_(1)
+    return state
+
+
+def track_reset(state):
+    """Free every track and restart the ids at 1, in place, with tensor ops on the current stream (no host sync)."""
+    state = TrackState(*state)
+    for t in state:
+        t.zero_()
+    state.next_id.fill_(1)
+    return state
+
+
+def track_update(det_xy_world, det_flow, det_valid, num_det, instance_mask, state, *, gate=0.5, q=1e-4, r_pos=2.5e-3,
+                 r_vel=2.5e-3, v0_var=0.25, max_misses=3, min_hits=3):
+    """N7: one step of the person tracks, one launch per batch (include/pof_abi.h has the step in full).
+
+    det_xy_world [B,N,2], det_flow [B,N,2] f64 and det_valid [B,N] u8 as ``person_flow`` returns them, num_det [B] i32
+    and instance_mask [B,N] i32 as the NMS does.  ``state``: a ``TrackState`` (``track_buffers``), updated IN PLACE:
+    every live track is predicted one scan ahead (centre + velocity), detections inside ``gate`` metres are associated
+    greedily by distance (ties: lower slot, lower row), a matched track takes a position update (noise ``r_pos`` m^2) and,
+    when the detection's flow is finite, a velocity update (``r_vel``); ``q`` is the velocity process noise per scan.
+    An unmatched track is dropped after more than ``max_misses`` misses, an unmatched detection starts a track with
+    the flow as its velocity (variance ``v0_var`` without one), and a track counts as confirmed from ``min_hits`` hits.
+    -> state; its track_det / track_confirmed / det_track / point_track / dropped describe this step.
+    max_tracks <= 256, N <= 4096.  The same bits in every run."""
+    det_xy_world = _dev(det_xy_world, torch.float64, "det_xy_world")
+    if det_xy_world.dim() != 3 or det_xy_world.shape[-1] != 2:
+        raise ValueError("det_xy_world must be [B,N,2]")
+    B, N = det_xy_world.shape[:2]
+    det_flow = _dev(det_flow, torch.float64, "det_flow")
+    det_valid = _dev(det_valid, torch.uint8, "det_valid")
+    num_det = _dev(num_det, torch.int32, "num_det")
+    instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
+    if tuple(det_flow.shape) != (B, N, 2) or tuple(det_valid.shape) != (B, N) or tuple(num_det.shape) != (B,) or \
+            tuple(instance_mask.shape) != (B, N):
+        raise ValueError("det_flow must be [B,N,2], det_valid and instance_mask [B,N] and num_det [B]")
+    state = TrackState(*state)
+    if state.track_id.dim() != 2:
+        raise ValueError("state.track_id must be [B,max_tracks]")
+    M = state.track_id.shape[1]
+    for (name, dt, per, w), t in zip(_TRACK_FIELDS, state):
+        _dev(t, dt, "state." + name)
+        if tuple(t.shape) != _track_shape(per, w, B, M, N):
+            raise ValueError("state.%s has the wrong shape" % name)
+    if B == 0:
+        return state
+    with torch.cuda.device(det_xy_world.device):
+        _lib.call("pof_track_update", _ptr(det_xy_world), _ptr(det_flow), _ptr(det_valid), _ptr(num_det),
+                  _ptr(instance_mask), B, N, M, *[_ptr(t) for t in state], float(gate), float(q), float(r_pos),
+                  float(r_vel), float(v0_var), int(max_misses), int(min_hits), _stream())
+    return state
+
+
 def flow_errors(pred, target, mask=None):
     """A12 reductions: returns (epe_sum [B], aae_sum [B] radians, count [B]) float64."""
     pred = _dev(pred, torch.float32, "pred")

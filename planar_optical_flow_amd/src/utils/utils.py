@@ -385,6 +385,54 @@ def person_flow(scan, scan_phi, pred_cls, pred_reg, pred_flow, odom1=None, odom0
             "instance_mask": host(inst), "flow_world": host(out.flow_world), "rgb": host(out.rgb)}
 
 
+class PersonTracker:
+    """Person tracks over the results of ``person_flow``, scan after scan (``ops.track_update``, one launch per scan;
+    the reference has no tracker).  ``tracker = PersonTracker(max_tracks=64, gate=0.5, ...)`` with the settings of
+    ``ops.track_update``; ``ids, tracks = tracker.update(result)`` per scan, ``tracker.reset()`` between sequences.
+
+    ``update(result)``: the dict ``person_flow`` returns (dets_xy_world [M,2], person_flow [M,2], valid [M] and, when
+    present, instance_mask [N]), NumPy in and NumPy out.  -> ids [M] int32, the track id of every detection (0: not
+    valid, or no slot was free), and the live tracks as a dict of arrays in slot order: id, xy [T,2], velocity [T,2]
+    (metres per scan), cov [T,3], hits, misses, age, confirmed and det (the detection's row, -1 when missed); with an
+    instance_mask also point_track [N], the track id of every scan point."""
+
+    def __init__(self, max_tracks=64, **settings):
+        unknown = set(settings) - {"gate", "q", "r_pos", "r_vel", "v0_var", "max_misses", "min_hits"}
+        if unknown:
+            raise ValueError("unknown tracks settings: %s" % sorted(unknown))
+        self.max_tracks, self.settings = int(max_tracks), settings
+        self._persistent = None
+
+    def reset(self):
+        self._persistent = None
+
+    def update(self, result):
+        xy = np.asarray(result["dets_xy_world"], dtype=np.float64).reshape(-1, 2)
+        m = len(xy)
+        inst = result.get("instance_mask")
+        n = max(m, 1) if inst is None else len(inst)
+        dev = _device()
+        pad = lambda a, dtype, *w: torch.from_numpy(np.concatenate(
+            [np.asarray(a, dtype=dtype).reshape((m,) + w), np.zeros((n - m,) + w, dtype)])[None]).to(dev)
+        state = ops.track_buffers(1, self.max_tracks, n, dev)
+        if self._persistent is not None:
+            state = state._replace(**self._persistent)
+        ops.track_update(pad(xy, np.float64, 2), pad(result["person_flow"], np.float64, 2),
+                         pad(result["valid"], np.uint8), torch.full((1,), m, dtype=torch.int32, device=dev),
+                         torch.zeros((1, n), dtype=torch.int32, device=dev) if inst is None else
+                         _to_dev(inst, torch.int32).reshape(1, n), state, **self.settings)
+        self._persistent = {k: getattr(state, k) for k in ops._TRACK_PERSISTENT}
+        h = {k: getattr(state, k)[0].cpu().numpy() for k in state._fields}
+        live = np.flatnonzero(h["track_id"])
+        tracks = {"id": h["track_id"][live], "xy": h["track_state"][live, :2], "velocity": h["track_state"][live, 2:],
+                  "cov": h["track_cov"][live], "hits": h["track_hits"][live], "misses": h["track_misses"][live],
+                  "age": h["track_age"][live], "confirmed": h["track_confirmed"][live].astype(bool),
+                  "det": h["track_det"][live]}
+        if inst is not None:
+            tracks["point_track"] = h["point_track"]
+        return h["det_track"][:m], tracks
+
+
 def _pose_terms(odom1, odom0=None, batch=1):
     """Host side of ``person_flow`` for B sensors at once: (rot [B,2,2] float32, trans [B,2], flow_trans [B,2]) of the
     poses odom1 [B,3] = (x, y, phi) and the previous ones odom0, as infer_person_flow.py:114-117,145-146 forms them

@@ -16,6 +16,8 @@ flow vector and colour per detection -- still one replay per scan, nothing per p
 With ``ego_motion`` the pose is not an input any more: ``ops.ego_motion`` fits the sensor's motion to the flow of the
 points that are not people, ``ops.pose_advance`` dead-reckons the pose on the device, and the per-person launch reads
 the pose terms it wrote -- two more nodes in the same linear chain, no host copy.
+With ``tracks`` the chain ends in ``ops.track_update``: the detections of the scan are associated with
+persistent tracks on the device, so a person keeps one id from scan to scan and has a filtered velocity.
 """
 import numpy as np
 import torch
@@ -50,10 +52,15 @@ class StreamingDetector:
     (20.0) and ``cls_thresh`` (the detector's) for ``ops.ego_motion``.  The detector then takes no pose: the flow
     model's output over the points outside this scan's confident detections gives the motion since the previous scan,
     a [B,3] pose state on the device is advanced by it (``reset(pose=...)`` sets it, zeros by default), and the
-    per-person flow is in the frame of that dead-reckoned pose.  ``ego_motion()`` returns the fit and the pose."""
+    per-person flow is in the frame of that dead-reckoned pose.  ``ego_motion()`` returns the fit and the pose.
+
+    ``tracks`` (needs ``flow_model``): None, or a dict of ``max_tracks`` (64) and the settings of ``ops.track_update``
+    (``gate``, ``q``, ``r_pos``, ``r_vel``, ``v0_var``, ``max_misses``, ``min_hits``).  The step then ends in the track
+    update on the per-person result: ``tracks()`` returns the live tracks and the track id of every detection from the
+    second scan of a sequence on, and ``reset()`` forgets them (ids restart at 1)."""
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
-                 nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None):
+                 nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -86,6 +93,8 @@ class StreamingDetector:
         self._flow_model = self._ego_kw = None
         if ego_motion is not None and flow_model is None:
             raise ValueError("ego_motion needs flow_model: the motion is fitted to the flow field")
+        if tracks is not None and flow_model is None:
+            raise ValueError("tracks needs flow_model: the tracks are fed by the per-person flow")
         if flow_model is not None:
             if self._nms is None:
                 raise ValueError("flow_model needs nms_min_dist: the per-person flow is aggregated over the NMS masks")
@@ -112,6 +121,15 @@ class StreamingDetector:
                 self._ego_kw = kw
                 self._ego_out = ops.ego_motion_buffers(self.B, self.N, dev)
                 self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
+            if tracks is not None:
+                kw = dict(max_tracks=64, gate=0.5, q=1e-4, r_pos=2.5e-3, r_vel=2.5e-3, v0_var=0.25, max_misses=3,
+                          min_hits=3)
+                unknown = set(tracks) - set(kw)
+                if unknown:
+                    raise ValueError("unknown tracks settings: %s" % sorted(unknown))
+                kw.update(tracks)
+                self._track_state = ops.track_buffers(self.B, kw.pop("max_tracks"), self.N, dev)
+                self._track_kw = kw
 
     @staticmethod
     def _refuse_float16(model):
@@ -140,6 +158,11 @@ class StreamingDetector:
                 np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose,
                            dtype=np.float64).reshape(-1, 3), (self.B, 3)).copy()
             self._pose_state.copy_(torch.from_numpy(start))
+        if self._has_tracks():
+            ops.track_reset(self._track_state)
+
+    def _has_tracks(self):
+        return getattr(self, "_track_kw", None) is not None
 
     def _ensure_fused(self):
         """The model was re-fused (new checkpoint) or left eval mode since the last step: fuse again if needed
@@ -185,6 +208,10 @@ class StreamingDetector:
                                  self._pose_flow_trans)
             ops.person_flow(flow, self.tab, inst, num, xy, conf, self._pose_rot, self._pose_trans,
                             self._pose_flow_trans, self._cls_thresh, out=self._pf_out)
+            if self._has_tracks():
+                o = self._pf_out
+                ops.track_update(o.det_xy_world, o.det_flow, o.det_valid, num, inst, self._track_state,
+                                 **self._track_kw)
 
     def _pose_views(self, buf):
         nb = self.B
@@ -217,12 +244,16 @@ class StreamingDetector:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                 # warm-up off the capture: library handles, lazy inits
             pose = None if self._ego_kw is None else self._pose_state.clone()
+            tracks = [t.clone() for t in self._track_state] if self._has_tracks() else None
             for _ in range(2):
                 self._step(False)
                 if self._flow_model is not None:
                     self._flow_tail()             # reads the previous scan, writes only the output buffers
             if pose is not None:
                 self._pose_state.copy_(pose)      # ... and the pose state, which the warm-up must not advance
+            if tracks is not None:                # ... nor the tracks: ids and ages would run ahead
+                for t, saved in zip(self._track_state, tracks):
+                    t.copy_(saved)
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -304,3 +335,22 @@ class StreamingDetector:
         motion, ok, count, rms, pose = (t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, self._pose_state))
         return [{"motion": motion[b], "ok": bool(ok[b]), "count": int(count[b]), "rms": float(rms[b]), "pose": pose[b]}
                 for b in range(self.B)], o
+
+    def tracks(self):
+        """-> (list with one list per sensor of the live tracks, in slot order: dicts of id, xy [2], velocity [2] in
+        metres per scan, cov [3] = (position variance, position/velocity covariance, velocity variance), hits,
+        misses, age, confirmed and det, the row of ``person_flow()`` the track was matched with or born from in this
+        step or -1;  det_track, one array per sensor with the track id of every row of ``person_flow()``;  the
+        device-resident ``ops.TrackState``, valid until the next call).  Needs ``tracks`` and two scans of a sequence.
+        Reads the state back, i.e. synchronises."""
+        if not self._has_tracks() or not self._have_flow:
+            raise RuntimeError("construct the detector with tracks and feed it two scans of a sequence first")
+        s = self._track_state
+        h = {k: getattr(s, k).cpu().numpy() for k in s._fields}
+        counts = self._dets[2].cpu().numpy()
+        live = [[{"id": int(h["track_id"][b, t]), "xy": h["track_state"][b, t, :2].copy(),
+                  "velocity": h["track_state"][b, t, 2:].copy(), "cov": h["track_cov"][b, t].copy(),
+                  "hits": int(h["track_hits"][b, t]), "misses": int(h["track_misses"][b, t]),
+                  "age": int(h["track_age"][b, t]), "confirmed": bool(h["track_confirmed"][b, t]),
+                  "det": int(h["track_det"][b, t])} for t in np.flatnonzero(h["track_id"][b])] for b in range(self.B)]
+        return live, [h["det_track"][b, :m].copy() for b, m in enumerate(counts)], s

@@ -152,10 +152,19 @@ if "person" in which:
     ego_out = ops.ego_motion_buffers(B, N, dev)
     ego = lambda iters: ops.ego_motion(scans, tab, flow, instance_mask=inst, num_det=num, det_cls=dc, huber_delta=0.02,
                                        iters=iters, out=ego_out)
+    # N7: the track update on the per-person result of these scans.  The same detections every call: after the first
+    # one every candidate (score >= 0.5, about half the detections) is matched with its track -- the steady state
+    ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out)
+    tracks = {M: ops.track_buffers(B, M, N, dev) for M in (64, 256)}
+    track = lambda M: ops.track_update(out.det_xy_world, out.det_flow, out.det_valid, num, inst, tracks[M])
     for rep in range(3):                                   # alternating, to see the spread
         ms_nms = timeit(lambda: ops.nms_predicted_center(scans, tab, cls, reg, 0.5), iters=50)
         ms_pf = timeit(lambda: ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out), iters=50)
         ms_e0, ms_e4 = timeit(lambda: ego(0), iters=50), timeit(lambda: ego(4), iters=50)
         print("B=%d N=%d (%.0f detections per scan): centre NMS %.3f ms, person flow %.3f ms, ego_motion %.3f ms "
               "(iters=0) %.3f ms (iters=4)" % (B, N, num.float().mean().item(), ms_nms, ms_pf, ms_e0, ms_e4))
+        ms_t = {M: timeit(lambda: track(M), iters=50) for M in tracks}
+        print("   track_update (%.0f candidates per scan): %s" % (out.det_valid.sum().item() / B, ", ".join(
+            "max_tracks %d: %.3f ms, %.0f live tracks per sensor" % (M, ms_t[M], (tracks[M].track_id > 0).sum().item() / B)
+            for M in tracks)))
 

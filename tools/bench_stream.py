@@ -1,9 +1,11 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego] [--tracks]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
-step with a pose per scan against the step that dead-reckons its own pose (ego_motion=dict()), alternating repeats."""
+step with a pose per scan against the step that dead-reckons its own pose (ego_motion=dict()), alternating repeats.
+--tracks (with --flow): the replayed step without and with the person tracks (tracks=dict()) as its last node,
+alternating repeats in one process; with --ego both dead-reckon their pose."""
 import faulthandler, os, sys, time
 faulthandler.dump_traceback_later(90, exit=True)       # a stuck step reports where it is instead of hanging the box
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,7 +19,8 @@ STORAGE = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--storage=")] 
 FLOW = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--flow=")] or [None])[0]
 NMS = 0.5 if (FLOW or "--nms" in sys.argv) else None
 EGO = "--ego" in sys.argv
-sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego"))]
+TRACKS = "--tracks" in sys.argv
+sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks"))]
 
 
 class DiffFlow(torch.nn.Module):
@@ -37,11 +40,17 @@ model = SpatialDROW(num_scans=5, num_pts=56, alpha=0.5, window_size=11, pedestri
 model.fuse_for_inference(storage={"float32": torch.float32, "float16": torch.float16}[STORAGE], embed=EMBED)
 for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
     scans = torch.from_numpy(synth.make_batch(seed=9, B=B, T=40).scans).cuda()     # [B, 40, 450]
-    if EGO:
+    if EGO or TRACKS:
         poses = np.cumsum(np.random.default_rng(4).normal(0, 0.05, (40, B, 3)), axis=0)
         mk = lambda **kw: StreamingDetector(model, batch=B, nms_min_dist=NMS, flow_model=flow_model, **kw)
-        posed, ego = mk(), mk(ego_motion=dict())
-        steps = {"pose=": lambda t: posed(scans[:, t], pose=poses[t]), "ego_motion": lambda t: ego(scans[:, t])}
+        if TRACKS:
+            kw = dict(ego_motion=dict()) if EGO else {}
+            plain, tracked = mk(tracks=None, **kw), mk(tracks=dict(), **kw)
+            call = (lambda det, t: det(scans[:, t])) if EGO else (lambda det, t: det(scans[:, t], pose=poses[t]))
+            steps = {"tracks=None": lambda t: call(plain, t), "tracks": lambda t: call(tracked, t)}
+        else:
+            posed, ego = mk(), mk(ego_motion=dict())
+            steps = {"pose=": lambda t: posed(scans[:, t], pose=poses[t]), "ego_motion": lambda t: ego(scans[:, t])}
         for step in steps.values():
             for t in range(8):
                 step(t)
@@ -54,8 +63,11 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
                     step(t)
                 torch.cuda.synchronize()
                 ms[name].append((time.perf_counter() - t0) / 32 * 1e3)
-        print("streaming step B=%d [flow %s], hipGraph replay per scan, 4 alternating repeats of 32 steps: %s"
-              % (B, FLOW, ", ".join("%s %s ms" % (k, " ".join("%.3f" % v for v in vs)) for k, vs in ms.items())), flush=True)
+        if TRACKS:
+            live, _, state = tracked.tracks()
+            print("   tracks after 40 scans: %s live, next_id %s" % ([len(l) for l in live], state.next_id.tolist()))
+        print("streaming step B=%d [flow %s%s], hipGraph replay per scan, 4 alternating repeats of 32 steps: %s"
+              % (B, FLOW, ", ego" if EGO and TRACKS else "", ", ".join("%s %s ms" % (k, " ".join("%.3f" % v for v in vs)) for k, vs in ms.items())), flush=True)
         continue
     res = {}
     for graph in (False, True):
