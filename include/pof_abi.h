@@ -368,6 +368,56 @@ int pof_track_update(const double *det_xy_world, const double *det_flow, const u
                      pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N8 scan-to-scan matching: the sensor's motion between two consecutive scans without a flow field, a point-to-line
+ * ICP of the current scan against the previous one.  On a static scene it inverts
+ *   get_displacement_from_odometry(scan1_xy, odom0, odom1)   src/utils/utils.py:639-662
+ * and has the (theta, u) convention of pof_ego_motion's rigid model (sign = -1): a point now at p was at
+ * R(theta) p + u; pof_pose_advance takes the result unchanged.  The reference has no scan matcher; the specification
+ * is this comment (restated in float64 NumPy by tests/test_scan_match.py).
+ * One scan pair per batch entry, one launch.  ranges_prev, ranges_cur [B][N] float32; tab the angle table.
+ * Points: a_j = r_prev[j] * (cos, sin)[j], p_i = r_cur[i] * (cos, sin)[i] in float64, as rphi_to_xy.  A range is
+ * valid when finite and < max_range.  A current point is also left out when -- with instance_mask [B][N] -- 1 <= id <=
+ * clamp(num_det[b], 0, N) and det_cls[b][id - 1] >= cls_thresh (as pof_ego_motion: people do not vote).
+ * dphi = tab[1] - tab[0] (0 for N = 1).  Start (theta, u) = init [B][3] float64, zeros when init is NULL or a
+ * component of the row is not finite.  init may be the motion buffer (a row is read before it is written).
+ * Correspondence of p_i at (theta, u), (c, s) = (cos theta, sin theta):
+ *   shift = (int)clamp(rint(theta / dphi), -N, N)  (0 when dphi == 0; a NaN quotient gives -N)
+ *   q = ((c p_x - s p_y) + u_x, (s p_x + c p_y) + u_y)
+ *   j = the valid vertex of smallest d2 = (q_x - a_jx)^2 + (q_y - a_jy)^2 over [i + shift - window, i + shift + window]
+ *       clamped to [0, N), ties to the lower j; unmatched without one or when not d2 <= gate^2.
+ *   k in {j - 1, j + 1}: inside [0, N), valid, e = a_k - a_j with 0 < |e|^2 <= max_gap^2; of two the one with the
+ *       smaller |q - a_k|^2, j - 1 on a tie; unmatched without one.
+ *   len = sqrt(|e|^2), n = (-e_y / len, e_x / len), d = q - a_j, r = n_x d_x + n_y d_y.
+ * One iteration: w = |r| > huber_delta ? huber_delta / |r| : 1 (1 when huber_delta == 0),
+ *   J = (n_x (-q_y) + n_y q_x, n_x, n_y); over the matched points A = sum w J J^T (terms w (J_a J_b)),
+ *   g = sum w (J r), sum w, sum w (r r), and their number.  The pair fails with fewer than 3 matched points (obs = 0).
+ *   dmax = max(A00, A11, A22); Cholesky with every pivot tested as it is formed, the pair fails at the first pivot that
+ *   is not > min_pivot * dmax (a corridor: the translation along it is not observable):
+ *     p0 = A00, l00 = sqrt(p0), l10 = A01 / l00, l20 = A02 / l00
+ *     p1 = A11 - l10 l10, l11 = sqrt(p1), l21 = (A12 - l20 l10) / l11
+ *     p2 = (A22 - l20 l20) - l21 l21, l22 = sqrt(p2);   obs = min(pivots formed) / dmax (0 when dmax is not > 0)
+ *     y0 = -g0 / l00, y1 = (-g1 - l10 y0) / l11, y2 = ((-g2 - l20 y0) - l21 y1) / l22
+ *     x2 = y2 / l22, x1 = (y1 - l21 x2) / l11, x0 = ((y0 - l10 x1) - l20 x2) / l00
+ *   (c0, s0) = (cos x0, sin x0): theta += x0, u <- ((c0 u_x - s0 u_y) + x1, (s0 u_x + c0 u_y) + x2).
+ *   Stop after `iters` (1..32) iterations or when |x0| < eps_theta and max(|x1|, |x2|) < eps_u.
+ * Outputs: motion [B][3] float64 = (theta, u_x, u_y), NaN when the pair failed; count [B] int32 = points matched in
+ *   the last iteration; rms [B] = sqrt(sum w r r / sum w) of the last iteration (NaN when failed); ok [B] uint8;
+ *   iters_used [B] int32; obs [B] float64 of the last solve.  After the last iteration one more correspondence pass at
+ *   the final (theta, u) writes (each may be NULL) corr [B][N] int32 = j or -1 and flow_residual [B][N][2] float64 =
+ *   (c d_x + s d_y, -s d_x + c d_y), the nearest-vertex displacement turned back into the current scanner frame, NaN
+ *   where unmatched (all -1 / NaN for a failed pair).
+ * Sums have a fixed order (no atomics, no FMA): the same bits in every run, at every batch position, in a graph
+ * replay.  N <= 4096 (POF_E_SHAPE beyond, nothing written); one wave per pair up to N = 512.  POF_E_BADARG: window
+ * outside 1..64, iters outside 1..32, gate, max_gap or huber_delta not >= 0.
+ * ---------------------------------------------------------------------- */
+int pof_scan_match(const float *ranges_prev, const float *ranges_cur, const double *tab, const double *init,
+                   const int32_t *instance_mask, const int32_t *num_det, const double *det_cls, double cls_thresh,
+                   double max_range, int window, double gate, double max_gap, double huber_delta, int iters,
+                   double eps_theta, double eps_u, double min_pivot, int B, int N, double *motion, int32_t *count,
+                   double *rms, uint8_t *ok, int32_t *iters_used, double *obs, int32_t *corr, double *flow_residual,
+                   pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

@@ -49,6 +49,8 @@ SIGNATURES = {
     "pof_pose_advance": (_i, [_p, _p, _p, _p, _p, _p, _i, _p]),
     "pof_track_update": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d,
                               _d, _d, _i, _i, _p]),
+    "pof_scan_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _d, _d, _i, _d, _d, _d, _i, _d, _d, _d, _i, _i, _p, _p, _p, _p,
+                            _p, _p, _p, _p, _p]),
     "pof_flow_errors": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "pof_band_correlation": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pof_band_correlation_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),

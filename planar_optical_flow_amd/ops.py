@@ -1097,6 +1097,89 @@ def pose_advance(motion, ok, pose, rot=None, trans=None, flow_trans=None):
     return pose
 
 
+ScanMatch = collections.namedtuple("ScanMatch", ("motion", "count", "rms", "ok", "iters_used", "obs", "corr",
+                                                  "flow_residual"))
+_SCAN_MATCH_OUT = (("motion", torch.float64), ("count", torch.int32), ("rms", torch.float64), ("ok", torch.uint8),
+                   ("iters_used", torch.int32), ("obs", torch.float64), ("corr", torch.int32),
+                   ("flow_residual", torch.float64))
+
+
+def _scan_match_shapes(B, N):
+    return (B, 3), (B,), (B,), (B,), (B,), (B,), (B, N), (B, N, 2)
+
+
+def scan_match_buffers(B, N, device="cuda"):
+    """The eight outputs of ``scan_match`` for B scan pairs of N points, zero-filled, as its ``out=`` (allocate once,
+    before a graph capture)."""
+    return ScanMatch(*(torch.zeros(shape, dtype=dt, device=device)
+                       for (_, dt), shape in zip(_SCAN_MATCH_OUT, _scan_match_shapes(B, N))))
+
+
+def scan_match(ranges_prev, ranges_cur, tab, *, init=None, instance_mask=None, num_det=None, det_cls=None,
+               cls_thresh=0.5, max_range=20.0, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16,
+               eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, out=None):
+    """N8: the sensor's own motion between two consecutive scans without a flow field -- a point-to-line ICP of the
+    current scan against the previous one, one launch per batch (include/pof_abi.h states the algorithm).
+
+    ranges_prev, ranges_cur [B,N] f32, tab the angle table.  ``init`` [B,3] f64 = (theta, u_x, u_y) to start from
+    (None, or a row that is not finite: zeros; it may be ``out.motion`` of the previous step).  Given the NMS results
+    of the current scan -- instance_mask [B,N] i32, num_det [B] i32, det_cls [B,N] f64 -- the points of detections with
+    a score >= ``cls_thresh`` do not vote.  Ranges >= ``max_range`` or not finite are left out.  ``window`` (1..64): a
+    point looks for its vertex that many beams either side of where the rotation puts it; ``gate`` / ``max_gap``
+    (metres): the largest point-to-vertex distance and the longest line segment; ``huber_delta`` (metres, 0: plain);
+    ``iters`` (1..32) with the early exit ``eps_theta`` / ``eps_u``; ``min_pivot``: the smallest Cholesky pivot, as a
+    fraction of the largest diagonal entry, below which the pair fails (a corridor).
+    -> ``ScanMatch``: motion [B,3] f64 with q = R(theta) p + u where the point now at p was (the convention of
+    ``ego_motion``'s rigid model: ``pose_advance`` takes it), NaN when the pair failed; count [B] i32 matched points,
+    rms [B] f64, ok [B] u8, iters_used [B] i32, obs [B] f64 (smallest pivot / largest diagonal entry), corr [B,N] i32
+    (the matched vertex or -1) and flow_residual [B,N,2] f64 (the motion-compensated nearest-vertex displacement in
+    the current scanner frame, NaN where unmatched).  Fixed summation order: the same bits in every run.
+    ``out``: a ``ScanMatch`` of preallocated tensors (``scan_match_buffers``)."""
+    if not 1 <= int(window) <= 64:
+        raise ValueError("window must be in [1, 64]")
+    if not 1 <= int(iters) <= 32:
+        raise ValueError("iters must be in [1, 32]")
+    for name, v in (("gate", gate), ("max_gap", max_gap), ("huber_delta", huber_delta)):
+        if not float(v) >= 0.0:
+            raise ValueError("%s must be >= 0" % name)
+    if instance_mask is not None and (num_det is None or det_cls is None):
+        raise ValueError("instance_mask needs num_det and det_cls (the NMS results)")
+    ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
+    ranges_prev = _dev(ranges_prev, torch.float32, "ranges_prev")
+    if ranges_cur.dim() != 2 or ranges_prev.shape != ranges_cur.shape:
+        raise ValueError("ranges_prev and ranges_cur must be [B,N]")
+    B, N = ranges_cur.shape
+    dev = ranges_cur.device
+    if N < 1 or _dev(tab, torch.float64, "tab").numel() != 3 * N:
+        raise ValueError("the ranges must be [B,N] matching the angle table")
+    if init is not None and tuple(_dev(init, torch.float64, "init").shape) != (B, 3):
+        raise ValueError("init must be [B,3]")
+    if instance_mask is not None:
+        instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
+        num_det = _dev(num_det, torch.int32, "num_det")
+        det_cls = _dev(det_cls, torch.float64, "det_cls")
+        if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_cls.shape) != (B, N):
+            raise ValueError("instance_mask and det_cls must be [B,N] and num_det [B]")
+    else:
+        num_det = det_cls = None
+    if out is None:
+        out = scan_match_buffers(B, N, dev)
+    else:
+        out = ScanMatch(*out)
+        for (name, dt), shape, t in zip(_SCAN_MATCH_OUT, _scan_match_shapes(B, N), out):
+            _dev(t, dt, "out." + name)
+            if tuple(t.shape) != shape:
+                raise ValueError("out.%s has the wrong shape" % name)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_scan_match", _ptr(ranges_prev), _ptr(ranges_cur), _ptr(tab), _ptr(init), _ptr(instance_mask),
+                  _ptr(num_det), _ptr(det_cls), float(cls_thresh), float(max_range), int(window), float(gate),
+                  float(max_gap), float(huber_delta), int(iters), float(eps_theta), float(eps_u), float(min_pivot),
+                  B, N, *[_ptr(t) for t in out], _stream())
+    return out
+
+
 TrackState = collections.namedtuple("TrackState", ("track_id", "track_state", "track_cov", "track_hits", "track_misses",
                                                     "track_age", "next_id", "track_det", "track_confirmed",
                                                     "det_track", "point_track", "dropped"))

@@ -252,6 +252,34 @@ def ego_motion(scan, scan_phi, pred_flow, pred_cls=None, pred_reg=None, min_dist
             "rms": float(res.rms[0].item()), "flow_residual": host(res.flow_residual)}
 
 
+def scan_match(scan_prev, scan_cur, scan_phi, pred_cls=None, pred_reg=None, **kw):
+    """The sensor's own motion between the previous scan and this one from the two scans alone (``ops.scan_match``, a
+    point-to-line ICP; no flow net), as a displacement: a point now at p was at R(theta) p + u.  With pred_cls [N,1]
+    (sigmoid scores) and pred_reg [N,2] of the current scan the centre NMS runs first and the points of detections
+    with a score >= cls_thresh do not vote.  ``kw``: min_dist (0.5, the NMS distance) and the settings of
+    ``ops.scan_match`` (init [3], cls_thresh, max_range, window, gate, max_gap, huber_delta, iters, eps_theta, eps_u,
+    min_pivot).  -> dict: motion [3] =
+    (theta, u_x, u_y), ok (bool), count, rms, iters_used, obs, corr [N] and flow_residual [N,2]."""
+    tab = _table_for(scan_phi)
+    prev = _to_dev(scan_prev, torch.float32).reshape(1, -1)
+    cur = _to_dev(scan_cur, torch.float32).reshape(1, -1)
+    kw = dict(kw)
+    min_dist = kw.pop("min_dist", 0.5)
+    if kw.get("init") is not None:
+        kw["init"] = _to_dev(kw["init"], torch.float64).reshape(1, 3)
+    if pred_cls is not None and pred_reg is not None:
+        pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
+        assert pc.ndim == 2 and pc.shape[1] == 1
+        _, dc, num, inst = ops.nms_predicted_center(cur, tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
+                                                    _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), min_dist)
+        kw.update(instance_mask=inst, num_det=num, det_cls=dc)
+    res = ops.scan_match(prev, cur, tab, **kw)
+    host = lambda t: t[0].cpu().numpy()
+    return {"motion": host(res.motion), "ok": bool(res.ok[0].item()), "count": int(res.count[0].item()),
+            "rms": float(res.rms[0].item()), "iters_used": int(res.iters_used[0].item()),
+            "obs": float(res.obs[0].item()), "corr": host(res.corr), "flow_residual": host(res.flow_residual)}
+
+
 # ------------------------------------------------------------------ A6
 def _csr_one(dets, cls_ids):
     d = np.asarray(dets, dtype=np.float64).reshape(-1, 2)

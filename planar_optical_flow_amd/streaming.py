@@ -18,6 +18,8 @@ points that are not people, ``ops.pose_advance`` dead-reckons the pose on the de
 the pose terms it wrote -- two more nodes in the same linear chain, no host copy.
 With ``tracks`` the chain ends in ``ops.track_update``: the detections of the scan are associated with
 persistent tracks on the device, so a person keeps one id from scan to scan and has a filtered velocity.
+With ``ego_motion=dict(method="scan_match")`` the motion comes from the two scans alone (``ops.scan_match``, DESIGN 8,
+N8): no flow net is needed for a pose, and with one the matched motion stands in front of the per-person launch.
 """
 import numpy as np
 import torch
@@ -53,6 +55,11 @@ class StreamingDetector:
     model's output over the points outside this scan's confident detections gives the motion since the previous scan,
     a [B,3] pose state on the device is advanced by it (``reset(pose=...)`` sets it, zeros by default), and the
     per-person flow is in the frame of that dead-reckoned pose.  ``ego_motion()`` returns the fit and the pose.
+    With ``method="scan_match"`` (default ``"flow"``) the dict holds the settings of ``ops.scan_match`` instead
+    (``window``, ``gate``, ``max_gap``, ``huber_delta``, ``iters``, ``eps_theta``, ``eps_u``, ``min_pivot``,
+    ``max_range``, ``cls_thresh``): the motion is matched between the previous scan and this one, every step starts
+    from the previous step's motion (from rest after a failed pair), and ``flow_model`` may be None -- the detector
+    then only dead-reckons; with ``nms_min_dist`` the points of this scan's confident detections do not vote.
 
     ``tracks`` (needs ``flow_model``): None, or a dict of ``max_tracks`` (64) and the settings of ``ops.track_update``
     (``gate``, ``q``, ``r_pos``, ``r_vel``, ``v0_var``, ``max_misses``, ``min_hits``).  The step then ends in the track
@@ -90,16 +97,20 @@ class StreamingDetector:
         self.template = None            # fixed buffer once the first scan has been seen
         self._have_template = False
         self.feat_fused = self.pred_cls = self.pred_reg = None
-        self._flow_model = self._ego_kw = None
-        if ego_motion is not None and flow_model is None:
-            raise ValueError("ego_motion needs flow_model: the motion is fitted to the flow field")
+        self._flow_model = self._ego_kw = self._match_kw = None
+        method = "flow" if ego_motion is None else dict(ego_motion).get("method", "flow")
+        if method not in ("flow", "scan_match"):
+            raise ValueError("ego_motion method must be 'flow' or 'scan_match'")
+        if ego_motion is not None and method == "flow" and flow_model is None:
+            raise ValueError("ego_motion needs flow_model: the motion is fitted to the flow field "
+                             "(method='scan_match' matches the scans themselves)")
+        self._cls_thresh = float(cls_thresh)
         if tracks is not None and flow_model is None:
             raise ValueError("tracks needs flow_model: the tracks are fed by the per-person flow")
         if flow_model is not None:
             if self._nms is None:
                 raise ValueError("flow_model needs nms_min_dist: the per-person flow is aggregated over the NMS masks")
             self._flow_model = flow_model.to(dev).eval()
-            self._cls_thresh = float(cls_thresh)
             # everything the tail of the step touches is allocated here, before any capture
             self._prev_scan = torch.zeros((self.B, self.N, 1), dtype=torch.float32, device=dev)
             self._pf_out = ops.person_flow_buffers(self.B, self.N, dev)
@@ -112,12 +123,12 @@ class StreamingDetector:
             self._pose_copied = torch.cuda.Event()
             self._prev_pose = None
             self._have_prev = self._have_flow = False
-            if ego_motion is not None:
+            if ego_motion is not None and method == "flow":
                 kw = dict(huber_delta=0.02, iters=4, max_range=20.0, cls_thresh=self._cls_thresh)
-                unknown = set(ego_motion) - set(kw)
+                unknown = set(ego_motion) - set(kw) - {"method"}
                 if unknown:
                     raise ValueError("unknown ego_motion settings: %s" % sorted(unknown))
-                kw.update(ego_motion)
+                kw.update({k: v for k, v in ego_motion.items() if k != "method"})
                 self._ego_kw = kw
                 self._ego_out = ops.ego_motion_buffers(self.B, self.N, dev)
                 self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
@@ -130,6 +141,20 @@ class StreamingDetector:
                 kw.update(tracks)
                 self._track_state = ops.track_buffers(self.B, kw.pop("max_tracks"), self.N, dev)
                 self._track_kw = kw
+        if method == "scan_match":
+            kw = dict(window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16, eps_theta=1e-7, eps_u=1e-7,
+                      min_pivot=1e-6, max_range=20.0, cls_thresh=self._cls_thresh)
+            unknown = set(ego_motion) - set(kw) - {"method"}
+            if unknown:
+                raise ValueError("unknown ego_motion settings: %s" % sorted(unknown))
+            kw.update({k: v for k, v in ego_motion.items() if k != "method"})
+            self._match_kw = kw
+            # everything the matching tail touches, before any capture; the motion buffer is also the next step's init
+            if flow_model is None:
+                self._prev_scan = torch.zeros((self.B, self.N, 1), dtype=torch.float32, device=dev)
+                self._have_prev = self._have_flow = False
+            self._match_out = ops.scan_match_buffers(self.B, self.N, dev)
+            self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
 
     @staticmethod
     def _refuse_float16(model):
@@ -147,13 +172,16 @@ class StreamingDetector:
     def reset(self, pose=None):
         """Forget the template (and the previous scan).  pose ([3] or [B,3], ego-motion detectors only): the pose the
         dead reckoning starts from; zeros by default."""
-        if pose is not None and self._ego_kw is None:
+        if pose is not None and not self._dead_reckons():
             raise ValueError("reset(pose=...) is only used with ego_motion")
         self._have_template = False
         if self._flow_model is not None:
             self._prev_pose = None
+        if self._has_tail():
             self._have_prev = self._have_flow = False
-        if self._ego_kw is not None:
+        if self._match_kw is not None:
+            self._match_out.motion.zero_()            # the first pair of a sequence starts from rest
+        if self._dead_reckons():
             start = np.zeros((self.B, 3)) if pose is None else np.broadcast_to(
                 np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose,
                            dtype=np.float64).reshape(-1, 3), (self.B, 3)).copy()
@@ -163,6 +191,13 @@ class StreamingDetector:
 
     def _has_tracks(self):
         return getattr(self, "_track_kw", None) is not None
+
+    def _dead_reckons(self):
+        return self._ego_kw is not None or self._match_kw is not None
+
+    def _has_tail(self):
+        """The step has a tail that reads the previous scan: a flow model, the scan matcher, or both."""
+        return self._flow_model is not None or self._match_kw is not None
 
     def _ensure_fused(self):
         """The model was re-fused (new checkpoint) or left eval mode since the last step: fuse again if needed
@@ -196,6 +231,20 @@ class StreamingDetector:
     # stream as the step, so a capture stays one linear chain; writes only the fixed output buffers.
     def _flow_tail(self):
         with torch.no_grad():
+            if self._match_kw is not None:
+                # the motion from the two scans alone, started from the previous step's (a NaN row, a failed pair,
+                # counts as zeros in the kernel), then the pose; with the NMS the confident detections do not vote
+                gate = {}
+                if self._dets is not None:
+                    _, conf, num, inst = self._dets
+                    gate = dict(instance_mask=inst, num_det=num, det_cls=conf)
+                m = ops.scan_match(self._prev_scan.view(self.B, self.N), self._scan[:, 0], self.tab,
+                                   init=self._match_out.motion, out=self._match_out, **gate, **self._match_kw)
+                if self._flow_model is None:
+                    ops.pose_advance(m.motion, m.ok, self._pose_state)
+                    return
+                ops.pose_advance(m.motion, m.ok, self._pose_state, self._pose_rot, self._pose_trans,
+                                 self._pose_flow_trans)
             flow = self._flow_model(self._prev_scan, self._scan.view(self.B, self.N, 1))
             xy, conf, num, inst = self._dets
             flow = flow.float().contiguous()
@@ -243,14 +292,17 @@ class StreamingDetector:
         side = torch.cuda.Stream(device=self._scan.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                 # warm-up off the capture: library handles, lazy inits
-            pose = None if self._ego_kw is None else self._pose_state.clone()
+            pose = self._pose_state.clone() if self._dead_reckons() else None
+            motion = None if self._match_kw is None else self._match_out.motion.clone()
             tracks = [t.clone() for t in self._track_state] if self._has_tracks() else None
             for _ in range(2):
                 self._step(False)
-                if self._flow_model is not None:
+                if self._has_tail():
                     self._flow_tail()             # reads the previous scan, writes only the output buffers
             if pose is not None:
                 self._pose_state.copy_(pose)      # ... and the pose state, which the warm-up must not advance
+            if motion is not None:
+                self._match_out.motion.copy_(motion)      # ... nor the start of the next match move
             if tracks is not None:                # ... nor the tracks: ids and ages would run ahead
                 for t, saved in zip(self._track_state, tracks):
                     t.copy_(saved)
@@ -259,7 +311,7 @@ class StreamingDetector:
         with torch.cuda.graph(g):
             cls, reg, tmpl, fused = self._step(False)
             self.template.copy_(tmpl)                 # feed the fused template back in place
-            if self._flow_model is not None:
+            if self._has_tail():
                 self._flow_tail()
                 self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
         self._graph, self._out, self._graph_dets = g, (cls, reg, fused), self._dets
@@ -268,7 +320,7 @@ class StreamingDetector:
         scan = torch.as_tensor(scan, dtype=torch.float32)
         self._ensure_fused()
         replayed = False
-        if self._ego_kw is not None:
+        if self._dead_reckons():
             if pose is not None:
                 raise ValueError("an ego_motion detector takes no pose: it dead-reckons its own (reset(pose=...))")
         elif self._flow_model is not None:
@@ -290,11 +342,11 @@ class StreamingDetector:
             cls, reg, fused = self._out
             self._dets = self._graph_dets
             replayed = True
-        if self._flow_model is not None and not replayed:     # the captured step holds this tail itself
+        if self._has_tail() and not replayed:                 # the captured step holds this tail itself
             if self._have_prev:
                 self._flow_tail()
             self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
-        if self._flow_model is not None:
+        if self._has_tail():
             self._have_flow, self._have_prev = self._have_prev, True
         self.pred_cls, self.pred_reg, self.feat_fused = cls, reg, fused
         return cls, reg
@@ -328,9 +380,16 @@ class StreamingDetector:
         """-> list (one dict per sensor) of the last step's fit: motion [3] = (theta, u_x, u_y) since the previous
         scan, ok, count, rms, and pose [3], the dead-reckoned (x, y, phi) at this scan; and the device-resident
         outputs (``ops.EgoMotion``, valid until the next call).  Needs ``ego_motion`` and two scans of a sequence.
+        With ``method="scan_match"`` the dicts also hold iters_used and obs, and the outputs are an ``ops.ScanMatch``.
         Synchronises."""
-        if self._ego_kw is None or not self._have_flow:
+        if not self._dead_reckons() or not self._have_flow:
             raise RuntimeError("construct the detector with ego_motion and feed it two scans of a sequence first")
+        if self._match_kw is not None:
+            o = self._match_out
+            host = [t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, o.iters_used, o.obs, self._pose_state)]
+            return [{"motion": host[0][b], "ok": bool(host[1][b]), "count": int(host[2][b]), "rms": float(host[3][b]),
+                     "iters_used": int(host[4][b]), "obs": float(host[5][b]), "pose": host[6][b]}
+                    for b in range(self.B)], o
         o = self._ego_out
         motion, ok, count, rms, pose = (t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, self._pose_state))
         return [{"motion": motion[b], "ok": bool(ok[b]), "count": int(count[b]), "rms": float(rms[b]), "pose": pose[b]}

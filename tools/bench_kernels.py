@@ -152,6 +152,13 @@ if "person" in which:
     ego_out = ops.ego_motion_buffers(B, N, dev)
     ego = lambda iters: ops.ego_motion(scans, tab, flow, instance_mask=inst, num_det=num, det_cls=dc, huber_delta=0.02,
                                        iters=iters, out=ego_out)
+    # N8: the scan matcher on the same scans and NMS results; the previous scan is the same scene with range noise of
+    # its own (the sensor stands still), every pair starts from rest.  One iteration, and the default 16 with the early
+    # exit (the mean number of iterations run is printed)
+    prev = torch.from_numpy(synth.make_batch(seed=3, B=B, T=2).scans[:, 1].copy()).to(dev)
+    sm_out = ops.scan_match_buffers(B, N, dev)
+    match = lambda iters: ops.scan_match(prev, scans, tab, instance_mask=inst, num_det=num, det_cls=dc, iters=iters,
+                                         out=sm_out)
     # N7: the track update on the per-person result of these scans.  The same detections every call: after the first
     # one every candidate (score >= 0.5, about half the detections) is matched with its track -- the steady state
     ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out)
@@ -163,6 +170,10 @@ if "person" in which:
         ms_e0, ms_e4 = timeit(lambda: ego(0), iters=50), timeit(lambda: ego(4), iters=50)
         print("B=%d N=%d (%.0f detections per scan): centre NMS %.3f ms, person flow %.3f ms, ego_motion %.3f ms "
               "(iters=0) %.3f ms (iters=4)" % (B, N, num.float().mean().item(), ms_nms, ms_pf, ms_e0, ms_e4))
+        ms_m1, ms_m16 = timeit(lambda: match(1), iters=50), timeit(lambda: match(16), iters=50)
+        print("   scan_match %.3f ms (iters=1) %.3f ms (iters=16: %.1f run per pair, %.0f points matched, %d of %d pairs ok)"
+              % (ms_m1, ms_m16, sm_out.iters_used.float().mean().item(), sm_out.count.float().mean().item(),
+                 int(sm_out.ok.sum().item()), B))
         ms_t = {M: timeit(lambda: track(M), iters=50) for M in tracks}
         print("   track_update (%.0f candidates per scan): %s" % (out.det_valid.sum().item() / B, ", ".join(
             "max_tracks %d: %.3f ms, %.0f live tracks per sensor" % (M, ms_t[M], (tracks[M].track_id > 0).sum().item() / B)
