@@ -418,6 +418,58 @@ int pof_scan_match(const float *ranges_prev, const float *ranges_cur, const doub
                    pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N9 keyframe scan matching: the current scan is matched against a reference scan (the keyframe) that stays fixed
+ * until the sensor has moved away from it; the pose is key_pose o (theta, u), so no fit error accumulates while one
+ * keyframe is held.  The reference has no scan matcher; the specification is this comment together with N8's
+ * (restated in float64 NumPy by tests/test_keyframe.py).  One sensor per batch entry, one launch.
+ * State per sensor, persistent, updated in place, allocated by the caller:
+ *   key_ranges [B][N] float32 (NaN = not a vertex), key_pose [B][3] float64 = (x, y, phi) of the keyframe,
+ *   key_rel [B][3] float64 = (theta, u) of the last good match against it, key_valid [B] uint8, key_age [B] int32 =
+ *   scans since the keyframe was taken, key_misses [B] int32 = failed matches in a row, pose [B][3] float64.
+ * Convention as N8: a point now at p was at R(theta) p + u in the keyframe's scanner frame, and the composition is
+ *   pof_pose_advance's: key_pose o (theta, u) = (t_k + R(phi_k) u, phi_k + theta) with
+ *   x = x_k + (c u_x - s u_y), y = y_k + (s u_x + c u_y), (c, s) = (cos phi_k, sin phi_k).
+ * Points: vertices a_j = key_ranges[j] * (cos, sin)[j], valid when the range is finite and < max_range (a stored NaN
+ *   is not); current points p_i, their validity and the NMS gate (instance_mask, num_det, det_cls, cls_thresh) exactly
+ *   as N8.  A current point that is valid and not gated `votes`; V = their number.  The gated current scan is the row
+ *   g[i] = votes ? ranges_cur[i] : NaN -- people standing in a scan that becomes the keyframe are never vertices.
+ * Correspondence of p at (theta, u): q as N8, then
+ *   mid = (int)clamp(rint((atan2(q_y, q_x) - tab[0]) / dphi), -N, 2N)   (0 when dphi == 0; a NaN gives -N)
+ *   j = the valid vertex of smallest d2 over [mid - window, mid + window] n [0, N), scanned upwards with a strict <.
+ *   No wrap-around: a point that projects more than `window` beams outside the keyframe's field of view is unmatched.
+ *   Everything after that -- the gate, the line partner, n, d, r, w, J, the twelve sums, the Cholesky with its pivot
+ *   tests, obs, the composition and the stop rule -- is N8's, operation for operation.
+ * One step of a sensor (old = the pose on entry):
+ *   1. key_valid == 0 (seeding): key_ranges <- g, key_pose = old, key_rel = 0, key_age = 0, key_misses = 0,
+ *      key_valid = 1; ok = 0, motion and rms NaN, count = 0, iters_used = 0, obs = 0, key_replaced = 1, corr -1,
+ *      flow_residual NaN; the pose stays.
+ *   2. otherwise the match runs from key_rel (zeros when a component is not finite) and key_age counts this scan.
+ *   3. match ok: key_rel = (theta, u), pose = key_pose o key_rel, key_misses = 0.  The keyframe is replaced when
+ *      |theta| > key_rot  or  u_x u_x + u_y u_y > key_dist key_dist  or  (double)count < min_share * V:
+ *      key_ranges <- g, key_pose = pose, key_rel = 0, key_age = 0; otherwise key_age += 1.
+ *   4. match failed: the pose and key_rel stay, motion NaN.  key_misses + 1 > max_misses re-anchors: key_ranges <- g,
+ *      key_pose = old, key_rel = 0, key_age = 0, key_misses = 0; otherwise key_misses += 1 and key_age += 1.
+ * Outputs: motion [B][3] = the (theta, u) the pose was formed from (NaN without ok); count, rms, ok, iters_used, obs
+ *   as N8; key_replaced [B] uint8; optional corr [B][N] and flow_residual [B][N][2] as N8, against the keyframe that
+ *   was matched (before any replacement); optional, as pof_pose_advance writes them for pof_person_flow, rot [B][4]
+ *   float32 of the new phi, trans [B][2] = the new t, flow_trans [B][2] = t_new - t_old (zeros without ok).
+ * A workgroup reads its key_ranges row only while staging and writes it after the last correspondence pass, every
+ * thread the beams it staged: the replacement needs no second buffer.  Fixed summation order, no atomics, no FMA: the
+ * same bits in every run, at every batch position, in a graph replay.  N <= 4096 (POF_E_SHAPE beyond, nothing
+ * written); one wave per sensor up to N = 512.  POF_E_BADARG: as N8, and key_dist, key_rot or min_share not >= 0,
+ * max_misses < 0.
+ * ---------------------------------------------------------------------- */
+int pof_keyframe_match(const float *ranges_cur, const double *tab, const int32_t *instance_mask,
+                       const int32_t *num_det, const double *det_cls, double cls_thresh, double max_range, int window,
+                       double gate, double max_gap, double huber_delta, int iters, double eps_theta, double eps_u,
+                       double min_pivot, double key_dist, double key_rot, double min_share, int max_misses, int B,
+                       int N, float *key_ranges, double *key_pose, double *key_rel, uint8_t *key_valid,
+                       int32_t *key_age, int32_t *key_misses, double *pose, double *motion, int32_t *count,
+                       double *rms, uint8_t *ok, int32_t *iters_used, double *obs, uint8_t *key_replaced,
+                       int32_t *corr, double *flow_residual, float *rot, double *trans, double *flow_trans,
+                       pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

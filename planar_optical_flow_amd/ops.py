@@ -1180,6 +1180,129 @@ def scan_match(ranges_prev, ranges_cur, tab, *, init=None, instance_mask=None, n
     return out
 
 
+KeyframeState = collections.namedtuple("KeyframeState", ("key_ranges", "key_pose", "key_rel", "key_valid", "key_age",
+                                                          "key_misses", "pose"))
+KeyframeMatch = collections.namedtuple("KeyframeMatch", ("motion", "count", "rms", "ok", "iters_used", "obs",
+                                                          "key_replaced", "corr", "flow_residual"))
+_KEYFRAME_STATE = (("key_ranges", torch.float32), ("key_pose", torch.float64), ("key_rel", torch.float64),
+                   ("key_valid", torch.uint8), ("key_age", torch.int32), ("key_misses", torch.int32),
+                   ("pose", torch.float64))
+_KEYFRAME_OUT = (("motion", torch.float64), ("count", torch.int32), ("rms", torch.float64), ("ok", torch.uint8),
+                 ("iters_used", torch.int32), ("obs", torch.float64), ("key_replaced", torch.uint8),
+                 ("corr", torch.int32), ("flow_residual", torch.float64))
+
+
+def _keyframe_state_shapes(B, N):
+    return (B, N), (B, 3), (B, 3), (B,), (B,), (B,), (B, 3)
+
+
+def _keyframe_out_shapes(B, N):
+    return (B, 3), (B,), (B,), (B,), (B,), (B,), (B,), (B, N), (B, N, 2)
+
+
+def keyframe_buffers(B, N, device="cuda"):
+    """The persistent state of ``keyframe_match`` for B sensors of N points: no keyframe yet, the pose at zero
+    (allocate once, before a graph capture).  -> ``KeyframeState``."""
+    return KeyframeState(*(torch.zeros(shape, dtype=dt, device=device)
+                           for (_, dt), shape in zip(_KEYFRAME_STATE, _keyframe_state_shapes(B, N))))
+
+
+def keyframe_match_buffers(B, N, device="cuda"):
+    """The nine outputs of ``keyframe_match``, zero-filled, as its ``out=``."""
+    return KeyframeMatch(*(torch.zeros(shape, dtype=dt, device=device)
+                           for (_, dt), shape in zip(_KEYFRAME_OUT, _keyframe_out_shapes(B, N))))
+
+
+def keyframe_reset(state, pose=None):
+    """Forget the keyframe of every sensor, IN PLACE and without a synchronisation: the next ``keyframe_match`` seeds.
+    pose ([3] or [B,3]): the pose to go on from; zeros by default."""
+    state = KeyframeState(*state)
+    for name in ("key_ranges", "key_pose", "key_rel", "key_valid", "key_age", "key_misses"):
+        getattr(state, name).zero_()
+    if pose is None:
+        state.pose.zero_()
+    else:
+        pose = torch.as_tensor(pose, dtype=torch.float64).reshape(-1, 3)
+        state.pose.copy_(pose.expand(state.pose.shape[0], 3), non_blocking=True)
+    return state
+
+
+def keyframe_match(ranges_cur, tab, state, *, instance_mask=None, num_det=None, det_cls=None, cls_thresh=0.5,
+                   max_range=20.0, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16, eps_theta=1e-7,
+                   eps_u=1e-7, min_pivot=1e-6, key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2, out=None,
+                   rot=None, trans=None, flow_trans=None):
+    """N9: one step of keyframe scan matching -- the current scan is matched against the sensor's keyframe (a
+    point-to-line ICP as ``scan_match``, the window of a point centred on the beam it projects to), the pose becomes
+    key_pose o (theta, u), and the keyframe is replaced on the device when the sensor has left it; one launch per
+    batch (include/pof_abi.h states the algorithm).
+
+    ranges_cur [B,N] f32, tab the angle table, ``state`` a ``KeyframeState`` (``keyframe_buffers``), UPDATED IN PLACE:
+    a sensor without a keyframe (``key_valid`` 0) takes this scan as its keyframe and reports ok = 0.  The NMS results
+    gate people as in ``scan_match``, also out of a scan that becomes the keyframe.  The settings up to ``min_pivot``
+    are ``scan_match``'s.  The keyframe is replaced by the current scan when the match has |theta| > ``key_rot``
+    (radians), |u| > ``key_dist`` (metres) or fewer matched points than ``min_share`` of the points that vote, and
+    after more than ``max_misses`` failed matches in a row (at the unchanged pose).
+    -> ``KeyframeMatch``: motion [B,3] f64 = (theta, u) against the keyframe that was matched (NaN without ok), count,
+    rms, ok, iters_used, obs as ``scan_match``, key_replaced [B] u8, corr [B,N] i32 and flow_residual [B,N,2] f64.
+    ``out``: a ``KeyframeMatch`` of preallocated tensors (``keyframe_match_buffers``).  ``rot`` [B,2,2] (or [B,4]) f32,
+    ``trans`` [B,2] f64, ``flow_trans`` [B,2] f64: the pose terms ``person_flow`` reads, as ``pose_advance`` writes
+    them."""
+    if not 1 <= int(window) <= 64:
+        raise ValueError("window must be in [1, 64]")
+    if not 1 <= int(iters) <= 32:
+        raise ValueError("iters must be in [1, 32]")
+    for name, v in (("gate", gate), ("max_gap", max_gap), ("huber_delta", huber_delta), ("key_dist", key_dist),
+                    ("key_rot", key_rot), ("min_share", min_share)):
+        if not float(v) >= 0.0:
+            raise ValueError("%s must be >= 0" % name)
+    if int(max_misses) < 0:
+        raise ValueError("max_misses must be >= 0")
+    if instance_mask is not None and (num_det is None or det_cls is None):
+        raise ValueError("instance_mask needs num_det and det_cls (the NMS results)")
+    ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
+    if ranges_cur.dim() != 2:
+        raise ValueError("ranges_cur must be [B,N]")
+    B, N = ranges_cur.shape
+    dev = ranges_cur.device
+    if N < 1 or _dev(tab, torch.float64, "tab").numel() != 3 * N:
+        raise ValueError("the ranges must be [B,N] matching the angle table")
+    state = KeyframeState(*state)
+    for (name, dt), shape, t in zip(_KEYFRAME_STATE, _keyframe_state_shapes(B, N), state):
+        _dev(t, dt, "state." + name)
+        if tuple(t.shape) != shape:
+            raise ValueError("state.%s has the wrong shape" % name)
+    if instance_mask is not None:
+        instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
+        num_det = _dev(num_det, torch.int32, "num_det")
+        det_cls = _dev(det_cls, torch.float64, "det_cls")
+        if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_cls.shape) != (B, N):
+            raise ValueError("instance_mask and det_cls must be [B,N] and num_det [B]")
+    else:
+        num_det = det_cls = None
+    if out is None:
+        out = keyframe_match_buffers(B, N, dev)
+    else:
+        out = KeyframeMatch(*out)
+        for (name, dt), shape, t in zip(_KEYFRAME_OUT, _keyframe_out_shapes(B, N), out):
+            _dev(t, dt, "out." + name)
+            if tuple(t.shape) != shape:
+                raise ValueError("out.%s has the wrong shape" % name)
+    if rot is not None and tuple(_dev(rot, torch.float32, "rot").shape) not in ((B, 2, 2), (B, 4)):
+        raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
+    for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
+        if t is not None and tuple(_dev(t, torch.float64, name).shape) != (B, 2):
+            raise ValueError("%s must be [B,2]" % name)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_keyframe_match", _ptr(ranges_cur), _ptr(tab), _ptr(instance_mask), _ptr(num_det), _ptr(det_cls),
+                  float(cls_thresh), float(max_range), int(window), float(gate), float(max_gap), float(huber_delta),
+                  int(iters), float(eps_theta), float(eps_u), float(min_pivot), float(key_dist), float(key_rot),
+                  float(min_share), int(max_misses), B, N, *[_ptr(t) for t in state], *[_ptr(t) for t in out],
+                  _ptr(rot), _ptr(trans), _ptr(flow_trans), _stream())
+    return out
+
+
 TrackState = collections.namedtuple("TrackState", ("track_id", "track_state", "track_cov", "track_hits", "track_misses",
                                                     "track_age", "next_id", "track_det", "track_confirmed",
                                                     "det_track", "point_track", "dropped"))

@@ -461,6 +461,55 @@ class PersonTracker:
         return h["det_track"][:m], tracks
 
 
+class KeyframeOdometry:
+    """The sensor's pose from its scans alone, scan after scan, without the drift of composing one scan-to-scan fit
+    per scan (``ops.keyframe_match``, one launch per scan; the reference has no scan matcher): every scan is matched
+    against a keyframe that stays fixed until the sensor has moved away from it.  ``odo = KeyframeOdometry(scan_phi,
+    key_dist=0.3, ...)`` with the settings of ``ops.keyframe_match`` and min_dist (0.5, the NMS distance);
+    ``res = odo.update(scan, pred_cls, pred_reg)`` per scan, ``odo.reset(pose)`` between sequences.
+
+    ``update``: NumPy in and NumPy out.  With pred_cls [N,1] (sigmoid scores) and pred_reg [N,2] the centre NMS runs
+    first: the points of detections with a score >= cls_thresh do not vote and never become vertices of a keyframe.
+    -> dict: pose [3] = (x, y, phi), motion [3] = (theta, u_x, u_y) against the keyframe, ok (bool; False on the first
+    scan, which only becomes the keyframe), count, rms, iters_used, obs, key_replaced (bool), key_age, key_misses,
+    key_pose [3], corr [N] and flow_residual [N,2]."""
+
+    def __init__(self, scan_phi, **kw):
+        self._tab = _table_for(scan_phi)
+        self._n = self._tab.numel() // 3
+        self._min_dist = kw.pop("min_dist", 0.5)
+        known = {"cls_thresh", "max_range", "window", "gate", "max_gap", "huber_delta", "iters", "eps_theta", "eps_u",
+                 "min_pivot", "key_dist", "key_rot", "min_share", "max_misses"}
+        unknown = set(kw) - known
+        if unknown:
+            raise ValueError("unknown keyframe settings: %s" % sorted(unknown))
+        self._kw = kw
+        self._state = ops.keyframe_buffers(1, self._n, self._tab.device)
+
+    def reset(self, pose=None):
+        ops.keyframe_reset(self._state, pose)
+
+    def update(self, scan, pred_cls=None, pred_reg=None):
+        cur = _to_dev(scan, torch.float32).reshape(1, -1)
+        gate = {}
+        if pred_cls is not None and pred_reg is not None:
+            pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
+            assert pc.ndim == 2 and pc.shape[1] == 1
+            _, dc, num, inst = ops.nms_predicted_center(cur, self._tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
+                                                        _to_dev(pred_reg, torch.float64).reshape(1, -1, 2),
+                                                        self._min_dist)
+            gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
+        res = ops.keyframe_match(cur, self._tab, self._state, **gate, **self._kw)
+        host = lambda t: t[0].cpu().numpy()
+        s = self._state
+        return {"pose": host(s.pose), "motion": host(res.motion), "ok": bool(res.ok[0].item()),
+                "count": int(res.count[0].item()), "rms": float(res.rms[0].item()),
+                "iters_used": int(res.iters_used[0].item()), "obs": float(res.obs[0].item()),
+                "key_replaced": bool(res.key_replaced[0].item()), "key_age": int(s.key_age[0].item()),
+                "key_misses": int(s.key_misses[0].item()), "key_pose": host(s.key_pose), "corr": host(res.corr),
+                "flow_residual": host(res.flow_residual)}
+
+
 def _pose_terms(odom1, odom0=None, batch=1):
     """Host side of ``person_flow`` for B sensors at once: (rot [B,2,2] float32, trans [B,2], flow_trans [B,2]) of the
     poses odom1 [B,3] = (x, y, phi) and the previous ones odom0, as infer_person_flow.py:114-117,145-146 forms them

@@ -20,6 +20,9 @@ With ``tracks`` the chain ends in ``ops.track_update``: the detec
 persistent tracks on the device, so a person keeps one id from scan to scan and has a filtered velocity.
 With ``ego_motion=dict(method="scan_match")`` the motion comes from the two scans alone (``ops.scan_match``, DESIGN 8,
 N8): no flow net is needed for a pose, and with one the matched motion stands in front of the per-person launch.
+With ``ego_motion=dict(method="keyframe")`` every scan is matched against a keyframe that stays fixed until the sensor
+has left it (``ops.keyframe_match``): one launch that keeps the keyframe, its bookkeeping and the pose on
+the device, so the pose of a sensor that stands still or works in one place does not walk away.
 """
 import numpy as np
 import torch
@@ -60,6 +63,11 @@ class StreamingDetector:
     ``max_range``, ``cls_thresh``): the motion is matched between the previous scan and this one, every step starts
     from the previous step's motion (from rest after a failed pair), and ``flow_model`` may be None -- the detector
     then only dead-reckons; with ``nms_min_dist`` the points of this scan's confident detections do not vote.
+    With ``method="keyframe"`` the dict holds those settings and ``key_dist`` (0.3), ``key_rot`` (0.3), ``min_share``
+    (0.5) and ``max_misses`` (2) of ``ops.keyframe_match``: the scan is matched against the sensor's keyframe, the pose
+    is the keyframe's composed with that one match, and the launch replaces the keyframe on the device.  It runs from
+    the first scan of a sequence on (which becomes the keyframe; ``ego_motion()`` reports ok = False there), and
+    ``flow_model`` may be None.
 
     ``tracks`` (needs ``flow_model``): None, or a dict of ``max_tracks`` (64) and the settings of ``ops.track_update``
     (``gate``, ``q``, ``r_pos``, ``r_vel``, ``v0_var``, ``max_misses``, ``min_hits``).  The step then ends in the track
@@ -97,13 +105,13 @@ class StreamingDetector:
         self.template = None            # fixed buffer once the first scan has been seen
         self._have_template = False
         self.feat_fused = self.pred_cls = self.pred_reg = None
-        self._flow_model = self._ego_kw = self._match_kw = None
+        self._flow_model = self._ego_kw = self._match_kw = self._key_kw = None
         method = "flow" if ego_motion is None else dict(ego_motion).get("method", "flow")
-        if method not in ("flow", "scan_match"):
-            raise ValueError("ego_motion method must be 'flow' or 'scan_match'")
+        if method not in ("flow", "scan_match", "keyframe"):
+            raise ValueError("ego_motion method must be 'flow', 'scan_match' or 'keyframe'")
         if ego_motion is not None and method == "flow" and flow_model is None:
             raise ValueError("ego_motion needs flow_model: the motion is fitted to the flow field "
-                             "(method='scan_match' matches the scans themselves)")
+                             "(method='scan_match' and method='keyframe' match the scans themselves)")
         self._cls_thresh = float(cls_thresh)
         if tracks is not None and flow_model is None:
             raise ValueError("tracks needs flow_model: the tracks are fed by the per-person flow")
@@ -155,6 +163,20 @@ class StreamingDetector:
                 self._have_prev = self._have_flow = False
             self._match_out = ops.scan_match_buffers(self.B, self.N, dev)
             self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
+        if method == "keyframe":
+            kw = dict(window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16, eps_theta=1e-7, eps_u=1e-7,
+                      min_pivot=1e-6, max_range=20.0, cls_thresh=self._cls_thresh, key_dist=0.3, key_rot=0.3,
+                      min_share=0.5, max_misses=2)
+            unknown = set(ego_motion) - set(kw) - {"method"}
+            if unknown:
+                raise ValueError("unknown ego_motion settings: %s" % sorted(unknown))
+            kw.update({k: v for k, v in ego_motion.items() if k != "method"})
+            self._key_kw = kw
+            # the keyframe, its bookkeeping and the pose live on the device, allocated before any capture
+            self._key_state = ops.keyframe_buffers(self.B, self.N, dev)
+            self._key_out = ops.keyframe_match_buffers(self.B, self.N, dev)
+            self._pose_state = self._key_state.pose
+            self._key_seen = False
 
     @staticmethod
     def _refuse_float16(model):
@@ -181,6 +203,9 @@ class StreamingDetector:
             self._have_prev = self._have_flow = False
         if self._match_kw is not None:
             self._match_out.motion.zero_()            # the first pair of a sequence starts from rest
+        if self._key_kw is not None:
+            ops.keyframe_reset(self._key_state)       # the next scan becomes the keyframe
+            self._key_seen = False
         if self._dead_reckons():
             start = np.zeros((self.B, 3)) if pose is None else np.broadcast_to(
                 np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose,
@@ -193,7 +218,7 @@ class StreamingDetector:
         return getattr(self, "_track_kw", None) is not None
 
     def _dead_reckons(self):
-        return self._ego_kw is not None or self._match_kw is not None
+        return self._ego_kw is not None or self._match_kw is not None or self._key_kw is not None
 
     def _has_tail(self):
         """The step has a tail that reads the previous scan: a flow model, the scan matcher, or both."""
@@ -262,6 +287,19 @@ class StreamingDetector:
                 ops.track_update(o.det_xy_world, o.det_flow, o.det_valid, num, inst, self._track_state,
                                  **self._track_kw)
 
+    # the keyframe launch: runs on every scan, the first of a sequence included (it seeds there); with a flow model it
+    # stands in front of the tail and writes the pose terms the per-person launch reads
+    def _key_step(self):
+        gate = {}
+        if self._dets is not None:
+            _, conf, num, inst = self._dets
+            gate = dict(instance_mask=inst, num_det=num, det_cls=conf)
+        terms = {}
+        if self._flow_model is not None:
+            terms = dict(rot=self._pose_rot, trans=self._pose_trans, flow_trans=self._pose_flow_trans)
+        ops.keyframe_match(self._scan[:, 0], self.tab, self._key_state, out=self._key_out, **gate, **terms,
+                           **self._key_kw)
+
     def _pose_views(self, buf):
         nb = self.B
         return (buf[:16 * nb].view(torch.float64).view(nb, 2), buf[16 * nb:32 * nb].view(torch.float64).view(nb, 2),
@@ -295,8 +333,11 @@ class StreamingDetector:
             pose = self._pose_state.clone() if self._dead_reckons() else None
             motion = None if self._match_kw is None else self._match_out.motion.clone()
             tracks = [t.clone() for t in self._track_state] if self._has_tracks() else None
+            key = None if self._key_kw is None else [t.clone() for t in self._key_state]
             for _ in range(2):
                 self._step(False)
+                if key is not None:
+                    self._key_step()
                 if self._has_tail():
                     self._flow_tail()             # reads the previous scan, writes only the output buffers
             if pose is not None:
@@ -306,11 +347,16 @@ class StreamingDetector:
             if tracks is not None:                # ... nor the tracks: ids and ages would run ahead
                 for t, saved in zip(self._track_state, tracks):
                     t.copy_(saved)
+            if key is not None:                   # ... nor the keyframe, its age and the pose
+                for t, saved in zip(self._key_state, key):
+                    t.copy_(saved)
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             cls, reg, tmpl, fused = self._step(False)
             self.template.copy_(tmpl)                 # feed the fused template back in place
+            if self._key_kw is not None:
+                self._key_step()
             if self._has_tail():
                 self._flow_tail()
                 self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
@@ -342,6 +388,10 @@ class StreamingDetector:
             cls, reg, fused = self._out
             self._dets = self._graph_dets
             replayed = True
+        if self._key_kw is not None:
+            if not replayed:
+                self._key_step()
+            self._key_seen = True
         if self._has_tail() and not replayed:                 # the captured step holds this tail itself
             if self._have_prev:
                 self._flow_tail()
@@ -381,7 +431,19 @@ class StreamingDetector:
         scan, ok, count, rms, and pose [3], the dead-reckoned (x, y, phi) at this scan; and the device-resident
         outputs (``ops.EgoMotion``, valid until the next call).  Needs ``ego_motion`` and two scans of a sequence.
         With ``method="scan_match"`` the dicts also hold iters_used and obs, and the outputs are an ``ops.ScanMatch``.
+        With ``method="keyframe"`` the motion is the one against the keyframe, the dicts also hold key_replaced,
+        key_age and key_pose [3], the outputs are an ``ops.KeyframeMatch``, and one scan is enough (ok is False there).
         Synchronises."""
+        if self._key_kw is not None:
+            if not self._key_seen:
+                raise RuntimeError("feed the detector a scan first")
+            o, s = self._key_out, self._key_state
+            host = [t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, o.iters_used, o.obs, s.pose,
+                                              o.key_replaced, s.key_age, s.key_pose)]
+            return [{"motion": host[0][b], "ok": bool(host[1][b]), "count": int(host[2][b]), "rms": float(host[3][b]),
+                     "iters_used": int(host[4][b]), "obs": float(host[5][b]), "pose": host[6][b],
+                     "key_replaced": bool(host[7][b]), "key_age": int(host[8][b]), "key_pose": host[9][b]}
+                    for b in range(self.B)], o
         if not self._dead_reckons() or not self._have_flow:
             raise RuntimeError("construct the detector with ego_motion and feed it two scans of a sequence first")
         if self._match_kw is not None:

@@ -159,6 +159,15 @@ if "person" in which:
     sm_out = ops.scan_match_buffers(B, N, dev)
     match = lambda iters: ops.scan_match(prev, scans, tab, instance_mask=inst, num_det=num, det_cls=dc, iters=iters,
                                          out=sm_out)
+    # N9: the keyframe matcher on the same inputs: `prev` seeds the keyframe of every sensor, then every timed call
+    # matches `scans` against it from rest (key_rel is zeroed in front of the launch: one memset node, timed on its own
+    # too); the sensor stands still, so no keyframe is replaced and the state stays what it was
+    kf_state, kf_out = ops.keyframe_buffers(B, N, dev), ops.keyframe_match_buffers(B, N, dev)
+    ops.keyframe_match(prev, tab, kf_state)
+
+    def keyframe(iters):
+        kf_state.key_rel.zero_()
+        ops.keyframe_match(scans, tab, kf_state, instance_mask=inst, num_det=num, det_cls=dc, iters=iters, out=kf_out)
     # N7: the track update on the per-person result of these scans.  The same detections every call: after the first
     # one every candidate (score >= 0.5, about half the detections) is matched with its track -- the steady state
     ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out)
@@ -174,6 +183,12 @@ if "person" in which:
         print("   scan_match %.3f ms (iters=1) %.3f ms (iters=16: %.1f run per pair, %.0f points matched, %d of %d pairs ok)"
               % (ms_m1, ms_m16, sm_out.iters_used.float().mean().item(), sm_out.count.float().mean().item(),
                  int(sm_out.ok.sum().item()), B))
+        ms_k1, ms_k16 = timeit(lambda: keyframe(1), iters=50), timeit(lambda: keyframe(16), iters=50)
+        ms_z = timeit(lambda: kf_state.key_rel.zero_(), iters=50)
+        print("   keyframe_match %.3f ms (iters=1) %.3f ms (iters=16: %.1f run per sensor, %.0f points matched, %d of %d "
+              "ok, %d keyframes replaced), both with the %.3f ms memset of key_rel in front"
+              % (ms_k1, ms_k16, kf_out.iters_used.float().mean().item(), kf_out.count.float().mean().item(),
+                 int(kf_out.ok.sum().item()), B, int(kf_out.key_replaced.sum().item()), ms_z))
         ms_t = {M: timeit(lambda: track(M), iters=50) for M in tracks}
         print("   track_update (%.0f candidates per scan): %s" % (out.det_valid.sum().item() / B, ", ".join(
             "max_tracks %d: %.3f ms, %.0f live tracks per sensor" % (M, ms_t[M], (tracks[M].track_id > 0).sum().item() / B)
