@@ -54,32 +54,6 @@ struct EgoMotionArgs {
     float *weight_out;
 };
 
-// Sum of K values over the workgroup, the same bits in every thread.  `part` is [K][8] doubles of LDS (unused by the
-// one-wave form).
-template <int THREADS, int K>
-__device__ __forceinline__ void group_sum(double (&v)[K], double *part)
-{
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum_f64(v[k]);
-    if (THREADS > 64) {
-        constexpr int kWaves = THREADS / 64;
-        const int wave = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) part[k * kWaves + wave] = v[k];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double s = part[k * kWaves];
-#pragma unroll
-            for (int j = 1; j < kWaves; ++j) s += part[k * kWaves + j];
-            v[k] = s;
-        }
-        __syncthreads();                                       // the next sum overwrites the partials
-    }
-}
-
 struct Solution {
     double a, b0, b1;      // (theta, u) or (omega, t)
     double c, s;           // cos / sin of theta (rigid)

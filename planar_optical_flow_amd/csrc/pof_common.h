@@ -74,6 +74,33 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     return v;
 }
 
+// Sum of K values over a workgroup of THREADS (64: one wave), the same bits in every thread: a butterfly stage adds
+// the same two numbers in both lanes, and the wave totals go through LDS and every thread adds them in wave order.
+// `part` is [K][THREADS / 64] doubles of LDS (unused by the one-wave form).
+template <int THREADS, int K>
+__device__ __forceinline__ void group_sum(double (&v)[K], double *part)
+{
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_sum_f64(v[k]);
+    if (THREADS > 64) {
+        constexpr int kWaves = THREADS / 64;
+        const int wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) part[k * kWaves + wave] = v[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            double s = part[k * kWaves];
+#pragma unroll
+            for (int j = 1; j < kWaves; ++j) s += part[k * kWaves + j];
+            v[k] = s;
+        }
+        __syncthreads();                                       // the next sum overwrites the partials
+    }
+}
+
 __device__ __forceinline__ float wave_sum_f32(float v)
 {
 #pragma unroll

@@ -985,6 +985,42 @@ def person_flow(flow_canonical, tab, instance_mask, num_det, det_xy, det_cls, ro
     return out
 
 
+def _nms_gate(instance_mask, num_det, det_cls, B=None, N=None):
+    """The NMS results that gate people out of a fit.  Without B and N (before any tensor is looked at): only that
+    instance_mask comes with the other two.  With them -> the three tensors, checked, or three Nones."""
+    if instance_mask is None:
+        return None, None, None
+    if num_det is None or det_cls is None:
+        raise ValueError("instance_mask needs num_det and det_cls (the NMS results)")
+    if B is None:
+        return instance_mask, num_det, det_cls
+    instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
+    num_det = _dev(num_det, torch.int32, "num_det")
+    det_cls = _dev(det_cls, torch.float64, "det_cls")
+    if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_cls.shape) != (B, N):
+        raise ValueError("instance_mask and det_cls must be [B,N] and num_det [B]")
+    return instance_mask, num_det, det_cls
+
+
+def _check_fields(tensors, fields, shapes, prefix):
+    """The tensors of a namedtuple against its fields (name, dtype, ...) and shapes; an error names ``prefix.name``."""
+    for (name, dt, *_), shape, t in zip(fields, shapes, tensors):
+        _dev(t, dt, prefix + "." + name)
+        if tuple(t.shape) != shape:
+            raise ValueError("%s.%s has the wrong shape" % (prefix, name))
+
+
+def _check_matcher_settings(window, iters, **not_negative):
+    """The settings ``scan_match`` and ``keyframe_match`` share; the keywords, in their order, must be >= 0."""
+    if not 1 <= int(window) <= 64:
+        raise ValueError("window must be in [1, 64]")
+    if not 1 <= int(iters) <= 32:
+        raise ValueError("iters must be in [1, 32]")
+    for name, v in not_negative.items():
+        if not float(v) >= 0.0:
+            raise ValueError("%s must be >= 0" % name)
+
+
 EgoMotion = collections.namedtuple("EgoMotion", ("motion", "count", "rms", "ok", "flow_residual", "weight"))
 _EGO_MOTION_OUT = (("motion", torch.float64), ("count", torch.int32), ("rms", torch.float64), ("ok", torch.uint8),
                    ("flow_residual", torch.float64), ("weight", torch.float32))
@@ -1027,8 +1063,7 @@ def ego_motion(ranges, tab, flow, *, xy=None, canonical=True, sign=-1, model="ri
         raise ValueError("model must be 'rigid' or 'linear'")
     if not 0 <= int(iters) <= 16:
         raise ValueError("iters must be in [0, 16]")
-    if instance_mask is not None and (num_det is None or det_cls is None):
-        raise ValueError("instance_mask needs num_det and det_cls (the NMS results)")
+    _nms_gate(instance_mask, num_det, det_cls)
     if not isinstance(flow, torch.Tensor) or flow.dtype not in (torch.float32, torch.float64):
         raise TypeError("flow must be a float32 or float64 tensor on the HIP device (no CPU path)")
     flow = _dev(flow, flow.dtype, "flow")
@@ -1047,22 +1082,12 @@ def ego_motion(ranges, tab, flow, *, xy=None, canonical=True, sign=-1, model="ri
         raise ValueError("flow must be [B,N,2] matching the angle table")
     if weight is not None and tuple(_dev(weight, torch.float32, "weight").shape) != (B, N):
         raise ValueError("weight must be [B,N]")
-    if instance_mask is not None:
-        instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
-        num_det = _dev(num_det, torch.int32, "num_det")
-        det_cls = _dev(det_cls, torch.float64, "det_cls")
-        if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_cls.shape) != (B, N):
-            raise ValueError("instance_mask and det_cls must be [B,N] and num_det [B]")
-    else:
-        num_det = det_cls = None
+    instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
     if out is None:
         out = ego_motion_buffers(B, N, dev)
     else:
         out = EgoMotion(*out)
-        for (name, dt), shape, t in zip(_EGO_MOTION_OUT, _ego_motion_shapes(B, N), out):
-            _dev(t, dt, "out." + name)
-            if tuple(t.shape) != shape:
-                raise ValueError("out.%s has the wrong shape" % name)
+        _check_fields(out, _EGO_MOTION_OUT, _ego_motion_shapes(B, N), "out")
     if B == 0:
         return out
     with torch.cuda.device(dev):
@@ -1135,15 +1160,8 @@ def scan_match(ranges_prev, ranges_cur, tab, *, init=None, instance_mask=None, n
     (the matched vertex or -1) and flow_residual [B,N,2] f64 (the motion-compensated nearest-vertex displacement in
     the current scanner frame, NaN where unmatched).  Fixed summation order: the same bits in every run.
     ``out``: a ``ScanMatch`` of preallocated tensors (``scan_match_buffers``)."""
-    if not 1 <= int(window) <= 64:
-        raise ValueError("window must be in [1, 64]")
-    if not 1 <= int(iters) <= 32:
-        raise ValueError("iters must be in [1, 32]")
-    for name, v in (("gate", gate), ("max_gap", max_gap), ("huber_delta", huber_delta)):
-        if not float(v) >= 0.0:
-            raise ValueError("%s must be >= 0" % name)
-    if instance_mask is not None and (num_det is None or det_cls is None):
-        raise ValueError("instance_mask needs num_det and det_cls (the NMS results)")
+    _check_matcher_settings(window, iters, gate=gate, max_gap=max_gap, huber_delta=huber_delta)
+    _nms_gate(instance_mask, num_det, det_cls)
     ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
     ranges_prev = _dev(ranges_prev, torch.float32, "ranges_prev")
     if ranges_cur.dim() != 2 or ranges_prev.shape != ranges_cur.shape:
@@ -1154,22 +1172,12 @@ def scan_match(ranges_prev, ranges_cur, tab, *, init=None, instance_mask=None, n
         raise ValueError("the ranges must be [B,N] matching the angle table")
     if init is not None and tuple(_dev(init, torch.float64, "init").shape) != (B, 3):
         raise ValueError("init must be [B,3]")
-    if instance_mask is not None:
-        instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
-        num_det = _dev(num_det, torch.int32, "num_det")
-        det_cls = _dev(det_cls, torch.float64, "det_cls")
-        if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_cls.shape) != (B, N):
-            raise ValueError("instance_mask and det_cls must be [B,N] and num_det [B]")
-    else:
-        num_det = det_cls = None
+    instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
     if out is None:
         out = scan_match_buffers(B, N, dev)
     else:
         out = ScanMatch(*out)
-        for (name, dt), shape, t in zip(_SCAN_MATCH_OUT, _scan_match_shapes(B, N), out):
-            _dev(t, dt, "out." + name)
-            if tuple(t.shape) != shape:
-                raise ValueError("out.%s has the wrong shape" % name)
+        _check_fields(out, _SCAN_MATCH_OUT, _scan_match_shapes(B, N), "out")
     if B == 0:
         return out
     with torch.cuda.device(dev):
@@ -1247,18 +1255,11 @@ def keyframe_match(ranges_cur, tab, state, *, instance_mask=None, num_det=None, 
     ``out``: a ``KeyframeMatch`` of preallocated tensors (``keyframe_match_buffers``).  ``rot`` [B,2,2] (or [B,4]) f32,
     ``trans`` [B,2] f64, ``flow_trans`` [B,2] f64: the pose terms ``person_flow`` reads, as ``pose_advance`` writes
     them."""
-    if not 1 <= int(window) <= 64:
-        raise ValueError("window must be in [1, 64]")
-    if not 1 <= int(iters) <= 32:
-        raise ValueError("iters must be in [1, 32]")
-    for name, v in (("gate", gate), ("max_gap", max_gap), ("huber_delta", huber_delta), ("key_dist", key_dist),
-                    ("key_rot", key_rot), ("min_share", min_share)):
-        if not float(v) >= 0.0:
-            raise ValueError("%s must be >= 0" % name)
+    _check_matcher_settings(window, iters, gate=gate, max_gap=max_gap, huber_delta=huber_delta, key_dist=key_dist,
+                            key_rot=key_rot, min_share=min_share)
     if int(max_misses) < 0:
         raise ValueError("max_misses must be >= 0")
-    if instance_mask is not None and (num_det is None or det_cls is None):
-        raise ValueError("instance_mask needs num_det and det_cls (the NMS results)")
+    _nms_gate(instance_mask, num_det, det_cls)
     ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
     if ranges_cur.dim() != 2:
         raise ValueError("ranges_cur must be [B,N]")
@@ -1267,26 +1268,13 @@ def keyframe_match(ranges_cur, tab, state, *, instance_mask=None, num_det=None, 
     if N < 1 or _dev(tab, torch.float64, "tab").numel() != 3 * N:
         raise ValueError("the ranges must be [B,N] matching the angle table")
     state = KeyframeState(*state)
-    for (name, dt), shape, t in zip(_KEYFRAME_STATE, _keyframe_state_shapes(B, N), state):
-        _dev(t, dt, "state." + name)
-        if tuple(t.shape) != shape:
-            raise ValueError("state.%s has the wrong shape" % name)
-    if instance_mask is not None:
-        instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
-        num_det = _dev(num_det, torch.int32, "num_det")
-        det_cls = _dev(det_cls, torch.float64, "det_cls")
-        if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_cls.shape) != (B, N):
-            raise ValueError("instance_mask and det_cls must be [B,N] and num_det [B]")
-    else:
-        num_det = det_cls = None
+    _check_fields(state, _KEYFRAME_STATE, _keyframe_state_shapes(B, N), "state")
+    instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
     if out is None:
         out = keyframe_match_buffers(B, N, dev)
     else:
         out = KeyframeMatch(*out)
-        for (name, dt), shape, t in zip(_KEYFRAME_OUT, _keyframe_out_shapes(B, N), out):
-            _dev(t, dt, "out." + name)
-            if tuple(t.shape) != shape:
-                raise ValueError("out.%s has the wrong shape" % name)
+        _check_fields(out, _KEYFRAME_OUT, _keyframe_out_shapes(B, N), "out")
     if rot is not None and tuple(_dev(rot, torch.float32, "rot").shape) not in ((B, 2, 2), (B, 4)):
         raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
     for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
@@ -1366,10 +1354,7 @@ def track_update(det_xy_world, det_flow, det_valid, num_det, instance_mask, stat
     if state.track_id.dim() != 2:
         raise ValueError("state.track_id must be [B,max_tracks]")
     M = state.track_id.shape[1]
-    for (name, dt, per, w), t in zip(_TRACK_FIELDS, state):
-        _dev(t, dt, "state." + name)
-        if tuple(t.shape) != _track_shape(per, w, B, M, N):
-            raise ValueError("state.%s has the wrong shape" % name)
+    _check_fields(state, _TRACK_FIELDS, [_track_shape(per, w, B, M, N) for _, _, per, w in _TRACK_FIELDS], "state")
     if B == 0:
         return state
     with torch.cuda.device(det_xy_world.device):

@@ -33,6 +33,14 @@ _DEFAULT_CUTOUT = dict(fixed=True, centered=True, window_width=1.0, window_depth
                        padding_val=29.99, area_mode=True)
 
 
+def _ego_settings(ego_motion, **defaults):
+    """The defaults of a method, overridden by the ``ego_motion`` dict less its ``method``; any other key raises."""
+    unknown = set(ego_motion) - set(defaults) - {"method"}
+    if unknown:
+        raise ValueError("unknown ego_motion settings: %s" % sorted(unknown))
+    defaults.update({k: v for k, v in ego_motion.items() if k != "method"})
+    return defaults
+
 class StreamingDetector:
     """``det = StreamingDetector(model)``; ``pred_cls, pred_reg = det(scan)`` per incoming scan.
 
@@ -132,12 +140,8 @@ class StreamingDetector:
             self._prev_pose = None
             self._have_prev = self._have_flow = False
             if ego_motion is not None and method == "flow":
-                kw = dict(huber_delta=0.02, iters=4, max_range=20.0, cls_thresh=self._cls_thresh)
-                unknown = set(ego_motion) - set(kw) - {"method"}
-                if unknown:
-                    raise ValueError("unknown ego_motion settings: %s" % sorted(unknown))
-                kw.update({k: v for k, v in ego_motion.items() if k != "method"})
-                self._ego_kw = kw
+                self._ego_kw = _ego_settings(ego_motion, huber_delta=0.02, iters=4, max_range=20.0,
+                                             cls_thresh=self._cls_thresh)
                 self._ego_out = ops.ego_motion_buffers(self.B, self.N, dev)
                 self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
             if tracks is not None:
@@ -150,13 +154,9 @@ class StreamingDetector:
                 self._track_state = ops.track_buffers(self.B, kw.pop("max_tracks"), self.N, dev)
                 self._track_kw = kw
         if method == "scan_match":
-            kw = dict(window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16, eps_theta=1e-7, eps_u=1e-7,
-                      min_pivot=1e-6, max_range=20.0, cls_thresh=self._cls_thresh)
-            unknown = set(ego_motion) - set(kw) - {"method"}
-            if unknown:
-                raise ValueError("unknown ego_motion settings: %s" % sorted(unknown))
-            kw.update({k: v for k, v in ego_motion.items() if k != "method"})
-            self._match_kw = kw
+            self._match_kw = _ego_settings(ego_motion, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16,
+                                           eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, max_range=20.0,
+                                           cls_thresh=self._cls_thresh)
             # everything the matching tail touches, before any capture; the motion buffer is also the next step's init
             if flow_model is None:
                 self._prev_scan = torch.zeros((self.B, self.N, 1), dtype=torch.float32, device=dev)
@@ -164,14 +164,10 @@ class StreamingDetector:
             self._match_out = ops.scan_match_buffers(self.B, self.N, dev)
             self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
         if method == "keyframe":
-            kw = dict(window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16, eps_theta=1e-7, eps_u=1e-7,
-                      min_pivot=1e-6, max_range=20.0, cls_thresh=self._cls_thresh, key_dist=0.3, key_rot=0.3,
-                      min_share=0.5, max_misses=2)
-            unknown = set(ego_motion) - set(kw) - {"method"}
-            if unknown:
-                raise ValueError("unknown ego_motion settings: %s" % sorted(unknown))
-            kw.update({k: v for k, v in ego_motion.items() if k != "method"})
-            self._key_kw = kw
+            self._key_kw = _ego_settings(ego_motion, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16,
+                                         eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, max_range=20.0,
+                                         cls_thresh=self._cls_thresh, key_dist=0.3, key_rot=0.3, min_share=0.5,
+                                         max_misses=2)
             # the keyframe, its bookkeeping and the pose live on the device, allocated before any capture
             self._key_state = ops.keyframe_buffers(self.B, self.N, dev)
             self._key_out = ops.keyframe_match_buffers(self.B, self.N, dev)

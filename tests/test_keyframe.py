@@ -18,7 +18,7 @@ import pytest
 
 from oracle import ref_numpy as R
 from test_ego_motion import seq_sum
-from test_scan_match import (DEFAULTS, MARGIN_MIN, _Margins, add_people, angle_table, corridor, make_room,
+from test_scan_match import (DEFAULTS, MARGIN_MIN, _Margins, _iterate, add_people, angle_table, corridor, make_room,
                              match_oracle, person_points, ray_cast)
 
 POLICY = dict(key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2)
@@ -43,133 +43,21 @@ def compose(pose, rel):
     return np.array([pose[0] + (c * rel[1] - s * rel[2]), pose[1] + (s * rel[1] + c * rel[2]), pose[2] + rel[0]])
 
 
-def _centres(qx, qy, phi0, dphi, N, valid, margins):
-    """mid [N] int: the beam every transformed point falls on; the rounding margins of the points that vote."""
-    if dphi == 0.0:
-        return np.zeros(len(qx), np.int64)
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        qd = (np.arctan2(qy, qx) - phi0) / dphi
-        t = np.rint(qd)
-    t = np.where(t >= -N, t, -N)                               # a NaN gives -N
-    t = np.where(t <= 2 * N, t, 2 * N)
-    fin = valid & np.isfinite(qd)
-    margins.take("centre", np.abs(np.abs(qd[fin] - np.floor(qd[fin])) - 0.5))
-    return t.astype(np.int64)
-
-
-def _correspond(ax, ay, px, py, valid, th, ux, uy, phi0, dphi, W, gate2, gap2, margins):
-    """_correspond of tests/test_scan_match.py with the projective window centre."""
-    N = len(ax)
-    c, s = np.cos(th), np.sin(th)
-    with np.errstate(invalid="ignore", over="ignore"):
-        qx, qy = (c * px - s * py) + ux, (s * px + c * py) + uy
-        mid = _centres(qx, qy, phi0, dphi, N, valid, margins)
-        i = np.arange(N)
-        js = mid[:, None] + np.arange(-W, W + 1)[None]
-        inside = (js >= 0) & (js < N)
-        jc = np.where(inside, js, 0)
-        assert jc.min() >= 0 and jc.max() < N                  # nothing outside [0, N) is read
-        dx, dy = qx[:, None] - np.take(ax, jc, mode="raise"), qy[:, None] - np.take(ay, jc, mode="raise")
-        d2 = dx * dx + dy * dy
-        d2 = np.where(inside & ~np.isnan(d2), d2, np.inf)
-        col = np.argmin(d2, axis=1)                            # the first minimum: the lower j
-        bd, j = d2[i, col], jc[i, col]
-        near = valid & (bd < np.inf) & (bd <= gate2)
-        second = np.partition(d2, 1, axis=1)[:, 1]
-        margins.take("nearest", (second - bd)[near])
-        margins.take("gate", np.abs(bd - gate2)[valid & (bd < np.inf)])
-        jx, jy = ax[j], ay[j]
-        qual, g2, e, f2s = [], [], [], []
-        for side in (-1, 1):
-            kk = j + side
-            ok = near & (kk >= 0) & (kk < N)
-            kc = np.where(ok, kk, 0)
-            fx, fy = ax[kc] - jx, ay[kc] - jy
-            f2 = fx * fx + fy * fy
-            qual.append(ok & (f2 > 0.0) & (f2 <= gap2))        # NaN: not valid
-            margins.take("gap", np.abs(f2 - gap2)[ok & (f2 > 0.0)])
-            gx, gy = qx - ax[kc], qy - ay[kc]
-            g2.append(gx * gx + gy * gy)
-            e.append((fx, fy))
-            f2s.append(f2)
-        plus = qual[1] & (~qual[0] | (g2[1] < g2[0]))
-        margins.take("partner", np.abs(g2[1] - g2[0])[qual[0] & qual[1]])
-        matched = near & (qual[0] | qual[1])
-        ex, ey = np.where(plus, e[1][0], e[0][0]), np.where(plus, e[1][1], e[0][1])
-        length = np.sqrt(np.where(plus, f2s[1], f2s[0]))
-        with np.errstate(divide="ignore"):
-            nx, ny = -ey / length, ex / length
-        return matched, j, (qx, qy), (qx - jx, qy - jy), (nx, ny)
-
-
-def _match(ax, ay, px, py, valid, init, phi0, dphi, window, gate, max_gap, huber_delta, iters, eps_theta, eps_u,
-           min_pivot, sum, margins):
-    """The iteration of match_oracle (tests/test_scan_match.py) around the projective correspondence."""
-    N = len(ax)
-    th, ux, uy = (float(v) for v in init)
-    gate2, gap2 = gate * gate, max_gap * max_gap
-    failed, used, count, rms, obs = False, 0, 0, np.nan, 0.0
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        for it in range(int(iters)):
-            k, _, (qx, qy), (dx, dy), (nx, ny) = _correspond(ax, ay, px, py, valid, th, ux, uy, phi0, dphi, window,
-                                                               gate2, gap2, margins)
-            qx, qy, dx, dy, nx, ny = (v[k] for v in (qx, qy, dx, dy, nx, ny))
-            r = nx * dx + ny * dy
-            ar = np.abs(r)
-            if huber_delta > 0.0:
-                w = np.where(ar > huber_delta, huber_delta / ar, 1.0)
-                margins.take("huber", np.abs(ar - huber_delta))
-            else:
-                w = np.ones_like(r)
-            J = (nx * (-qy) + ny * qx, nx, ny)
-            A = {(a, b): float(sum(w * (J[a] * J[b]))) for a in range(3) for b in range(a, 3)}
-            g = [float(sum(w * (J[a] * r))) for a in range(3)]
-            sw, swrr = float(sum(w)), float(sum(w * (r * r)))
-            used, count = it + 1, int(k.sum())
-            rms = np.sqrt(np.float64(swrr) / np.float64(sw))
-            if count < 3:
-                failed, obs = True, 0.0
-                break
-            dmax = max(A[0, 0], max(A[1, 1], A[2, 2]))
-            floor_ = min_pivot * dmax
-            pivots = [A[0, 0]]
-            failed = not pivots[0] > floor_
-            if not failed:
-                l00 = np.sqrt(pivots[0])
-                l10, l20 = A[0, 1] / l00, A[0, 2] / l00
-                pivots.append(A[1, 1] - l10 * l10)
-                failed = not pivots[1] > floor_
-                if not failed:
-                    l11 = np.sqrt(pivots[1])
-                    l21 = (A[1, 2] - l20 * l10) / l11
-                    pivots.append((A[2, 2] - l20 * l20) - l21 * l21)
-                    failed = not pivots[2] > floor_
-                    if not failed:
-                        l22 = np.sqrt(pivots[2])
-            obs = min(pivots) / dmax if dmax > 0.0 else 0.0
-            if dmax > 0.0:
-                margins.take("pivot", [abs(p / dmax - min_pivot) for p in pivots])
-            if failed:
-                break
-            y0 = -g[0] / l00
-            y1 = (-g[1] - l10 * y0) / l11
-            y2 = ((-g[2] - l20 * y0) - l21 * y1) / l22
-            x2 = y2 / l22
-            x1 = (y1 - l21 * x2) / l11
-            x0 = ((y0 - l10 * x1) - l20 * x2) / l00
-            c0, s0 = np.cos(x0), np.sin(x0)
-            th, ux, uy = th + x0, (c0 * ux - s0 * uy) + x1, (s0 * ux + c0 * uy) + x2
-            margins.take("stop", [abs(abs(x0) - eps_theta), abs(max(abs(x1), abs(x2)) - eps_u)])
-            if abs(x0) < eps_theta and max(abs(x1), abs(x2)) < eps_u:
-                break
-        corr, res = np.full(N, -1, np.int32), np.full((N, 2), np.nan)
-        if not failed:
-            k, j, _, (dx, dy), _ = _correspond(ax, ay, px, py, valid, th, ux, uy, phi0, dphi, window, gate2, gap2,
-                                               margins)
-            c, s = np.cos(th), np.sin(th)
-            corr[k] = j[k]
-            res[k] = np.stack([c * dx + s * dy, (-s) * dx + c * dy], axis=1)[k]
-    return failed, np.array([th, ux, uy]), count, rms, used, obs, corr, res
+def _centres(phi0, dphi, N):
+    """N9's window centres for ``_correspond`` of tests/test_scan_match.py: mid [N] int, the beam every transformed
+    point falls on; the rounding margins of the points that vote."""
+    def centres(qx, qy, th, valid, margins):
+        if dphi == 0.0:
+            return np.zeros(len(qx), np.int64)
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            qd = (np.arctan2(qy, qx) - phi0) / dphi
+            t = np.rint(qd)
+        t = np.where(t >= -N, t, -N)                           # a NaN gives -N
+        t = np.where(t <= 2 * N, t, 2 * N)
+        fin = valid & np.isfinite(qd)
+        margins.take("centre", np.abs(np.abs(qd[fin] - np.floor(qd[fin])) - 0.5))
+        return t.astype(np.int64)
+    return centres
 
 
 def keyframe_oracle(r_cur, tab, state, person=None, max_range=20.0, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05,
@@ -207,9 +95,9 @@ def keyframe_oracle(r_cur, tab, state, person=None, max_range=20.0, window=16, g
         init = np.asarray(state["key_rel"], np.float64)
         if not np.isfinite(init).all():
             init = np.zeros(3)
-        failed, rel, count, rms, used, obs, corr, res = _match(ax, ay, px, py, valid, init, phi0, dphi, window, gate,
-                                                               max_gap, huber_delta, iters, eps_theta, eps_u,
-                                                               min_pivot, sum, margins)
+        failed, rel, count, rms, used, obs, corr, res = _iterate(ax, ay, px, py, valid, init, _centres(phi0, dphi, N),
+                                                                 window, gate, max_gap, huber_delta, iters, eps_theta,
+                                                                 eps_u, min_pivot, sum, margins)
         out.update(count=np.int32(count), iters_used=np.int32(used), obs=float(obs), corr=corr, flow_residual=res)
         if not failed:
             out.update(motion=rel, ok=np.uint8(1), rms=float(rms))

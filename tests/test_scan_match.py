@@ -152,16 +152,25 @@ class _Margins(dict):
             self[kind] = min(self.get(kind, np.inf), float(v.min()))
 
 
-def _correspond(ax, ay, px, py, valid, th, ux, uy, dphi, W, gate2, gap2, margins):
-    """The correspondence of every current point at (th, u) -> matched [N] bool, j [N], q, d, n [N,2] each."""
+def _shift_centres(dphi, N):
+    """N8's window centres: beam i + shift(th)."""
+    def centres(qx, qy, th, valid, margins):
+        shift, m_shift = _beam_shift(th, dphi, N)
+        margins.take("shift", [m_shift])
+        return np.arange(N) + shift
+    return centres
+
+
+def _correspond(ax, ay, px, py, valid, th, ux, uy, centres, W, gate2, gap2, margins):
+    """The correspondence of every current point at (th, u) -> matched [N] bool, j [N], q, d, n [N,2] each.
+    centres(qx, qy, th, valid, margins) -> mid [N] int: the centre of every point's search window."""
     N = len(ax)
     c, s = np.cos(th), np.sin(th)
-    shift, m_shift = _beam_shift(th, dphi, N)
-    margins.take("shift", [m_shift])
     with np.errstate(invalid="ignore", over="ignore"):
         qx, qy = (c * px - s * py) + ux, (s * px + c * py) + uy
+        mid = centres(qx, qy, th, valid, margins)
         i = np.arange(N)
-        js = i[:, None] + shift + np.arange(-W, W + 1)[None]
+        js = mid[:, None] + np.arange(-W, W + 1)[None]
         inside = (js >= 0) & (js < N)
         jc = np.where(inside, js, 0)
         assert jc.min() >= 0 and jc.max() < N                  # nothing outside [0, N) is read
@@ -198,34 +207,19 @@ def _correspond(ax, ay, px, py, valid, th, ux, uy, dphi, W, gate2, gap2, margins
         return matched, j, (qx, qy), (qx - jx, qy - jy), (nx, ny)
 
 
-def match_oracle(r_prev, r_cur, tab, init=None, person=None, max_range=20.0, window=16, gate=0.5, max_gap=0.3,
-                 huber_delta=0.05, iters=16, eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, sum=np.sum):
-    """The formulas of pof_scan_match for one scan pair in float64.  r_prev, r_cur [N] float32, tab [3N] the angle
-    table, init [3] or None, person [N] bool: current points that do not vote (``person_points``).  `sum` adds a 1-D
-    array (np.sum: pairwise; seq_sum).  -> dict motion [3], ok, count, rms, iters_used, obs, corr [N], flow_residual
-    [N,2], and margins: the smallest margin of every kind of discrete decision taken, and their number."""
-    r0, r1 = np.asarray(r_prev, np.float32), np.asarray(r_cur, np.float32)
-    N = len(r0)
-    tab = np.asarray(tab, np.float64)
-    cs, sn = tab[N::2], tab[N + 1::2]
-    dphi = tab[1] - tab[0] if N > 1 else 0.0
-    with np.errstate(invalid="ignore", over="ignore"):
-        v0 = np.isfinite(r0) & (r0.astype(np.float64) < max_range)
-        valid = np.isfinite(r1) & (r1.astype(np.float64) < max_range)
-        ax, ay = np.where(v0, r0.astype(np.float64) * cs, np.nan), np.where(v0, r0.astype(np.float64) * sn, np.nan)
-        px, py = r1.astype(np.float64) * cs, r1.astype(np.float64) * sn
-    if person is not None:
-        valid = valid & ~np.asarray(person, bool)
-    th, ux, uy = 0.0, 0.0, 0.0
-    if init is not None and np.isfinite(np.asarray(init, np.float64)).all():
-        th, ux, uy = (float(v) for v in init)
+def _iterate(ax, ay, px, py, valid, init, centres, window, gate, max_gap, huber_delta, iters, eps_theta, eps_u,
+             min_pivot, sum, margins):
+    """The matcher core from the start value init [3]: the iterations and the final correspondence pass, around the
+    window centres of ``_correspond``.  -> failed, (theta, u) [3], count, rms, iters_used, obs, corr [N],
+    flow_residual [N,2]."""
+    N = len(ax)
+    th, ux, uy = (float(v) for v in init)
     gate2, gap2 = gate * gate, max_gap * max_gap
-    margins = _Margins()
     failed, used, count, rms, obs = False, 0, 0, np.nan, 0.0
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         for it in range(int(iters)):
-            k, _, (qx, qy), (dx, dy), (nx, ny) = _correspond(ax, ay, px, py, valid, th, ux, uy, dphi, window, gate2,
-                                                               gap2, margins)
+            k, _, (qx, qy), (dx, dy), (nx, ny) = _correspond(ax, ay, px, py, valid, th, ux, uy, centres, window,
+                                                               gate2, gap2, margins)
             qx, qy, dx, dy, nx, ny = (v[k] for v in (qx, qy, dx, dy, nx, ny))
             r = nx * dx + ny * dy
             ar = np.abs(r)
@@ -277,12 +271,39 @@ def match_oracle(r_prev, r_cur, tab, init=None, person=None, max_range=20.0, win
                 break
         corr, res = np.full(N, -1, np.int32), np.full((N, 2), np.nan)
         if not failed:
-            k, j, _, (dx, dy), _ = _correspond(ax, ay, px, py, valid, th, ux, uy, dphi, window, gate2, gap2, margins)
+            k, j, _, (dx, dy), _ = _correspond(ax, ay, px, py, valid, th, ux, uy, centres, window, gate2, gap2, margins)
             c, s = np.cos(th), np.sin(th)
             corr[k] = j[k]
             res[k] = np.stack([c * dx + s * dy, (-s) * dx + c * dy], axis=1)[k]
+    return failed, np.array([th, ux, uy]), count, rms, used, obs, corr, res
+
+
+def match_oracle(r_prev, r_cur, tab, init=None, person=None, max_range=20.0, window=16, gate=0.5, max_gap=0.3,
+                 huber_delta=0.05, iters=16, eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, sum=np.sum):
+    """The formulas of pof_scan_match for one scan pair in float64.  r_prev, r_cur [N] float32, tab [3N] the angle
+    table, init [3] or None, person [N] bool: current points that do not vote (``person_points``).  `sum` adds a 1-D
+    array (np.sum: pairwise; seq_sum).  -> dict motion [3], ok, count, rms, iters_used, obs, corr [N], flow_residual
+    [N,2], and margins: the smallest margin of every kind of discrete decision taken, and their number."""
+    r0, r1 = np.asarray(r_prev, np.float32), np.asarray(r_cur, np.float32)
+    N = len(r0)
+    tab = np.asarray(tab, np.float64)
+    cs, sn = tab[N::2], tab[N + 1::2]
+    dphi = tab[1] - tab[0] if N > 1 else 0.0
+    with np.errstate(invalid="ignore", over="ignore"):
+        v0 = np.isfinite(r0) & (r0.astype(np.float64) < max_range)
+        valid = np.isfinite(r1) & (r1.astype(np.float64) < max_range)
+        ax, ay = np.where(v0, r0.astype(np.float64) * cs, np.nan), np.where(v0, r0.astype(np.float64) * sn, np.nan)
+        px, py = r1.astype(np.float64) * cs, r1.astype(np.float64) * sn
+    if person is not None:
+        valid = valid & ~np.asarray(person, bool)
+    if init is None or not np.isfinite(np.asarray(init, np.float64)).all():
+        init = np.zeros(3)
+    margins = _Margins()
+    failed, motion, count, rms, used, obs, corr, res = _iterate(ax, ay, px, py, valid, init, _shift_centres(dphi, N),
+                                                                window, gate, max_gap, huber_delta, iters, eps_theta,
+                                                                eps_u, min_pivot, sum, margins)
     nan = np.nan
-    return {"motion": np.array([nan, nan, nan] if failed else [th, ux, uy]), "ok": np.uint8(not failed),
+    return {"motion": np.full(3, nan) if failed else motion, "ok": np.uint8(not failed),
             "count": np.int32(count), "rms": nan if failed else float(rms), "iters_used": np.int32(used),
             "obs": float(obs), "corr": corr, "flow_residual": res, "margins": margins}
 
