@@ -470,6 +470,73 @@ int pof_keyframe_match(const float *ranges_cur, const double *tab, const int32_t
                        pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N10 keyframe map: N9 with a ring of `keys` = K keyframes per sensor.  The scan is matched against the ACTIVE keyframe
+ * exactly as N9 matches against its only one; when the sensor leaves it, it first looks for a stored keyframe it has
+ * come back to and switches to that one instead of storing a new one.  The next match against a revisited keyframe k
+ * gives pose = key_pose[k] o match: everything accumulated since k was stored is dropped, so the drift is bounded by
+ * the area the ring covers and not by the distance travelled.  The reference has no scan matcher; the specification is
+ * this comment together with N8's and N9's (restated in float64 NumPy by tests/test_keyframe_map.py).  One sensor per
+ * batch entry, one launch.
+ * State per sensor, persistent, updated in place, allocated by the caller:
+ *   key_ranges [B][K][N] float32 (NaN = not a vertex), key_pose [B][K][3] float64 = (x, y, phi) of every stored
+ *   keyframe, key_valid [B][K] uint8 = the slot holds a keyframe, key_stamp [B][K] int32 = the value of `step` when the
+ *   slot was last active, key_active [B] int32 = the active slot (a value outside [0, K) is read as the nearest slot),
+ *   key_rel [B][3] float64 = (theta, u) of the last good match against the active slot, key_age [B] int32 = scans on
+ *   the active slot, key_misses [B] int32 = failed matches in a row, step [B] int32 = the scan counter, pose [B][3]
+ *   float64.
+ * Settings: N9's, keys (1..64) and revisit in [0, 1].  Points, the gated current scan g, V, the correspondence with
+ * its beam-projected window centre, the iterations and the composition key_pose o (theta, u): N9's, operation for
+ * operation.
+ * One step of a sensor (a = key_active, old = the pose on entry):
+ *   1. key_valid[a] == 0 (seeding): N9's rule 1 on slot a -- key_ranges[a] <- g, key_pose[a] = old, key_valid[a] = 1,
+ *      key_rel = 0, key_age = 0, key_misses = 0; ok = 0, motion and rms NaN, count = 0, iters_used = 0, obs = 0,
+ *      key_replaced = 1, corr -1, flow_residual NaN; the pose stays.
+ *   2. otherwise the match runs against slot a from key_rel (zeros when a component is not finite), exactly N9's;
+ *      corr and flow_residual are written against slot a.
+ *   3. match ok: key_rel = (theta, u), pose = key_pose[a] o key_rel, key_misses = 0.  With
+ *        left  = |theta| > key_rot  or  u_x u_x + u_y u_y > key_dist key_dist
+ *        stale = (double)count < min_share * V
+ *      neither: the keyframe is held, key_age += 1.
+ *      left (whether or not stale): for every valid slot k != a, in ascending k, the pose relative to that keyframe
+ *          theta_k = remainder(phi - phi_k, 2 pi)  (the IEEE remainder),  d = t - t_k,  (c_k, s_k) = (cos, sin) phi_k,
+ *          u_k = (c_k d_x + s_k d_y, (-s_k) d_x + c_k d_y),  d2_k = u_kx u_kx + u_ky u_ky;
+ *        k qualifies when |theta_k| <= revisit * key_rot and d2_k <= (revisit * key_dist) (revisit * key_dist); the
+ *        winner is the qualifying slot of smallest d2_k, compared with a strict <: ties go to the lower k.
+ *        With a winner the sensor SWITCHES: key_active = k, key_rel = (theta_k, u_k), key_age = 0, key_switched = 1;
+ *          nothing is stored and the pose stays the one just formed from slot a -- the next scan's match against k
+ *          re-anchors it.
+ *        Without one a NEW KEYFRAME is stored: slot = the lowest k with key_valid == 0; if there is none the valid slot
+ *          k != a of smallest key_stamp (strict <: the lower k on a tie); if there is none either (K = 1) a.  Then
+ *          key_ranges[slot] <- g, key_pose[slot] = pose, key_valid[slot] = 1, key_active = slot, key_rel = 0,
+ *          key_age = 0, key_replaced = 1.
+ *      stale only: the sensor has not left, the place has changed -- slot a is overwritten in place as N9's rule 3:
+ *        key_ranges[a] <- g, key_pose[a] = pose, key_rel = 0, key_age = 0, key_replaced = 1.
+ *   4. match failed: N9's rule 4 on slot a; re-anchoring overwrites slot a at the unchanged pose.
+ *   5. always: key_stamp[key_active] = step for the slot that is active at the end, then step += 1.
+ * Outputs: N9's (motion, count, rms, ok, iters_used, obs, key_replaced; optional corr, flow_residual, rot, trans,
+ *   flow_trans) and key_switched [B] uint8, key_slot [B] int32 = the active slot at the end.
+ * Properties:
+ *   With K = 1 every field and output has the bits of pof_keyframe_match on the same scans.
+ *   A workgroup reads and writes only its own sensor's rows.  The row of the active slot is read before the first
+ *   barrier; any row is written after the last correspondence pass, every thread the beams it staged: N9's in-place
+ *   argument, and a write to another slot has no hazard at all.  The slot search runs in every thread over the same
+ *   values in ascending k -- the same decision everywhere, no atomics -- and the scalar state is written only after a
+ *   barrier behind it.  Fixed summation order, no FMA: the same bits in every run, at every batch position, in a graph
+ *   replay.  N <= 4096 (POF_E_SHAPE beyond, nothing written); one wave per sensor up to N = 512.  POF_E_BADARG: as N9,
+ *   keys outside 1..64, revisit outside [0, 1] (or NaN), a NULL state or required output pointer.
+ * ---------------------------------------------------------------------- */
+int pof_keyframe_map_match(const float *ranges_cur, const double *tab, const int32_t *instance_mask,
+                           const int32_t *num_det, const double *det_cls, double cls_thresh, double max_range,
+                           int window, double gate, double max_gap, double huber_delta, int iters, double eps_theta,
+                           double eps_u, double min_pivot, double key_dist, double key_rot, double min_share,
+                           int max_misses, double revisit, int B, int N, int keys, float *key_ranges, double *key_pose,
+                           uint8_t *key_valid, int32_t *key_stamp, int32_t *key_active, double *key_rel,
+                           int32_t *key_age, int32_t *key_misses, int32_t *step, double *pose, double *motion,
+                           int32_t *count, double *rms, uint8_t *ok, int32_t *iters_used, double *obs,
+                           uint8_t *key_replaced, uint8_t *key_switched, int32_t *key_slot, int32_t *corr,
+                           double *flow_residual, float *rot, double *trans, double *flow_trans, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

@@ -1291,6 +1291,125 @@ def keyframe_match(ranges_cur, tab, state, *, instance_mask=None, num_det=None, 
     return out
 
 
+KeyframeMapState = collections.namedtuple("KeyframeMapState", ("key_ranges", "key_pose", "key_valid", "key_stamp",
+                                                                "key_active", "key_rel", "key_age", "key_misses", "step",
+                                                                "pose"))
+KeyframeMapMatch = collections.namedtuple("KeyframeMapMatch", ("motion", "count", "rms", "ok", "iters_used", "obs",
+                                                                "key_replaced", "key_switched", "key_slot", "corr",
+                                                                "flow_residual"))
+_KEYFRAME_MAP_STATE = (("key_ranges", torch.float32), ("key_pose", torch.float64), ("key_valid", torch.uint8),
+                       ("key_stamp", torch.int32), ("key_active", torch.int32), ("key_rel", torch.float64),
+                       ("key_age", torch.int32), ("key_misses", torch.int32), ("step", torch.int32),
+                       ("pose", torch.float64))
+_KEYFRAME_MAP_OUT = (("motion", torch.float64), ("count", torch.int32), ("rms", torch.float64), ("ok", torch.uint8),
+                     ("iters_used", torch.int32), ("obs", torch.float64), ("key_replaced", torch.uint8),
+                     ("key_switched", torch.uint8), ("key_slot", torch.int32), ("corr", torch.int32),
+                     ("flow_residual", torch.float64))
+
+
+def _keyframe_map_state_shapes(B, N, K):
+    return (B, K, N), (B, K, 3), (B, K), (B, K), (B,), (B, 3), (B,), (B,), (B,), (B, 3)
+
+
+def _keyframe_map_out_shapes(B, N):
+    return (B, 3), (B,), (B,), (B,), (B,), (B,), (B,), (B,), (B,), (B, N), (B, N, 2)
+
+
+def _check_keys(keys):
+    if not 1 <= int(keys) <= 64:
+        raise ValueError("keys must be in [1, 64]")
+    return int(keys)
+
+
+def keyframe_map_buffers(B, N, keys=16, device="cuda"):
+    """The persistent state of ``keyframe_map_match`` for B sensors of N points and a ring of ``keys`` (1..64)
+    keyframes each: no keyframe yet, slot 0 active, the pose at zero (allocate once, before a graph capture).
+    -> ``KeyframeMapState``."""
+    keys = _check_keys(keys)
+    return KeyframeMapState(*(torch.zeros(shape, dtype=dt, device=device)
+                              for (_, dt), shape in zip(_KEYFRAME_MAP_STATE, _keyframe_map_state_shapes(B, N, keys))))
+
+
+def keyframe_map_match_buffers(B, N, device="cuda"):
+    """The eleven outputs of ``keyframe_map_match``, zero-filled, as its ``out=``."""
+    return KeyframeMapMatch(*(torch.zeros(shape, dtype=dt, device=device)
+                              for (_, dt), shape in zip(_KEYFRAME_MAP_OUT, _keyframe_map_out_shapes(B, N))))
+
+
+def keyframe_map_reset(state, pose=None):
+    """Forget every keyframe of every sensor, IN PLACE and without a synchronisation: slot 0 is active, the scan
+    counter restarts and the next ``keyframe_map_match`` seeds.  pose ([3] or [B,3]): the pose to go on from; zeros by
+    default."""
+    state = KeyframeMapState(*state)
+    for t in state[:-1]:
+        t.zero_()
+    if pose is None:
+        state.pose.zero_()
+    else:
+        pose = torch.as_tensor(pose, dtype=torch.float64).reshape(-1, 3)
+        state.pose.copy_(pose.expand(state.pose.shape[0], 3), non_blocking=True)
+    return state
+
+
+def keyframe_map_match(ranges_cur, tab, state, *, instance_mask=None, num_det=None, det_cls=None, cls_thresh=0.5,
+                       max_range=20.0, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16, eps_theta=1e-7,
+                       eps_u=1e-7, min_pivot=1e-6, key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2, revisit=0.5,
+                       out=None, rot=None, trans=None, flow_trans=None):
+    """N10: one step of keyframe matching against a ring of keyframes per sensor -- ``keyframe_match`` on the active
+    keyframe, and when the sensor leaves it, it switches to a stored keyframe it has come back to instead of storing a
+    new one, so the next match re-anchors the pose there and the drift of the way round is dropped; one launch per
+    batch (include/pof_abi.h states the algorithm).
+
+    ranges_cur [B,N] f32, tab the angle table, ``state`` a ``KeyframeMapState`` (``keyframe_map_buffers``; its
+    key_ranges [B,K,N] gives the ring size K), UPDATED IN PLACE.  The settings up to ``max_misses`` are
+    ``keyframe_match``'s.  A stored keyframe counts as revisited when the pose just formed lies within ``revisit``
+    (0..1) times ``key_rot`` and ``key_dist`` of it; the nearest such keyframe becomes the active one.  Without one the
+    scan is stored in a free slot, else over the slot that has not been active for the longest time.
+    -> ``KeyframeMapMatch``: the outputs of ``keyframe_match`` and key_switched [B] u8, key_slot [B] i32 (the active
+    slot after the step).  ``out``: a ``KeyframeMapMatch`` of preallocated tensors (``keyframe_map_match_buffers``);
+    ``rot``, ``trans``, ``flow_trans`` as ``keyframe_match``."""
+    _check_matcher_settings(window, iters, gate=gate, max_gap=max_gap, huber_delta=huber_delta, key_dist=key_dist,
+                            key_rot=key_rot, min_share=min_share)
+    if int(max_misses) < 0:
+        raise ValueError("max_misses must be >= 0")
+    if not 0.0 <= float(revisit) <= 1.0:
+        raise ValueError("revisit must be in [0, 1]")
+    _nms_gate(instance_mask, num_det, det_cls)
+    ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
+    if ranges_cur.dim() != 2:
+        raise ValueError("ranges_cur must be [B,N]")
+    B, N = ranges_cur.shape
+    dev = ranges_cur.device
+    if N < 1 or _dev(tab, torch.float64, "tab").numel() != 3 * N:
+        raise ValueError("the ranges must be [B,N] matching the angle table")
+    state = KeyframeMapState(*state)
+    if not isinstance(state.key_ranges, torch.Tensor) or state.key_ranges.dim() != 3:
+        raise ValueError("state.key_ranges must be [B,K,N]")
+    K = _check_keys(state.key_ranges.shape[1])
+    _check_fields(state, _KEYFRAME_MAP_STATE, _keyframe_map_state_shapes(B, N, K), "state")
+    instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
+    if out is None:
+        out = keyframe_map_match_buffers(B, N, dev)
+    else:
+        out = KeyframeMapMatch(*out)
+        _check_fields(out, _KEYFRAME_MAP_OUT, _keyframe_map_out_shapes(B, N), "out")
+    if rot is not None and tuple(_dev(rot, torch.float32, "rot").shape) not in ((B, 2, 2), (B, 4)):
+        raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
+    for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
+        if t is not None and tuple(_dev(t, torch.float64, name).shape) != (B, 2):
+            raise ValueError("%s must be [B,2]" % name)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_keyframe_map_match", _ptr(ranges_cur), _ptr(tab), _ptr(instance_mask), _ptr(num_det),
+                  _ptr(det_cls), float(cls_thresh), float(max_range), int(window), float(gate), float(max_gap),
+                  float(huber_delta), int(iters), float(eps_theta), float(eps_u), float(min_pivot), float(key_dist),
+                  float(key_rot), float(min_share), int(max_misses), float(revisit), B, N, K,
+                  *[_ptr(t) for t in state], *[_ptr(t) for t in out], _ptr(rot), _ptr(trans), _ptr(flow_trans),
+                  _stream())
+    return out
+
+
 TrackState = collections.namedtuple("TrackState", ("track_id", "track_state", "track_cov", "track_hits", "track_misses",
                                                     "track_age", "next_id", "track_det", "track_confirmed",
                                                     "det_track", "point_track", "dropped"))

@@ -510,6 +510,56 @@ class KeyframeOdometry:
                 "flow_residual": host(res.flow_residual)}
 
 
+class KeyframeMapOdometry:
+    """``KeyframeOdometry`` with a ring of ``keys`` keyframes (``ops.keyframe_map_match``, one launch per scan): a
+    sensor that comes back to a place it has a keyframe of switches to that keyframe, and the next match re-anchors
+    the pose on it -- the drift of the way round is dropped.  ``odo = KeyframeMapOdometry(scan_phi, keys=16,
+    revisit=0.5, key_dist=0.3, ...)`` with the settings of ``ops.keyframe_map_match`` and min_dist (0.5, the NMS
+    distance); ``res = odo.update(scan, pred_cls, pred_reg)`` per scan, ``odo.reset(pose)`` between sequences.
+
+    ``update``: NumPy in and NumPy out, as ``KeyframeOdometry.update``.  -> its dict (key_pose [3] is the active
+    slot's) with key_switched (bool) and key_slot, the active slot after the step."""
+
+    def __init__(self, scan_phi, keys=16, revisit=0.5, **kw):
+        self._tab = _table_for(scan_phi)
+        self._n = self._tab.numel() // 3
+        self._min_dist = kw.pop("min_dist", 0.5)
+        known = {"cls_thresh", "max_range", "window", "gate", "max_gap", "huber_delta", "iters", "eps_theta", "eps_u",
+                 "min_pivot", "key_dist", "key_rot", "min_share", "max_misses"}
+        unknown = set(kw) - known
+        if unknown:
+            raise ValueError("unknown keyframe settings: %s" % sorted(unknown))
+        if not 0.0 <= float(revisit) <= 1.0:
+            raise ValueError("revisit must be in [0, 1]")
+        self._kw = dict(kw, revisit=float(revisit))
+        self._state = ops.keyframe_map_buffers(1, self._n, keys, self._tab.device)
+
+    def reset(self, pose=None):
+        ops.keyframe_map_reset(self._state, pose)
+
+    def update(self, scan, pred_cls=None, pred_reg=None):
+        cur = _to_dev(scan, torch.float32).reshape(1, -1)
+        gate = {}
+        if pred_cls is not None and pred_reg is not None:
+            pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
+            assert pc.ndim == 2 and pc.shape[1] == 1
+            _, dc, num, inst = ops.nms_predicted_center(cur, self._tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
+                                                        _to_dev(pred_reg, torch.float64).reshape(1, -1, 2),
+                                                        self._min_dist)
+            gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
+        res = ops.keyframe_map_match(cur, self._tab, self._state, **gate, **self._kw)
+        host = lambda t: t[0].cpu().numpy()
+        s = self._state
+        slot = int(res.key_slot[0].item())
+        return {"pose": host(s.pose), "motion": host(res.motion), "ok": bool(res.ok[0].item()),
+                "count": int(res.count[0].item()), "rms": float(res.rms[0].item()),
+                "iters_used": int(res.iters_used[0].item()), "obs": float(res.obs[0].item()),
+                "key_replaced": bool(res.key_replaced[0].item()), "key_switched": bool(res.key_switched[0].item()),
+                "key_slot": slot, "key_age": int(s.key_age[0].item()), "key_misses": int(s.key_misses[0].item()),
+                "key_pose": s.key_pose[0, slot].cpu().numpy(), "corr": host(res.corr),
+                "flow_residual": host(res.flow_residual)}
+
+
 def _pose_terms(odom1, odom0=None, batch=1):
     """Host side of ``person_flow`` for B sensors at once: (rot [B,2,2] float32, trans [B,2], flow_trans [B,2]) of the
     poses odom1 [B,3] = (x, y, phi) and the previous ones odom0, as infer_person_flow.py:114-117,145-146 forms them

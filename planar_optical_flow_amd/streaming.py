@@ -23,6 +23,9 @@ N8): no flow net is needed for a pose, and with one the matched motion stands in
 With ``ego_motion=dict(method="keyframe")`` every scan is matched against a keyframe that stays fixed until the sensor
 has left it (``ops.keyframe_match``): one launch that keeps the keyframe, its bookkeeping and the pose on
 the device, so the pose of a sensor that stands still or works in one place does not walk away.
+With ``ego_motion=dict(method="keyframe_map")`` the sensor keeps a ring of keyframes (``ops.keyframe_map_match``, DESIGN
+8, N10): coming back to a stored keyframe switches to it instead of storing a new one, and the next match re-anchors
+the pose there -- still one launch, every decision on the device.
 """
 import numpy as np
 import torch
@@ -76,6 +79,9 @@ class StreamingDetector:
     is the keyframe's composed with that one match, and the launch replaces the keyframe on the device.  It runs from
     the first scan of a sequence on (which becomes the keyframe; ``ego_motion()`` reports ok = False there), and
     ``flow_model`` may be None.
+    With ``method="keyframe_map"`` the dict holds those settings and ``keys`` (16) and ``revisit`` (0.5) of
+    ``ops.keyframe_map_match``: a ring of ``keys`` keyframes per sensor, and a sensor that returns to within ``revisit``
+    times ``key_dist`` / ``key_rot`` of a stored keyframe switches to it, so the next match re-anchors the pose on it.
 
     ``tracks`` (needs ``flow_model``): None, or a dict of ``max_tracks`` (64) and the settings of ``ops.track_update``
     (``gate``, ``q``, ``r_pos``, ``r_vel``, ``v0_var``, ``max_misses``, ``min_hits``).  The step then ends in the track
@@ -115,8 +121,8 @@ class StreamingDetector:
         self.feat_fused = self.pred_cls = self.pred_reg = None
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = None
         method = "flow" if ego_motion is None else dict(ego_motion).get("method", "flow")
-        if method not in ("flow", "scan_match", "keyframe"):
-            raise ValueError("ego_motion method must be 'flow', 'scan_match' or 'keyframe'")
+        if method not in ("flow", "scan_match", "keyframe", "keyframe_map"):
+            raise ValueError("ego_motion method must be 'flow', 'scan_match', 'keyframe' or 'keyframe_map'")
         if ego_motion is not None and method == "flow" and flow_model is None:
             raise ValueError("ego_motion needs flow_model: the motion is fitted to the flow field "
                              "(method='scan_match' and method='keyframe' match the scans themselves)")
@@ -173,6 +179,19 @@ class StreamingDetector:
             self._key_out = ops.keyframe_match_buffers(self.B, self.N, dev)
             self._pose_state = self._key_state.pose
             self._key_seen = False
+        self._key_map = method == "keyframe_map"
+        if self._key_map:
+            kw = _ego_settings(ego_motion, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16,
+                               eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, max_range=20.0, cls_thresh=self._cls_thresh,
+                               key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2, keys=16, revisit=0.5)
+            # the ring of keyframes, its bookkeeping and the pose live on the device, allocated before any capture
+            self._key_state = ops.keyframe_map_buffers(self.B, self.N, kw.pop("keys"), dev)
+            self._key_out = ops.keyframe_map_match_buffers(self.B, self.N, dev)
+            if not 0.0 <= float(kw["revisit"]) <= 1.0:
+                raise ValueError("revisit must be in [0, 1]")
+            self._key_kw = kw
+            self._pose_state = self._key_state.pose
+            self._key_seen = False
 
     @staticmethod
     def _refuse_float16(model):
@@ -200,7 +219,8 @@ class StreamingDetector:
         if self._match_kw is not None:
             self._match_out.motion.zero_()            # the first pair of a sequence starts from rest
         if self._key_kw is not None:
-            ops.keyframe_reset(self._key_state)       # the next scan becomes the keyframe
+            # the next scan becomes the keyframe
+            (ops.keyframe_map_reset if self._key_map else ops.keyframe_reset)(self._key_state)
             self._key_seen = False
         if self._dead_reckons():
             start = np.zeros((self.B, 3)) if pose is None else np.broadcast_to(
@@ -293,8 +313,8 @@ class StreamingDetector:
         terms = {}
         if self._flow_model is not None:
             terms = dict(rot=self._pose_rot, trans=self._pose_trans, flow_trans=self._pose_flow_trans)
-        ops.keyframe_match(self._scan[:, 0], self.tab, self._key_state, out=self._key_out, **gate, **terms,
-                           **self._key_kw)
+        match = ops.keyframe_map_match if self._key_map else ops.keyframe_match
+        match(self._scan[:, 0], self.tab, self._key_state, out=self._key_out, **gate, **terms, **self._key_kw)
 
     def _pose_views(self, buf):
         nb = self.B
@@ -429,11 +449,26 @@ class StreamingDetector:
         With ``method="scan_match"`` the dicts also hold iters_used and obs, and the outputs are an ``ops.ScanMatch``.
         With ``method="keyframe"`` the motion is the one against the keyframe, the dicts also hold key_replaced,
         key_age and key_pose [3], the outputs are an ``ops.KeyframeMatch``, and one scan is enough (ok is False there).
+        With ``method="keyframe_map"`` the dicts hold those and key_switched and key_slot, key_pose is the active
+        slot's, and the outputs are an ``ops.KeyframeMapMatch``.
         Synchronises."""
         if self._key_kw is not None:
             if not self._key_seen:
                 raise RuntimeError("feed the detector a scan first")
             o, s = self._key_out, self._key_state
+            if self._key_map:
+                host = {k: t.cpu().numpy() for k, t in (("motion", o.motion), ("ok", o.ok), ("count", o.count),
+                                                        ("rms", o.rms), ("iters_used", o.iters_used), ("obs", o.obs),
+                                                        ("pose", s.pose), ("key_replaced", o.key_replaced),
+                                                        ("key_age", s.key_age), ("key_pose", s.key_pose),
+                                                        ("key_switched", o.key_switched), ("key_slot", o.key_slot))}
+                return [{"motion": host["motion"][b], "ok": bool(host["ok"][b]), "count": int(host["count"][b]),
+                         "rms": float(host["rms"][b]), "iters_used": int(host["iters_used"][b]),
+                         "obs": float(host["obs"][b]), "pose": host["pose"][b],
+                         "key_replaced": bool(host["key_replaced"][b]), "key_age": int(host["key_age"][b]),
+                         "key_pose": host["key_pose"][b, host["key_slot"][b]],
+                         "key_switched": bool(host["key_switched"][b]), "key_slot": int(host["key_slot"][b])}
+                        for b in range(self.B)], o
             host = [t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, o.iters_used, o.obs, s.pose,
                                               o.key_replaced, s.key_age, s.key_pose)]
             return [{"motion": host[0][b], "ok": bool(host[1][b]), "count": int(host[2][b]), "rms": float(host[3][b]),

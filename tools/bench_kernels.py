@@ -168,6 +168,17 @@ if "person" in which:
     def keyframe(iters):
         kf_state.key_rel.zero_()
         ops.keyframe_match(scans, tab, kf_state, instance_mask=inst, num_det=num, det_cls=dc, iters=iters, out=kf_out)
+    # N10: the keyframe map on the same inputs, with one slot and with sixteen: `prev` seeds slot 0 of every sensor, the
+    # rest as N9's row.  The sensor stands still, so no step leaves its keyframe and the slot search never runs
+    km_state = {K: ops.keyframe_map_buffers(B, N, K, dev) for K in (1, 16)}
+    km_out = ops.keyframe_map_match_buffers(B, N, dev)
+    for K in km_state:
+        ops.keyframe_map_match(prev, tab, km_state[K])
+
+    def keyframe_map(K, iters):
+        km_state[K].key_rel.zero_()
+        ops.keyframe_map_match(scans, tab, km_state[K], instance_mask=inst, num_det=num, det_cls=dc, iters=iters,
+                               out=km_out)
     # N7: the track update on the per-person result of these scans.  The same detections every call: after the first
     # one every candidate (score >= 0.5, about half the detections) is matched with its track -- the steady state
     ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out)
@@ -189,6 +200,13 @@ if "person" in which:
               "ok, %d keyframes replaced), both with the %.3f ms memset of key_rel in front"
               % (ms_k1, ms_k16, kf_out.iters_used.float().mean().item(), kf_out.count.float().mean().item(),
                  int(kf_out.ok.sum().item()), B, int(kf_out.key_replaced.sum().item()), ms_z))
+        for K in km_state:
+            ms_k1, ms_k16 = timeit(lambda: keyframe_map(K, 1), iters=50), timeit(lambda: keyframe_map(K, 16), iters=50)
+            print("   keyframe_map_match keys=%d %.3f ms (iters=1) %.3f ms (iters=16: %.1f run per sensor, %.0f points "
+                  "matched, %d of %d ok, %d keyframes stored, %d switches), both with the memset of key_rel in front"
+                  % (K, ms_k1, ms_k16, km_out.iters_used.float().mean().item(), km_out.count.float().mean().item(),
+                     int(km_out.ok.sum().item()), B, int(km_out.key_replaced.sum().item()),
+                     int(km_out.key_switched.sum().item())))
         ms_t = {M: timeit(lambda: track(M), iters=50) for M in tracks}
         print("   track_update (%.0f candidates per scan): %s" % (out.det_valid.sum().item() / B, ", ".join(
             "max_tracks %d: %.3f ms, %.0f live tracks per sensor" % (M, ms_t[M], (tracks[M].track_id > 0).sum().item() / B)

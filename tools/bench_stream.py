@@ -1,5 +1,5 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe]] [--tracks]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
@@ -10,7 +10,9 @@ alternating repeats in one process; with --ego both dead-reckon their pose.
 replayed step against the step that ends in the scan matcher and the pose; with --flow: pose per scan, the flow fit
 and the scan matcher in front of the per-person flow, alternating repeats.
 --ego=keyframe: as --ego=scan_match with the keyframe matcher (ego_motion=dict(method="keyframe")) as one more step
-next to the scan matcher's, so one process gives the bare step, scan_match and keyframe."""
+next to the scan matcher's, so one process gives the bare step, scan_match and keyframe.
+--ego=keyframe_map: as --ego=keyframe with the keyframe map (ego_motion=dict(method="keyframe_map")) as one more step
+next to the keyframe matcher's, so one process gives the bare step, scan_match, keyframe and keyframe_map."""
 import faulthandler, os, sys, time
 faulthandler.dump_traceback_later(90, exit=True)       # a stuck step reports where it is instead of hanging the box
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,6 +29,8 @@ EGO_METHOD = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--ego=")] o
 EGO = any(a == "--ego" or a.startswith("--ego=") for a in sys.argv)
 MATCH = dict(method="scan_match")
 KEYFRAME = dict(method="keyframe")
+KEYFRAME_MAP = dict(method="keyframe_map")
+KEYED = ("keyframe", "keyframe_map")
 TRACKS = "--tracks" in sys.argv
 sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks"))]
 
@@ -52,25 +56,31 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
         poses = np.cumsum(np.random.default_rng(4).normal(0, 0.05, (40, B, 3)), axis=0)
         mk = lambda **kw: StreamingDetector(model, batch=B, nms_min_dist=NMS, flow_model=flow_model, **kw)
         if TRACKS:
-            kw = dict(ego_motion={"scan_match": MATCH, "keyframe": KEYFRAME}.get(EGO_METHOD, dict())) if EGO else {}
+            kw = dict(ego_motion={"scan_match": MATCH, "keyframe": KEYFRAME, "keyframe_map": KEYFRAME_MAP}.get(EGO_METHOD, dict())) if EGO else {}
             plain, tracked = mk(tracks=None, **kw), mk(tracks=dict(), **kw)
             call = (lambda det, t: det(scans[:, t])) if EGO else (lambda det, t: det(scans[:, t], pose=poses[t]))
             steps = {"tracks=None": lambda t: call(plain, t), "tracks": lambda t: call(tracked, t)}
-        elif EGO_METHOD in ("scan_match", "keyframe") and flow_model is None:
+        elif EGO_METHOD in ("scan_match",) + KEYED and flow_model is None:
             bare, matched = mk(), mk(ego_motion=MATCH)
             steps = {"no pose": lambda t: bare(scans[:, t]), "scan_match": lambda t: matched(scans[:, t])}
-            if EGO_METHOD == "keyframe":
+            if EGO_METHOD in KEYED:
                 keyed = mk(ego_motion=KEYFRAME)
                 steps["keyframe"] = lambda t: keyed(scans[:, t])
+            if EGO_METHOD == "keyframe_map":
+                mapped = mk(ego_motion=KEYFRAME_MAP)
+                steps["keyframe_map"] = lambda t: mapped(scans[:, t])
         else:
             posed, ego = mk(), mk(ego_motion=dict())
             steps = {"pose=": lambda t: posed(scans[:, t], pose=poses[t]), "ego_motion": lambda t: ego(scans[:, t])}
-            if EGO_METHOD in ("scan_match", "keyframe"):
+            if EGO_METHOD in ("scan_match",) + KEYED:
                 matched = mk(ego_motion=MATCH)
                 steps["scan_match"] = lambda t: matched(scans[:, t])
-            if EGO_METHOD == "keyframe":
+            if EGO_METHOD in KEYED:
                 keyed = mk(ego_motion=KEYFRAME)
                 steps["keyframe"] = lambda t: keyed(scans[:, t])
+            if EGO_METHOD == "keyframe_map":
+                mapped = mk(ego_motion=KEYFRAME_MAP)
+                steps["keyframe_map"] = lambda t: mapped(scans[:, t])
         for step in steps.values():
             for t in range(8):
                 step(t)
@@ -83,12 +93,17 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
                     step(t)
                 torch.cuda.synchronize()
                 ms[name].append((time.perf_counter() - t0) / 32 * 1e3)
-        if EGO_METHOD == "keyframe" and not TRACKS:
+        if EGO_METHOD == "keyframe_map" and not TRACKS:
+            fits, _ = mapped.ego_motion()
+            print("   keyframe_map at the last scan: iterations %s, matched %s, ok %s, key age %s, slot %s"
+                  % ([f["iters_used"] for f in fits], [f["count"] for f in fits], [f["ok"] for f in fits],
+                     [f["key_age"] for f in fits], [f["key_slot"] for f in fits]))
+        if EGO_METHOD in KEYED and not TRACKS:
             fits, _ = keyed.ego_motion()
             print("   keyframe at the last scan: iterations %s, matched %s, ok %s, key age %s"
                   % ([f["iters_used"] for f in fits], [f["count"] for f in fits], [f["ok"] for f in fits],
                      [f["key_age"] for f in fits]))
-        if EGO_METHOD in ("scan_match", "keyframe") and not TRACKS:
+        if EGO_METHOD in ("scan_match",) + KEYED and not TRACKS:
             fits, _ = matched.ego_motion()
             print("   scan_match at the last scan: iterations %s, matched %s, ok %s"
                   % ([f["iters_used"] for f in fits], [f["count"] for f in fits], [f["ok"] for f in fits]))
