@@ -252,22 +252,7 @@ __global__ void pose_advance_kernel(const double *motion, const uint8_t *ok, dou
     pose[3 * b] = x1;
     pose[3 * b + 1] = y1;
     pose[3 * b + 2] = phi1;
-    if (rot) {
-        double s1, c1;
-        sincos(phi1, &s1, &c1);
-        rot[4 * b] = (float)c1;
-        rot[4 * b + 1] = (float)(-s1);
-        rot[4 * b + 2] = (float)s1;
-        rot[4 * b + 3] = (float)c1;
-    }
-    if (trans) {
-        trans[2 * b] = x1;
-        trans[2 * b + 1] = y1;
-    }
-    if (flow_trans) {
-        flow_trans[2 * b] = dx;
-        flow_trans[2 * b + 1] = dy;
-    }
+    pof_write_pose_terms(b, x1, y1, phi1, dx, dy, rot, trans, flow_trans);
 }
 
 }  // namespace

@@ -60,6 +60,30 @@ __device__ __forceinline__ void pof_rotate_flow_point(double c, double s, T fx_i
     oy = (T)gy;
 }
 
+// The pose terms pof_person_flow reads, of sensor b at the pose (x, y, phi) that this step moved by (dx, dy):
+// rot = R(phi) row-major in float, trans = (x, y), flow_trans = (dx, dy).  A null pointer is skipped.
+// pof_pose_advance and the keyframe kernel both write them here.
+__device__ __forceinline__ void pof_write_pose_terms(int b, double x, double y, double phi, double dx, double dy,
+                                                     float *rot, double *trans, double *flow_trans)
+{
+    if (rot) {
+        double s1, c1;
+        sincos(phi, &s1, &c1);
+        rot[4 * b] = (float)c1;
+        rot[4 * b + 1] = (float)(-s1);
+        rot[4 * b + 2] = (float)s1;
+        rot[4 * b + 3] = (float)c1;
+    }
+    if (trans) {
+        trans[2 * b] = x;
+        trans[2 * b + 1] = y;
+    }
+    if (flow_trans) {
+        flow_trans[2 * b] = dx;
+        flow_trans[2 * b + 1] = dy;
+    }
+}
+
 __device__ __forceinline__ double wave_max_f64(double v)
 {
 #pragma unroll

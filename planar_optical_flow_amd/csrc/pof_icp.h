@@ -1,6 +1,7 @@
-// The point-to-line ICP core of pof_scan_match (N8, scan_match.hip) and pof_keyframe_match (N9, keyframe_match.hip):
-// one copy of every formula.  The two differ in where the search window of a point is centred (a functor, below), in
-// what feeds the start value and in what they do with the result; everything here they share operation for operation.
+// The point-to-line ICP core of pof_scan_match (N8, scan_match.hip) and of pof_keyframe_match and
+// pof_keyframe_map_match (N9 and N10, one kernel in keyframe_match.hip): one copy of every formula.  The two kernels
+// differ in where the search window of a point is centred (a functor, below), in what feeds the start value and in
+// what they do with the result; everything here they share operation for operation.
 // Restated in float64 NumPy by tests/test_scan_match.py (_correspond, _iterate).
 //
 // Reference vertices a_j, current points p_i, gate2 = gate * gate, gap2 = max_gap * max_gap.

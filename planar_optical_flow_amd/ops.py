@@ -1010,6 +1010,20 @@ def _check_fields(tensors, fields, shapes, prefix):
             raise ValueError("%s.%s has the wrong shape" % (prefix, name))
 
 
+def _zeros(cls, fields, shapes, device):
+    """The namedtuple ``cls`` of zero-filled tensors: one per field (name, dtype, ...), of the shape beside it."""
+    return cls(*(torch.zeros(shape, dtype=dt, device=device) for (_, dt, *_), shape in zip(fields, shapes)))
+
+
+def _check_pose_terms(B, rot, trans, flow_trans):
+    """The optional pose terms ``person_flow`` reads, as ``pose_advance`` and the keyframe matchers write them."""
+    if rot is not None and tuple(_dev(rot, torch.float32, "rot").shape) not in ((B, 2, 2), (B, 4)):
+        raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
+    for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
+        if t is not None and tuple(_dev(t, torch.float64, name).shape) != (B, 2):
+            raise ValueError("%s must be [B,2]" % name)
+
+
 def _check_matcher_settings(window, iters, **not_negative):
     """The settings ``scan_match`` and ``keyframe_match`` share; the keywords, in their order, must be >= 0."""
     if not 1 <= int(window) <= 64:
@@ -1034,8 +1048,7 @@ def _ego_motion_shapes(B, N):
 def ego_motion_buffers(B, N, device="cuda"):
     """The six outputs of ``ego_motion`` for B scans of N points, zero-filled, as its ``out=`` (allocate once, before
     a graph capture)."""
-    return EgoMotion(*(torch.zeros(shape, dtype=dt, device=device)
-                       for (_, dt), shape in zip(_EGO_MOTION_OUT, _ego_motion_shapes(B, N))))
+    return _zeros(EgoMotion, _EGO_MOTION_OUT, _ego_motion_shapes(B, N), device)
 
 
 def ego_motion(ranges, tab, flow, *, xy=None, canonical=True, sign=-1, model="rigid", weight=None, instance_mask=None,
@@ -1109,11 +1122,7 @@ def pose_advance(motion, ok, pose, rot=None, trans=None, flow_trans=None):
     B = pose.shape[0] if pose.dim() == 2 else -1
     if tuple(pose.shape) != (B, 3) or tuple(motion.shape) != (B, 3) or tuple(ok.shape) != (B,):
         raise ValueError("motion and pose must be [B,3] and ok [B]")
-    if rot is not None and tuple(_dev(rot, torch.float32, "rot").shape) not in ((B, 2, 2), (B, 4)):
-        raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
-    for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
-        if t is not None and tuple(_dev(t, torch.float64, name).shape) != (B, 2):
-            raise ValueError("%s must be [B,2]" % name)
+    _check_pose_terms(B, rot, trans, flow_trans)
     if B == 0:
         return pose
     with torch.cuda.device(pose.device):
@@ -1136,8 +1145,7 @@ def _scan_match_shapes(B, N):
 def scan_match_buffers(B, N, device="cuda"):
     """The eight outputs of ``scan_match`` for B scan pairs of N points, zero-filled, as its ``out=`` (allocate once,
     before a graph capture)."""
-    return ScanMatch(*(torch.zeros(shape, dtype=dt, device=device)
-                       for (_, dt), shape in zip(_SCAN_MATCH_OUT, _scan_match_shapes(B, N))))
+    return _zeros(ScanMatch, _SCAN_MATCH_OUT, _scan_match_shapes(B, N), device)
 
 
 def scan_match(ranges_prev, ranges_cur, tab, *, init=None, instance_mask=None, num_det=None, det_cls=None,
@@ -1208,31 +1216,80 @@ def _keyframe_out_shapes(B, N):
     return (B, 3), (B,), (B,), (B,), (B,), (B,), (B,), (B, N), (B, N, 2)
 
 
-def keyframe_buffers(B, N, device="cuda"):
-    """The persistent state of ``keyframe_match`` for B sensors of N points: no keyframe yet, the pose at zero
-    (allocate once, before a graph capture).  -> ``KeyframeState``."""
-    return KeyframeState(*(torch.zeros(shape, dtype=dt, device=device)
-                           for (_, dt), shape in zip(_KEYFRAME_STATE, _keyframe_state_shapes(B, N))))
-
-
-def keyframe_match_buffers(B, N, device="cuda"):
-    """The nine outputs of ``keyframe_match``, zero-filled, as its ``out=``."""
-    return KeyframeMatch(*(torch.zeros(shape, dtype=dt, device=device)
-                           for (_, dt), shape in zip(_KEYFRAME_OUT, _keyframe_out_shapes(B, N))))
-
-
-def keyframe_reset(state, pose=None):
-    """Forget the keyframe of every sensor, IN PLACE and without a synchronisation: the next ``keyframe_match`` seeds.
-    pose ([3] or [B,3]): the pose to go on from; zeros by default."""
-    state = KeyframeState(*state)
-    for name in ("key_ranges", "key_pose", "key_rel", "key_valid", "key_age", "key_misses"):
-        getattr(state, name).zero_()
+def _keyframe_reset(state, pose):
+    """Zero every tensor of a keyframe state but ``pose`` (its last field), which takes ``pose`` or zeros."""
+    for t in state[:-1]:
+        t.zero_()
     if pose is None:
         state.pose.zero_()
     else:
         pose = torch.as_tensor(pose, dtype=torch.float64).reshape(-1, 3)
         state.pose.copy_(pose.expand(state.pose.shape[0], 3), non_blocking=True)
     return state
+
+
+def _keyframe_step(entry, state_spec, out_spec, ranges_cur, tab, state, instance_mask, num_det, det_cls, cls_thresh,
+                   max_range, window, gate, max_gap, huber_delta, iters, eps_theta, eps_u, min_pivot, key_dist, key_rot,
+                   min_share, max_misses, out, rot, trans, flow_trans, revisit=None):
+    """``keyframe_match`` (``revisit`` None) and ``keyframe_map_match``: the checks and the call of ``entry``.  A spec
+    is (namedtuple class, field table, shapes function).  With a ring the state's shapes also take K, read off
+    state.key_ranges [B,K,N], and the entry point takes ``revisit`` in front of B and K behind N."""
+    (State, state_fields, state_shapes), (Out, out_fields, out_shapes) = state_spec, out_spec
+    _check_matcher_settings(window, iters, gate=gate, max_gap=max_gap, huber_delta=huber_delta, key_dist=key_dist,
+                            key_rot=key_rot, min_share=min_share)
+    if int(max_misses) < 0:
+        raise ValueError("max_misses must be >= 0")
+    if revisit is not None and not 0.0 <= float(revisit) <= 1.0:
+        raise ValueError("revisit must be in [0, 1]")
+    _nms_gate(instance_mask, num_det, det_cls)
+    ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
+    if ranges_cur.dim() != 2:
+        raise ValueError("ranges_cur must be [B,N]")
+    B, N = ranges_cur.shape
+    dev = ranges_cur.device
+    if N < 1 or _dev(tab, torch.float64, "tab").numel() != 3 * N:
+        raise ValueError("the ranges must be [B,N] matching the angle table")
+    state = State(*state)
+    ring = ()
+    if revisit is not None:
+        if not isinstance(state.key_ranges, torch.Tensor) or state.key_ranges.dim() != 3:
+            raise ValueError("state.key_ranges must be [B,K,N]")
+        ring = (_check_keys(state.key_ranges.shape[1]),)
+    _check_fields(state, state_fields, state_shapes(B, N, *ring), "state")
+    instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
+    if out is None:
+        out = _zeros(Out, out_fields, out_shapes(B, N), dev)
+    else:
+        out = Out(*out)
+        _check_fields(out, out_fields, out_shapes(B, N), "out")
+    _check_pose_terms(B, rot, trans, flow_trans)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call(entry, _ptr(ranges_cur), _ptr(tab), _ptr(instance_mask), _ptr(num_det), _ptr(det_cls),
+                  float(cls_thresh), float(max_range), int(window), float(gate), float(max_gap), float(huber_delta),
+                  int(iters), float(eps_theta), float(eps_u), float(min_pivot), float(key_dist), float(key_rot),
+                  float(min_share), int(max_misses), *(() if revisit is None else (float(revisit),)), B, N, *ring,
+                  *[_ptr(t) for t in state], *[_ptr(t) for t in out], _ptr(rot), _ptr(trans), _ptr(flow_trans),
+                  _stream())
+    return out
+
+
+def keyframe_buffers(B, N, device="cuda"):
+    """The persistent state of ``keyframe_match`` for B sensors of N points: no keyframe yet, the pose at zero
+    (allocate once, before a graph capture).  -> ``KeyframeState``."""
+    return _zeros(KeyframeState, _KEYFRAME_STATE, _keyframe_state_shapes(B, N), device)
+
+
+def keyframe_match_buffers(B, N, device="cuda"):
+    """The nine outputs of ``keyframe_match``, zero-filled, as its ``out=``."""
+    return _zeros(KeyframeMatch, _KEYFRAME_OUT, _keyframe_out_shapes(B, N), device)
+
+
+def keyframe_reset(state, pose=None):
+    """Forget the keyframe of every sensor, IN PLACE and without a synchronisation: the next ``keyframe_match`` seeds.
+    pose ([3] or [B,3]): the pose to go on from; zeros by default."""
+    return _keyframe_reset(KeyframeState(*state), pose)
 
 
 def keyframe_match(ranges_cur, tab, state, *, instance_mask=None, num_det=None, det_cls=None, cls_thresh=0.5,
@@ -1255,40 +1312,10 @@ def keyframe_match(ranges_cur, tab, state, *, instance_mask=None, num_det=None, 
     ``out``: a ``KeyframeMatch`` of preallocated tensors (``keyframe_match_buffers``).  ``rot`` [B,2,2] (or [B,4]) f32,
     ``trans`` [B,2] f64, ``flow_trans`` [B,2] f64: the pose terms ``person_flow`` reads, as ``pose_advance`` writes
     them."""
-    _check_matcher_settings(window, iters, gate=gate, max_gap=max_gap, huber_delta=huber_delta, key_dist=key_dist,
-                            key_rot=key_rot, min_share=min_share)
-    if int(max_misses) < 0:
-        raise ValueError("max_misses must be >= 0")
-    _nms_gate(instance_mask, num_det, det_cls)
-    ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
-    if ranges_cur.dim() != 2:
-        raise ValueError("ranges_cur must be [B,N]")
-    B, N = ranges_cur.shape
-    dev = ranges_cur.device
-    if N < 1 or _dev(tab, torch.float64, "tab").numel() != 3 * N:
-        raise ValueError("the ranges must be [B,N] matching the angle table")
-    state = KeyframeState(*state)
-    _check_fields(state, _KEYFRAME_STATE, _keyframe_state_shapes(B, N), "state")
-    instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
-    if out is None:
-        out = keyframe_match_buffers(B, N, dev)
-    else:
-        out = KeyframeMatch(*out)
-        _check_fields(out, _KEYFRAME_OUT, _keyframe_out_shapes(B, N), "out")
-    if rot is not None and tuple(_dev(rot, torch.float32, "rot").shape) not in ((B, 2, 2), (B, 4)):
-        raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
-    for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
-        if t is not None and tuple(_dev(t, torch.float64, name).shape) != (B, 2):
-            raise ValueError("%s must be [B,2]" % name)
-    if B == 0:
-        return out
-    with torch.cuda.device(dev):
-        _lib.call("pof_keyframe_match", _ptr(ranges_cur), _ptr(tab), _ptr(instance_mask), _ptr(num_det), _ptr(det_cls),
-                  float(cls_thresh), float(max_range), int(window), float(gate), float(max_gap), float(huber_delta),
-                  int(iters), float(eps_theta), float(eps_u), float(min_pivot), float(key_dist), float(key_rot),
-                  float(min_share), int(max_misses), B, N, *[_ptr(t) for t in state], *[_ptr(t) for t in out],
-                  _ptr(rot), _ptr(trans), _ptr(flow_trans), _stream())
-    return out
+    return _keyframe_step("pof_keyframe_match", (KeyframeState, _KEYFRAME_STATE, _keyframe_state_shapes),
+                          (KeyframeMatch, _KEYFRAME_OUT, _keyframe_out_shapes), ranges_cur, tab, state, instance_mask,
+                          num_det, det_cls, cls_thresh, max_range, window, gate, max_gap, huber_delta, iters, eps_theta,
+                          eps_u, min_pivot, key_dist, key_rot, min_share, max_misses, out, rot, trans, flow_trans)
 
 
 KeyframeMapState = collections.namedtuple("KeyframeMapState", ("key_ranges", "key_pose", "key_valid", "key_stamp",
@@ -1325,30 +1352,19 @@ def keyframe_map_buffers(B, N, keys=16, device="cuda"):
     """The persistent state of ``keyframe_map_match`` for B sensors of N points and a ring of ``keys`` (1..64)
     keyframes each: no keyframe yet, slot 0 active, the pose at zero (allocate once, before a graph capture).
     -> ``KeyframeMapState``."""
-    keys = _check_keys(keys)
-    return KeyframeMapState(*(torch.zeros(shape, dtype=dt, device=device)
-                              for (_, dt), shape in zip(_KEYFRAME_MAP_STATE, _keyframe_map_state_shapes(B, N, keys))))
+    return _zeros(KeyframeMapState, _KEYFRAME_MAP_STATE, _keyframe_map_state_shapes(B, N, _check_keys(keys)), device)
 
 
 def keyframe_map_match_buffers(B, N, device="cuda"):
     """The eleven outputs of ``keyframe_map_match``, zero-filled, as its ``out=``."""
-    return KeyframeMapMatch(*(torch.zeros(shape, dtype=dt, device=device)
-                              for (_, dt), shape in zip(_KEYFRAME_MAP_OUT, _keyframe_map_out_shapes(B, N))))
+    return _zeros(KeyframeMapMatch, _KEYFRAME_MAP_OUT, _keyframe_map_out_shapes(B, N), device)
 
 
 def keyframe_map_reset(state, pose=None):
     """Forget every keyframe of every sensor, IN PLACE and without a synchronisation: slot 0 is active, the scan
     counter restarts and the next ``keyframe_map_match`` seeds.  pose ([3] or [B,3]): the pose to go on from; zeros by
     default."""
-    state = KeyframeMapState(*state)
-    for t in state[:-1]:
-        t.zero_()
-    if pose is None:
-        state.pose.zero_()
-    else:
-        pose = torch.as_tensor(pose, dtype=torch.float64).reshape(-1, 3)
-        state.pose.copy_(pose.expand(state.pose.shape[0], 3), non_blocking=True)
-    return state
+    return _keyframe_reset(KeyframeMapState(*state), pose)
 
 
 def keyframe_map_match(ranges_cur, tab, state, *, instance_mask=None, num_det=None, det_cls=None, cls_thresh=0.5,
@@ -1368,46 +1384,12 @@ def keyframe_map_match(ranges_cur, tab, state, *, instance_mask=None, num_det=No
     -> ``KeyframeMapMatch``: the outputs of ``keyframe_match`` and key_switched [B] u8, key_slot [B] i32 (the active
     slot after the step).  ``out``: a ``KeyframeMapMatch`` of preallocated tensors (``keyframe_map_match_buffers``);
     ``rot``, ``trans``, ``flow_trans`` as ``keyframe_match``."""
-    _check_matcher_settings(window, iters, gate=gate, max_gap=max_gap, huber_delta=huber_delta, key_dist=key_dist,
-                            key_rot=key_rot, min_share=min_share)
-    if int(max_misses) < 0:
-        raise ValueError("max_misses must be >= 0")
-    if not 0.0 <= float(revisit) <= 1.0:
-        raise ValueError("revisit must be in [0, 1]")
-    _nms_gate(instance_mask, num_det, det_cls)
-    ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
-    if ranges_cur.dim() != 2:
-        raise ValueError("ranges_cur must be [B,N]")
-    B, N = ranges_cur.shape
-    dev = ranges_cur.device
-    if N < 1 or _dev(tab, torch.float64, "tab").numel() != 3 * N:
-        raise ValueError("the ranges must be [B,N] matching the angle table")
-    state = KeyframeMapState(*state)
-    if not isinstance(state.key_ranges, torch.Tensor) or state.key_ranges.dim() != 3:
-        raise ValueError("state.key_ranges must be [B,K,N]")
-    K = _check_keys(state.key_ranges.shape[1])
-    _check_fields(state, _KEYFRAME_MAP_STATE, _keyframe_map_state_shapes(B, N, K), "state")
-    instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
-    if out is None:
-        out = keyframe_map_match_buffers(B, N, dev)
-    else:
-        out = KeyframeMapMatch(*out)
-        _check_fields(out, _KEYFRAME_MAP_OUT, _keyframe_map_out_shapes(B, N), "out")
-    if rot is not None and tuple(_dev(rot, torch.float32, "rot").shape) not in ((B, 2, 2), (B, 4)):
-        raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
-    for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
-        if t is not None and tuple(_dev(t, torch.float64, name).shape) != (B, 2):
-            raise ValueError("%s must be [B,2]" % name)
-    if B == 0:
-        return out
-    with torch.cuda.device(dev):
-        _lib.call("pof_keyframe_map_match", _ptr(ranges_cur), _ptr(tab), _ptr(instance_mask), _ptr(num_det),
-                  _ptr(det_cls), float(cls_thresh), float(max_range), int(window), float(gate), float(max_gap),
-                  float(huber_delta), int(iters), float(eps_theta), float(eps_u), float(min_pivot), float(key_dist),
-                  float(key_rot), float(min_share), int(max_misses), float(revisit), B, N, K,
-                  *[_ptr(t) for t in state], *[_ptr(t) for t in out], _ptr(rot), _ptr(trans), _ptr(flow_trans),
-                  _stream())
-    return out
+    return _keyframe_step("pof_keyframe_map_match",
+                          (KeyframeMapState, _KEYFRAME_MAP_STATE, _keyframe_map_state_shapes),
+                          (KeyframeMapMatch, _KEYFRAME_MAP_OUT, _keyframe_map_out_shapes), ranges_cur, tab, state,
+                          instance_mask, num_det, det_cls, cls_thresh, max_range, window, gate, max_gap, huber_delta,
+                          iters, eps_theta, eps_u, min_pivot, key_dist, key_rot, min_share, max_misses, out, rot, trans,
+                          flow_trans, revisit=revisit)
 
 
 TrackState = collections.namedtuple("TrackState", ("track_id", "track_state", "track_cov", "track_hits", "track_misses",

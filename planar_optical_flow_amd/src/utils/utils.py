@@ -475,6 +475,10 @@ class KeyframeOdometry:
     key_pose [3], corr [N] and flow_residual [N,2]."""
 
     def __init__(self, scan_phi, **kw):
+        self._setup(scan_phi, kw)
+        self._state = ops.keyframe_buffers(1, self._n, self._tab.device)
+
+    def _setup(self, scan_phi, kw):
         self._tab = _table_for(scan_phi)
         self._n = self._tab.numel() // 3
         self._min_dist = kw.pop("min_dist", 0.5)
@@ -484,12 +488,17 @@ class KeyframeOdometry:
         if unknown:
             raise ValueError("unknown keyframe settings: %s" % sorted(unknown))
         self._kw = kw
-        self._state = ops.keyframe_buffers(1, self._n, self._tab.device)
+
+    _reset, _match = staticmethod(ops.keyframe_reset), staticmethod(ops.keyframe_match)
 
     def reset(self, pose=None):
-        ops.keyframe_reset(self._state, pose)
+        self._reset(self._state, pose)
 
     def update(self, scan, pred_cls=None, pred_reg=None):
+        return self._step(scan, pred_cls, pred_reg)[1]
+
+    def _step(self, scan, pred_cls, pred_reg):
+        """-> the outputs on the device and the dict ``KeyframeOdometry.update`` returns."""
         cur = _to_dev(scan, torch.float32).reshape(1, -1)
         gate = {}
         if pred_cls is not None and pred_reg is not None:
@@ -499,18 +508,18 @@ class KeyframeOdometry:
                                                         _to_dev(pred_reg, torch.float64).reshape(1, -1, 2),
                                                         self._min_dist)
             gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
-        res = ops.keyframe_match(cur, self._tab, self._state, **gate, **self._kw)
+        res = self._match(cur, self._tab, self._state, **gate, **self._kw)
         host = lambda t: t[0].cpu().numpy()
         s = self._state
-        return {"pose": host(s.pose), "motion": host(res.motion), "ok": bool(res.ok[0].item()),
-                "count": int(res.count[0].item()), "rms": float(res.rms[0].item()),
-                "iters_used": int(res.iters_used[0].item()), "obs": float(res.obs[0].item()),
-                "key_replaced": bool(res.key_replaced[0].item()), "key_age": int(s.key_age[0].item()),
-                "key_misses": int(s.key_misses[0].item()), "key_pose": host(s.key_pose), "corr": host(res.corr),
-                "flow_residual": host(res.flow_residual)}
+        return res, {"pose": host(s.pose), "motion": host(res.motion), "ok": bool(res.ok[0].item()),
+                     "count": int(res.count[0].item()), "rms": float(res.rms[0].item()),
+                     "iters_used": int(res.iters_used[0].item()), "obs": float(res.obs[0].item()),
+                     "key_replaced": bool(res.key_replaced[0].item()), "key_age": int(s.key_age[0].item()),
+                     "key_misses": int(s.key_misses[0].item()), "key_pose": host(s.key_pose), "corr": host(res.corr),
+                     "flow_residual": host(res.flow_residual)}
 
 
-class KeyframeMapOdometry:
+class KeyframeMapOdometry(KeyframeOdometry):
     """``KeyframeOdometry`` with a ring of ``keys`` keyframes (``ops.keyframe_map_match``, one launch per scan): a
     sensor that comes back to a place it has a keyframe of switches to that keyframe, and the next match re-anchors
     the pose on it -- the drift of the way round is dropped.  ``odo = KeyframeMapOdometry(scan_phi, keys=16,
@@ -521,43 +530,20 @@ class KeyframeMapOdometry:
     slot's) with key_switched (bool) and key_slot, the active slot after the step."""
 
     def __init__(self, scan_phi, keys=16, revisit=0.5, **kw):
-        self._tab = _table_for(scan_phi)
-        self._n = self._tab.numel() // 3
-        self._min_dist = kw.pop("min_dist", 0.5)
-        known = {"cls_thresh", "max_range", "window", "gate", "max_gap", "huber_delta", "iters", "eps_theta", "eps_u",
-                 "min_pivot", "key_dist", "key_rot", "min_share", "max_misses"}
-        unknown = set(kw) - known
-        if unknown:
-            raise ValueError("unknown keyframe settings: %s" % sorted(unknown))
+        self._setup(scan_phi, kw)
         if not 0.0 <= float(revisit) <= 1.0:
             raise ValueError("revisit must be in [0, 1]")
         self._kw = dict(kw, revisit=float(revisit))
         self._state = ops.keyframe_map_buffers(1, self._n, keys, self._tab.device)
 
-    def reset(self, pose=None):
-        ops.keyframe_map_reset(self._state, pose)
+    _reset, _match = staticmethod(ops.keyframe_map_reset), staticmethod(ops.keyframe_map_match)
 
     def update(self, scan, pred_cls=None, pred_reg=None):
-        cur = _to_dev(scan, torch.float32).reshape(1, -1)
-        gate = {}
-        if pred_cls is not None and pred_reg is not None:
-            pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
-            assert pc.ndim == 2 and pc.shape[1] == 1
-            _, dc, num, inst = ops.nms_predicted_center(cur, self._tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
-                                                        _to_dev(pred_reg, torch.float64).reshape(1, -1, 2),
-                                                        self._min_dist)
-            gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
-        res = ops.keyframe_map_match(cur, self._tab, self._state, **gate, **self._kw)
-        host = lambda t: t[0].cpu().numpy()
-        s = self._state
+        res, d = self._step(scan, pred_cls, pred_reg)
         slot = int(res.key_slot[0].item())
-        return {"pose": host(s.pose), "motion": host(res.motion), "ok": bool(res.ok[0].item()),
-                "count": int(res.count[0].item()), "rms": float(res.rms[0].item()),
-                "iters_used": int(res.iters_used[0].item()), "obs": float(res.obs[0].item()),
-                "key_replaced": bool(res.key_replaced[0].item()), "key_switched": bool(res.key_switched[0].item()),
-                "key_slot": slot, "key_age": int(s.key_age[0].item()), "key_misses": int(s.key_misses[0].item()),
-                "key_pose": s.key_pose[0, slot].cpu().numpy(), "corr": host(res.corr),
-                "flow_residual": host(res.flow_residual)}
+        d.update(key_switched=bool(res.key_switched[0].item()), key_slot=slot,
+                 key_pose=self._state.key_pose[0, slot].cpu().numpy())
+        return d
 
 
 def _pose_terms(odom1, odom0=None, batch=1):

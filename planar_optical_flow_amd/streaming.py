@@ -169,26 +169,24 @@ class StreamingDetector:
                 self._have_prev = self._have_flow = False
             self._match_out = ops.scan_match_buffers(self.B, self.N, dev)
             self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
-        if method == "keyframe":
-            self._key_kw = _ego_settings(ego_motion, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16,
-                                         eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, max_range=20.0,
-                                         cls_thresh=self._cls_thresh, key_dist=0.3, key_rot=0.3, min_share=0.5,
-                                         max_misses=2)
-            # the keyframe, its bookkeeping and the pose live on the device, allocated before any capture
-            self._key_state = ops.keyframe_buffers(self.B, self.N, dev)
-            self._key_out = ops.keyframe_match_buffers(self.B, self.N, dev)
-            self._pose_state = self._key_state.pose
-            self._key_seen = False
         self._key_map = method == "keyframe_map"
-        if self._key_map:
+        if method == "keyframe" or self._key_map:
             kw = _ego_settings(ego_motion, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16,
                                eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, max_range=20.0, cls_thresh=self._cls_thresh,
-                               key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2, keys=16, revisit=0.5)
-            # the ring of keyframes, its bookkeeping and the pose live on the device, allocated before any capture
-            self._key_state = ops.keyframe_map_buffers(self.B, self.N, kw.pop("keys"), dev)
-            self._key_out = ops.keyframe_map_match_buffers(self.B, self.N, dev)
-            if not 0.0 <= float(kw["revisit"]) <= 1.0:
-                raise ValueError("revisit must be in [0, 1]")
+                               key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2,
+                               **(dict(keys=16, revisit=0.5) if self._key_map else {}))
+            # the keyframe (or the ring of them), its bookkeeping and the pose live on the device, allocated before
+            # any capture
+            if self._key_map:
+                self._key_state = ops.keyframe_map_buffers(self.B, self.N, kw.pop("keys"), dev)
+                self._key_out = ops.keyframe_map_match_buffers(self.B, self.N, dev)
+                if not 0.0 <= float(kw["revisit"]) <= 1.0:
+                    raise ValueError("revisit must be in [0, 1]")
+                self._key_match, self._key_reset = ops.keyframe_map_match, ops.keyframe_map_reset
+            else:
+                self._key_state = ops.keyframe_buffers(self.B, self.N, dev)
+                self._key_out = ops.keyframe_match_buffers(self.B, self.N, dev)
+                self._key_match, self._key_reset = ops.keyframe_match, ops.keyframe_reset
             self._key_kw = kw
             self._pose_state = self._key_state.pose
             self._key_seen = False
@@ -220,7 +218,7 @@ class StreamingDetector:
             self._match_out.motion.zero_()            # the first pair of a sequence starts from rest
         if self._key_kw is not None:
             # the next scan becomes the keyframe
-            (ops.keyframe_map_reset if self._key_map else ops.keyframe_reset)(self._key_state)
+            self._key_reset(self._key_state)
             self._key_seen = False
         if self._dead_reckons():
             start = np.zeros((self.B, 3)) if pose is None else np.broadcast_to(
@@ -313,8 +311,7 @@ class StreamingDetector:
         terms = {}
         if self._flow_model is not None:
             terms = dict(rot=self._pose_rot, trans=self._pose_trans, flow_trans=self._pose_flow_trans)
-        match = ops.keyframe_map_match if self._key_map else ops.keyframe_match
-        match(self._scan[:, 0], self.tab, self._key_state, out=self._key_out, **gate, **terms, **self._key_kw)
+        self._key_match(self._scan[:, 0], self.tab, self._key_state, out=self._key_out, **gate, **terms, **self._key_kw)
 
     def _pose_views(self, buf):
         nb = self.B
@@ -456,25 +453,17 @@ class StreamingDetector:
             if not self._key_seen:
                 raise RuntimeError("feed the detector a scan first")
             o, s = self._key_out, self._key_state
-            if self._key_map:
-                host = {k: t.cpu().numpy() for k, t in (("motion", o.motion), ("ok", o.ok), ("count", o.count),
-                                                        ("rms", o.rms), ("iters_used", o.iters_used), ("obs", o.obs),
-                                                        ("pose", s.pose), ("key_replaced", o.key_replaced),
-                                                        ("key_age", s.key_age), ("key_pose", s.key_pose),
-                                                        ("key_switched", o.key_switched), ("key_slot", o.key_slot))}
-                return [{"motion": host["motion"][b], "ok": bool(host["ok"][b]), "count": int(host["count"][b]),
-                         "rms": float(host["rms"][b]), "iters_used": int(host["iters_used"][b]),
-                         "obs": float(host["obs"][b]), "pose": host["pose"][b],
-                         "key_replaced": bool(host["key_replaced"][b]), "key_age": int(host["key_age"][b]),
-                         "key_pose": host["key_pose"][b, host["key_slot"][b]],
-                         "key_switched": bool(host["key_switched"][b]), "key_slot": int(host["key_slot"][b])}
-                        for b in range(self.B)], o
             host = [t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, o.iters_used, o.obs, s.pose,
                                               o.key_replaced, s.key_age, s.key_pose)]
-            return [{"motion": host[0][b], "ok": bool(host[1][b]), "count": int(host[2][b]), "rms": float(host[3][b]),
+            fits = [{"motion": host[0][b], "ok": bool(host[1][b]), "count": int(host[2][b]), "rms": float(host[3][b]),
                      "iters_used": int(host[4][b]), "obs": float(host[5][b]), "pose": host[6][b],
                      "key_replaced": bool(host[7][b]), "key_age": int(host[8][b]), "key_pose": host[9][b]}
-                    for b in range(self.B)], o
+                    for b in range(self.B)]
+            if self._key_map:
+                switched, slot = o.key_switched.cpu().numpy(), o.key_slot.cpu().numpy()
+                for b, fit in enumerate(fits):
+                    fit.update(key_pose=host[9][b, slot[b]], key_switched=bool(switched[b]), key_slot=int(slot[b]))
+            return fits, o
         if not self._dead_reckons() or not self._have_flow:
             raise RuntimeError("construct the detector with ego_motion and feed it two scans of a sequence first")
         if self._match_kw is not None:
