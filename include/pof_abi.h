@@ -764,7 +764,7 @@ int pof_conv1d_bn_lrelu(const float *x, const float *wt, const float *scale, con
 
 /* No device work (no HIP call at all: it answers on a machine without a GPU).  The kernel form
  * pof_conv3_bn_lrelu (kernel_size 3, stride 1), pof_conv1d_bn_lrelu or, with fused_first != 0,
- * pof_conv3_first_two (Ci = C1) would launch for these sizes, POF_CONV_CT included: split_k (1: the
+ * pof_conv3_first_two (Ci = C1) would launch for these sizes: split_k (1: the
  * four waves of a workgroup share one column tile and split the K loop), channels_per_workgroup (32,
  * 64 or 128), both of the first launch; launches (sequences go in chunks of < 2^30 input elements,
  * and a smaller last chunk may take a narrower form); wide_offsets = how many launches write at

@@ -21,7 +21,6 @@
 //   * epilogue: y = acc * scale[co] + shift[co] (BatchNorm folded with the conv bias), LeakyReLU,
 //     optional max over position pairs (adjacent lanes), store.
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "pof_common.h"
@@ -505,8 +504,6 @@ int conv_form(int S, int Ci, int Co, int Lc, int kernel, int stride, bool fused,
     // batch: 256 -> 256 L = 14 0.234 -> 0.218 ms, 512 -> 256 L = 14 0.425 -> 0.390, 256 -> 128 L = 28 0.214 -> 0.195),
     // at equal summation order
     if (ct == 4 && gx * ((Co + 127) / 128) < 8 * kCvFillWorkgroups) ct = 2;
-    { static const int force = [] { const char *e = getenv("POF_CONV_CT"); return e ? atoi(e) : 0; }();
-      if (force == 1 || force == 2 || force == 4) ct = (Co <= 32 && force > 1) ? 1 : (Co <= 64 && force > 2) ? 2 : force; }
     const long long wgs = gx * ((Co + 32 * ct - 1) / (32 * ct));
     const int nchunk = (Ci + kCvCC - 1) / kCvCC;
     if (!fused && kernel == 3 && stride == 1 && wgs < 2 * kCvFillWorkgroups && Ci >= Co && nchunk >= 8 * kCvWaves &&

@@ -22,8 +22,6 @@
 //               outputs, the range rows sit in LDS (loaded into registers at
 //               kernel entry, their latency hidden behind phase A), floor/ratio
 //               use trunc + v_fract (exact in range), np.clip is compare + select.
-#include <cstdlib>
-#include <string>
 #include <type_traits>
 
 #include "pof_common.h"
@@ -187,11 +185,9 @@ __device__ __forceinline__ float finish_value(const CutArgs &a, double ct, doubl
 //               centre arithmetic runs in float32 (|error| <= 1e-5 in the normalised output;
 //               saturated samples are exactly +-1).  Opt-in (value_mode = 1).
 //   DBG      also write the inds_ct_low debug tensor (tests only)
-#ifndef POF_CUTOUT_MINWG
-#define POF_CUTOUT_MINWG 4      // workgroups per CU the register allocation is held to (tools: experimental builds)
-#endif
+constexpr int kMinWorkgroups = 4;   // workgroups per CU the register allocation is held to
 template <int LDSMODE, int P4, int VMODE, bool DBG>
-__global__ __launch_bounds__(kThreads, POF_CUTOUT_MINWG) void cutout_kernel(CutArgs a)
+__global__ __launch_bounds__(kThreads, kMinWorkgroups) void cutout_kernel(CutArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int cap = a.fixed ? a.tile * a.T : a.tile;
@@ -790,17 +786,7 @@ int cutout_launch(const float *scans, int B, int T, int N, const double *tab, in
     a.out = out32; a.out16 = out16; a.s_area = area_mode ? workspace : nullptr; a.dbg_lo = dbg_lo;
     hipStream_t s = pof_stream(stream);
     if (area_mode) {
-        // POF_CUTOUT_CLEAR=memset restores round 1's hipMemsetAsync node -- for tools/diag_graph_dump.py only, which
-        // captures and dumps the streaming step in that form WITHOUT replaying it
-        static const bool memset_form = [] {
-            const char *e = std::getenv("POF_CUTOUT_CLEAR");
-            return e && std::string(e) == "memset";
-        }();
-        if (memset_form) {
-            if (hipMemsetAsync(workspace, 0, sizeof(int32_t) * (size_t)B, s) != hipSuccess) return POF_E_LAUNCH;
-        } else {
-            clear_area_kernel<<<(B + 255) / 256, 256, 0, s>>>(workspace, B);
-        }
+        clear_area_kernel<<<(B + 255) / 256, 256, 0, s>>>(workspace, B);
         POF_CHECK_LAUNCH();
         const int windows = (fixed ? T : 1) * a.Ns;
         int chunks = (windows + kThreads - 1) / kThreads;
@@ -825,8 +811,7 @@ int cutout_launch(const float *scans, int B, int T, int N, const double *tab, in
     // 16-byte float4 stores / 8-byte half4 stores both need P % 4 == 0 and an aligned base
     const bool vec4 = (num_cutout_pts % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
     // pair rows (see cutout_kernel): the reference's configuration -- centred output, power-of-two depth, exact values
-    static const bool pair_off = [] { const char *e = std::getenv("POF_CUTOUT_PAIR"); return e && atoi(e) == 0; }();
-    const bool pair = rows_in_lds && centered && a.depth_pow2 && value_mode == 0 && !dbg_lo && !pair_off &&
+    const bool pair = rows_in_lds && centered && a.depth_pow2 && value_mode == 0 && !dbg_lo &&
                       tbl + 2 * row_bytes <= 64 * 1024;
     if (pair) { launch_cutout<3>(a, grid, tbl + 2 * row_bytes, s, vec4); POF_CHECK_LAUNCH(); return POF_OK; }
     if (rows_in_lds) launch_cutout<1>(a, grid, lds, s, vec4);

@@ -12,7 +12,6 @@
 // the association): two orders of magnitude below the float64 vector peak at
 // the HBM rate, so nothing here is worth MFMA.
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 #include "pof_common.h"
@@ -20,6 +19,12 @@
 namespace {
 
 constexpr int kThreads = 256;
+// The flat kernel (scan_flat_kernel): threads per workgroup and 128-point runs per wave.  Measured and settled
+// (DESIGN.md section 3.1); the kernel keeps its loops over the one run because without them the compiler schedules
+// the same instructions differently.
+constexpr int kFlatThreads = 128;
+constexpr int kFlatRuns = 1;
+constexpr int kFlatPairs = 64 * kFlatRuns;   // pairs of points per wave-chunk
 
 __global__ void laser_phi_kernel(double start, double stop, double step, int n, double *tab)
 {
@@ -266,23 +271,6 @@ __device__ __forceinline__ void params_sincos(double x, double *sn, double *cs)
     *cs = cc;
 }
 
-// AP: pointer to the arguments -- a plain pointer to a by-value kernel argument, or a constant-address-space
-// pointer into the kernel-argument segment (slot chosen at run time, scan_flat_kernel)
-template <typename AP>
-__device__ __forceinline__ void det_entry(AP a, int g, double *w)
-{
-    const double dr = a->det_rphi[2 * g], dp = a->det_rphi[2 * g + 1];
-    double s, c;
-    sincos(dp, &s, &c);
-    const int cl = a->det_cls[g];
-    w[0] = dr * c;
-    w[1] = dr * s;
-    w[2] = cl == 0 ? a->ra0 : (cl == 1 ? a->ra1 : a->ra2);
-    w[3] = cl == 0 ? a->sd0 : (cl == 1 ? a->sd1 : a->sd2);   // dist <= dyn radius   <=>  s <= w[3]
-    w[4] = (double)(cl == 0 ? a->lb0 : (cl == 1 ? a->lb1 : a->lb2));
-    w[5] = cl == 0 ? a->sa0 : (cl == 1 ? a->sa1 : a->sa2);   // dist <  assoc radius <=>  s <= w[5]
-}
-
 // float32 screen of the flat kernel (flat_run).  For a detection j the kernel tracks
 //   dd_j = fl(ex*ex + fl(ey*ey - sd_j))     ex, ey = float32 point - float32 centre, sd_j rounded to float32
 // and keeps the minimum over the sample's inline detections.  With all coordinates below 100 m and sd <= 400 m^2,
@@ -300,9 +288,8 @@ __device__ __forceinline__ bool det_is_far(double cx, double cy, double sd)
 }
 
 // number of params jobs of a batch: kInline (8) lanes per sample
-__host__ __device__ inline int params_job_count(int B, bool have_dets)
+__host__ __device__ inline int params_job_count(int B)
 {
-    (void)have_dets;
     return kInline * B;
 }
 
@@ -320,6 +307,8 @@ __host__ __device__ inline int params_job_count(int B, bool have_dets)
 // motion as 16-byte stores: ~11 store instructions per wave of 8 samples, <= 8 lines each.  WRITE_F64: also the
 // float64 part that only the per-sample kernels read (the flat kernel needs the 384-byte image and, for crowded
 // samples, the CSR table).
+// AP: pointer to the arguments -- a plain pointer to a by-value kernel argument, or a constant-address-space
+// pointer into the kernel-argument segment (slot chosen at run time, scan_flat_kernel)
 template <bool FALLBACK, bool WRITE_F64, typename AP>
 __device__ __forceinline__ void params_work(AP a, int t)
 {
@@ -748,7 +737,7 @@ __device__ __forceinline__ void scan_main(const PreArgs &a, const int block_y)
 // 128-byte line between two workgroups on different XCDs, and the bare I/O shape of the launch runs at
 // 4.6-4.9 TB/s; with line-aligned 1024-byte (flow / reg / cls) and 512-byte (mask) runs per wave the same
 // bytes stream at 6.2-6.3 TB/s (tools/ubench/store_ceiling.hip, profiles/r2_store_*).
-// A wave touches at most two samples (N >= 128 * CPW): it copies the float32 part of their records (motion,
+// A wave touches at most two samples (N >= 128): it copies the float32 part of their records (motion,
 // screen of the inline detections) and the float64 centres into its OWN slice of LDS -- no workgroup barrier,
 // LDS operations of one wave are ordered -- and each lane picks its own sample's.  Crowded samples (more than
 // kInline detections) read the rest of their detections from the CSR table in the workspace (exact test only).
@@ -1144,7 +1133,7 @@ __device__ __forceinline__ void flat_run(const FlatArgs &L, const FlatBatch &bt,
     }
 }
 
-// grid = main_blocks (THREADS / 64 wave-chunks each, CPW runs of 128 points per wave-chunk) + the blocks that
+// grid = main_blocks (kFlatThreads / 64 wave-chunks each, kFlatRuns runs of 128 points per wave-chunk) + the blocks that
 // run the params jobs of the NEXT batches (chained form; params blocks last: dispatched first, their long
 // sincos chains would hold the slots the streaming waves need)
 // A slot of an array inside the kernel arguments, chosen at run time: indexing the by-value argument itself makes
@@ -1164,10 +1153,10 @@ __device__ __forceinline__ S kernarg_struct(kernarg_ptr p)
 }
 constexpr size_t kFlatArgsKernargBytes = (sizeof(FlatArgs) + 7) & ~(size_t)7;   // offset of the second argument
 
-template <typename OutT, int CFG, int THREADS, int CPW>
-__global__ __launch_bounds__(THREADS, 8) void scan_flat_kernel(const FlatArgs L, const ParamsMulti P)
+template <typename OutT, int CFG>
+__global__ __launch_bounds__(kFlatThreads, 8) void scan_flat_kernel(const FlatArgs L, const ParamsMulti P)
 {
-    constexpr int WAVES = THREADS / 64;
+    constexpr int WAVES = kFlatThreads / 64;
     __shared__ __align__(16) unsigned char smem[WAVES][kWaveLds];
     kernarg_ptr ka = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
     // Role of this block.  The params blocks (P.total of them) sit at block indices [P.first, P.first + P.total):
@@ -1177,7 +1166,6 @@ __global__ __launch_bounds__(THREADS, 8) void scan_flat_kernel(const FlatArgs L,
     int sblock = (int)blockIdx.x;
     if (sblock >= P.first) {
         if (sblock < P.first + P.total) {
-#ifndef POF_FLAT_NO_PARAMS
             // a params block belongs to ONE batch (uniform slot index -> scalar loads of its arguments)
             const int blk = sblock - P.first;
             int k = 0, b0 = P.blk0[0];
@@ -1193,8 +1181,7 @@ __global__ __launch_bounds__(THREADS, 8) void scan_flat_kernel(const FlatArgs L,
             }
             const auto *pa = reinterpret_cast<const __attribute__((address_space(4))) PreArgs *>(
                 ka + kFlatArgsKernargBytes + offsetof(ParamsMulti, p) + (size_t)k * sizeof(PreArgs));
-            params_work<false, false>(pa, (blk - b0) * THREADS + (int)threadIdx.x);   // jobs past the batch's count do nothing
-#endif
+            params_work<false, false>(pa, (blk - b0) * kFlatThreads + (int)threadIdx.x);   // jobs past the batch's count do nothing
             return;
         }
         sblock -= P.total;
@@ -1219,16 +1206,16 @@ __global__ __launch_bounds__(THREADS, 8) void scan_flat_kernel(const FlatArgs L,
     const FlatCfg<CFG> cfg{L.flags};
     unsigned char *lds = smem[wv];
 
-    // pairs [p0, p0 + 64 * CPW) of the batch's flat pair axis
-    const unsigned p0 = (unsigned)(w - bt.wave0) * (64u * CPW);
+    // pairs [p0, p0 + kFlatPairs) of the batch's flat pair axis
+    const unsigned p0 = (unsigned)(w - bt.wave0) * (unsigned)kFlatPairs;
     const int sA = (int)(__umulhi(p0, L.magic_m) >> L.magic_s);      // p0 / halfN
     const int l0 = (int)(p0 - (unsigned)sA * (unsigned)L.halfN);
 
     // run c starts 64 * c pairs further; addressed relative to sA (a run that begins in sA + 1 already has q = 1
-    // in every lane; it cannot reach sA + 2: N >= 128 * CPW)
-    RunLoads in[CPW];
+    // in every lane; it cannot reach sA + 2: N >= 128 * kFlatRuns)
+    RunLoads in[kFlatRuns];
 #pragma unroll
-    for (int c = 0; c < CPW; ++c) in[c] = flat_loads<OutT>(L, bt, lane, sA, l0 + 64 * c);
+    for (int c = 0; c < kFlatRuns; ++c) in[c] = flat_loads<OutT>(L, bt, lane, sA, l0 + 64 * c);
 
     if (cfg.has(kOutFlow) || cfg.has(kHasDets)) {
         // flat images of samples sA and sA + 1 -> this wave's LDS slice, a plain copy of 2 x 384 contiguous
@@ -1247,7 +1234,7 @@ __global__ __launch_bounds__(THREADS, 8) void scan_flat_kernel(const FlatArgs L,
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 #pragma unroll
-    for (int c = 0; c < CPW; ++c)
+    for (int c = 0; c < kFlatRuns; ++c)
         flat_run<OutT, CFG>(L, bt, cfg, lds, lane, sA, l0 + 64 * c, (long long)p0 + 64 * c, in[c]);
 }
 
@@ -1458,31 +1445,6 @@ float f32_round_up(double v)
     return f;
 }
 
-// tuning knobs of the flat kernel, POF_FLAT_TUNE="threads,cpw[,ppos]": threads per workgroup, 128-point runs per
-// wave, position of the params blocks in the grid in percent of the streaming blocks (0 first ... 100 last)
-void flat_tuning(int *threads, int *cpw, int *ppos)
-{
-    static int t = 0, c = 0, pp = 0;
-    if (t == 0) {
-        int tt = 128, cc = 1, qq = 50;
-        if (const char *e = std::getenv("POF_FLAT_TUNE")) {
-            int a = 0, b = 0, q = 50;
-            const int n = std::sscanf(e, "%d,%d,%d", &a, &b, &q);
-            if (n >= 2 && (a == 64 || a == 128 || a == 256) && (b == 1 || b == 2)) {
-                tt = a;
-                cc = b;
-                if (n == 3 && q >= 0 && q <= 100) qq = q;
-            }
-        }
-        c = cc;
-        pp = qq;
-        t = tt;
-    }
-    *threads = t;
-    *cpw = c;
-    *ppos = pp;
-}
-
 struct FlatCommon {
     const double *tab;
     const float *tabf;
@@ -1492,7 +1454,7 @@ struct FlatCommon {
 };
 
 // can the flat kernel take this shape?  (pairs of beams per lane, a wave's points within two samples)
-bool flat_shape_ok(int N, int cpw) { return N % 2 == 0 && N >= 128 * cpw; }
+bool flat_shape_ok(int N) { return N % 2 == 0 && N >= 2 * kFlatPairs; }   // N >= 128
 
 unsigned flat_flags(const FlatBatch &b, const FlatCommon &c)
 {
@@ -1509,20 +1471,6 @@ unsigned flat_flags(const FlatBatch &b, const FlatCommon &c)
     if (c.canonical) f |= kCanonical;
     f |= (unsigned)c.flow_kind << kKindShift;
     return f;
-}
-
-template <typename OutT, int CFG>
-void flat_dispatch(int threads, int cpw, dim3 grid, hipStream_t s, const FlatArgs &L, const ParamsMulti &P)
-{
-#define POF_FLAT_CASE(T, C) \
-    if (threads == T && cpw == C) { scan_flat_kernel<OutT, CFG, T, C><<<grid, T, 0, s>>>(L, P); return; }
-    POF_FLAT_CASE(64, 1)
-    POF_FLAT_CASE(64, 2)
-    POF_FLAT_CASE(128, 1)
-    POF_FLAT_CASE(128, 2)
-    POF_FLAT_CASE(256, 1)
-    POF_FLAT_CASE(256, 2)
-#undef POF_FLAT_CASE
 }
 
 // fill the params job set of one "next" batch; returns a status
@@ -1543,7 +1491,7 @@ int bind_next(const pof_scan_inputs *next, PreArgs &nx, int *jobs)
         nx.det_offsets = next->det_offsets; nx.det_rphi = next->det_rphi; nx.det_cls = next->det_cls;
         fill_class_constants(nx, next->det_offsets != nullptr, next->assoc_radius, next->labels, next->dyn_radius);
         bind_workspace(nx, next->workspace, next->B);
-        *jobs = params_job_count(nx.B, nx.det_offsets != nullptr);
+        *jobs = params_job_count(nx.B);
     }
     return POF_OK;
 }
@@ -1561,9 +1509,6 @@ void magic_u31(unsigned d, unsigned *m, int *sh)
 int launch_flat(const FlatBatch *cur, int n_cur, const FlatCommon &c, const pof_scan_inputs *const *next, int n_next,
                 hipStream_t s)
 {
-    int threads, cpw, ppos;
-    flat_tuning(&threads, &cpw, &ppos);
-    if (!flat_shape_ok(c.N, cpw)) cpw = 1;
     FlatArgs L = {};
     L.tab = c.tab; L.tabf = c.tabf; L.N = c.N; L.halfN = c.N / 2;
     int lg = 0;
@@ -1589,7 +1534,7 @@ int launch_flat(const FlatBatch *cur, int n_cur, const FlatCommon &c, const pof_
     L.m_assoc = f32_round_up(ma * 1.001 + 2.4e-7 * span);
     L.thr_assoc = f32_round_up(gap + (double)L.m_assoc + 1e-6 * std::fabs(gap));
     long long waves = 0;
-    const long long pairs_per_wave = 64LL * cpw;
+    const long long pairs_per_wave = kFlatPairs;
     for (int i = 0; i < n_cur; ++i) {
         if (flat_flags(cur[i], c) != L.flags) return POF_E_BADARG;   // one configuration per launch
         L.b[i] = cur[i];
@@ -1607,7 +1552,7 @@ int launch_flat(const FlatBatch *cur, int n_cur, const FlatCommon &c, const pof_
         for (int i = 0; i < n_cur && same; ++i) same = L.wave0[i] == (int)(per * i);
         if (same) { L.uni_waves = (int)per; magic_u31((unsigned)per, &L.uni_m, &L.uni_s); }
     }
-    const int wpb = threads / 64;
+    const int wpb = kFlatThreads / 64;
     L.main_blocks = (int)((waves + wpb - 1) / wpb);
     ParamsMulti P = {};
     P.nb = 0;
@@ -1620,7 +1565,7 @@ int launch_flat(const FlatBatch *cur, int n_cur, const FlatCommon &c, const pof_
         if (jobs == 0) continue;
         P.blk0[P.nb] = extra;
         P.p[P.nb] = nx;
-        extra += (jobs + threads - 1) / threads;
+        extra += (jobs + kFlatThreads - 1) / kFlatThreads;
         ++P.nb;
     }
     for (int i = P.nb; i <= kMaxSlots; ++i) P.blk0[i] = extra;
@@ -1632,16 +1577,16 @@ int launch_flat(const FlatBatch *cur, int n_cur, const FlatCommon &c, const pof_
         for (int i = 0; i < P.nb && same; ++i) same = P.blk0[i] == per * i;
         if (same) { P.uni_blocks = per; magic_u31((unsigned)per, &P.uni_m, &P.uni_s); }
     }
-    P.first = (int)((long long)L.main_blocks * ppos / 100);
+    P.first = L.main_blocks / 2;   // params blocks in the middle of the grid (see scan_flat_kernel)
     if (L.main_blocks + extra == 0) return POF_OK;
     dim3 grid((unsigned)(L.main_blocks + extra));
     const bool headline = (L.flags == (unsigned)kCfgHeadline);
     if (c.out_f64) {
-        if (headline) flat_dispatch<double, kCfgHeadline>(threads, cpw, grid, s, L, P);
-        else flat_dispatch<double, -1>(threads, cpw, grid, s, L, P);
+        if (headline) scan_flat_kernel<double, kCfgHeadline><<<grid, kFlatThreads, 0, s>>>(L, P);
+        else scan_flat_kernel<double, -1><<<grid, kFlatThreads, 0, s>>>(L, P);
     } else {
-        if (headline) flat_dispatch<float, kCfgHeadline>(threads, cpw, grid, s, L, P);
-        else flat_dispatch<float, -1>(threads, cpw, grid, s, L, P);
+        if (headline) scan_flat_kernel<float, kCfgHeadline><<<grid, kFlatThreads, 0, s>>>(L, P);
+        else scan_flat_kernel<float, -1><<<grid, kFlatThreads, 0, s>>>(L, P);
     }
     return POF_OK;
 }
@@ -1677,7 +1622,7 @@ int launch_preprocess(const float *ranges, long long sample_stride, int B, int N
     bind_workspace(a, workspace, B);
     hipStream_t s = pof_stream(stream);
     if (need_ws && (phases & 1)) {
-        const int total = params_job_count(B, det_offsets != nullptr);
+        const int total = params_job_count(B);
         scan_params_kernel<<<(total + 255) / 256, 256, 0, s>>>(a);
         POF_CHECK_LAUNCH();
     }
@@ -1697,7 +1642,7 @@ int launch_preprocess(const float *ranges, long long sample_stride, int B, int N
                       al16(xy) && al16(flow) && al16(closest) && al16(target_cls) && al16(target_reg) &&
                       al16(dyn_mask) && al16(valid_mask) && al16(exclude_mask);
     bool chained = false;
-    if (vec2 && flat_shape_ok(N, 1) && (long long)B * (N / 2) < (1LL << 31)) {
+    if (vec2 && flat_shape_ok(N) && (long long)B * (N / 2) < (1LL << 31)) {
         // flat form: line-aligned output runs per wave (see scan_flat_kernel)
         FlatBatch fb = {};
         fb.ranges = ranges; fb.sample_stride = sample_stride; fb.xy = xy; fb.flow = flow;
@@ -1783,7 +1728,7 @@ extern "C" int pof_scan_preprocess_multi(const pof_scan_batch *cur, int n_cur, c
     if ((n_cur > 0 && !cur) || (n_next > 0 && !next)) return POF_E_BADARG;
     if (n_cur > 0 && (!tab || N < 1)) return POF_E_BADARG;
     if (flow_kind < 0 || flow_kind > 4) return POF_E_BADARG;
-    if (n_cur > 0 && !flat_shape_ok(N, 1)) return POF_E_SHAPE;   // odd or short scans: pof_scan_preprocess_chained
+    if (n_cur > 0 && !flat_shape_ok(N)) return POF_E_SHAPE;   // odd or short scans: pof_scan_preprocess_chained
     FlatBatch fb[kMaxSlots] = {};
     for (int i = 0; i < n_cur; ++i) {
         const pof_scan_batch &c = cur[i];

@@ -2,8 +2,6 @@
 spatial attention walks, from the size of a launch.  The launchers call the same host functions, so these answers
 are what runs.  Checked here: the forms production shapes run, and that the parameter tables of
 tests/test_launch_size_gpu.py (tests/cases.py) launch every form the selection rules can produce."""
-import os
-
 import pytest
 
 import cases
@@ -18,12 +16,6 @@ def ops():
     return _ops
 
 
-def _no_forced_channel_group():
-    assert "POF_CONV_CT" not in os.environ, \
-        "POF_CONV_CT=%r forces the conv channel group: these plans assume the launcher's own choice; unset it" \
-        % os.environ["POF_CONV_CT"]
-
-
 def _form(ops, S, Ci, Co, L, kernel=3, stride=1, pool=False, fused=False):
     p = ops.conv1d_plan(S, Ci, Co, L, kernel, stride, pool, fused)
     return ("splitk" if p["split_k"] else "ct") + str(p["channels_per_workgroup"]) + \
@@ -34,7 +26,6 @@ def test_production_shapes(ops):
     """DR-SPAAM (S = windows x 5 scans x 450 cutouts through blocks 1-2, windows x 450 through blocks 3-4) and the
     Prototype at the README's batches run the 128-channel and quantised 64-channel tiles; streaming runs split K;
     attention at production batches walks segments of 29 .. 450 points."""
-    _no_forced_channel_group()
     f = lambda *a, **k: _form(ops, *a, **k)
     # DR-SPAAM forward at 32 windows (README row)
     S12, S34 = 32 * 5 * 450, 32 * 450
@@ -93,7 +84,6 @@ def test_gpu_tables_reach_every_form(ops):
     """The cases of tests/test_launch_size_gpu.py between them launch every conv family x {32, 64, 128} channels,
     split K with 32 and 64 channels, the quantised 64-channel form, ragged Co = 130 / 70 at 128 and 64 channels,
     64-bit output offsets, and attention segments from the shortest (B = 1) to the whole scan."""
-    _no_forced_channel_group()
     seen = set()
     for case in cases.CONV_FORM_CASES:
         family, Ci, Co, L, pool, cpw, split, quantised = case
