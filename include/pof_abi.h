@@ -537,6 +537,49 @@ int pof_keyframe_map_match(const float *ranges_cur, const double *tab, const int
                            double *flow_residual, float *rot, double *trans, double *flow_trans, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N11 person motion without a flow net: per detection the centroid of its own scan points in the world frame, paired
+ * with a centroid of the previous scan by a strict mutual-nearest rule; the difference is the person's displacement
+ * per scan.  It has the shape and meaning of pof_person_flow's det_flow, so pof_track_update takes det_xy_world /
+ * det_flow / det_valid unchanged.  The reference has nothing of the kind; the specification is this comment (restated
+ * in float64 NumPy by tests/test_person_motion.py).  One sensor per batch entry, one launch.
+ * Inputs: ranges [B][N] float32, the current scan; tab the angle table; the NMS results instance_mask [B][N], num_det
+ *   [B] (clamped to [0, N]), det_xy [B][N][2], det_cls [B][N]; the pose terms as pof_pose_advance and the keyframe
+ *   launches write them, rot [B][4] float32 row-major = (R00, R01, R10, R11) and trans [B][2] = (t_x, t_y).
+ * State per sensor, persistent, updated in place, allocated by the caller: prev_centre [B][N][2] float64, prev_cand
+ *   [B][N] uint8, prev_num [B] int32 (clamped to [0, N] when read).  A reset state has prev_num = 0: the launch runs
+ *   from the first scan of a sequence on and seeds itself there.
+ * Per detection row k < num_det:
+ *   det_xy_world [B][N][2] = fma(d1, Rt[1][c], d0 * Rt[0][c]) + trans and det_valid [B][N] uint8 = det_cls >= cls_thresh:
+ *     pof_person_flow's expressions, and its bits for the same inputs.
+ *   A point i counts for row k when instance_mask[i] = k + 1 and ranges[i] is finite and < max_range.  Its world
+ *     position, float64, plain multiplies and adds (no FMA):  r = (double)ranges[i], p = (r cos_i, r sin_i),
+ *     w_x = ((double)R00 p_x + (double)R01 p_y) + t_x,  w_y = ((double)R10 p_x + (double)R11 p_y) + t_y.
+ *   det_count [B][N] int32 = the number of counted points; det_centre [B][N][2] = the sum of their w, added in
+ *     ascending point index with float64 adds starting from 0, divided by (double)det_count (count 0 -> NaN).
+ *   Row k is a candidate when det_valid, det_count >= min_points and both centre components are finite.
+ * Association with the previous scan's candidate rows (j < prev_num with prev_cand[j] != 0):
+ *   d2(k, j) = dx dx + dy dy with d = det_centre[k] - prev_centre[j]; it counts only while d2 <= reach reach.
+ *   best(k) of a current candidate k: the previous candidate j of smallest d2, j scanned upwards with a strict <.
+ *   back(j) of a previous candidate j: the current candidate k of smallest d2, k scanned upwards with a strict <
+ *     (the lower k keeps a tie).
+ *   (k, j) is a pair when j = best(k) and k = back(j).  Then det_flow [B][N][2] = det_centre[k] - prev_centre[j] and
+ *   det_prev [B][N] int32 = j; otherwise det_flow is NaN and det_prev -1 (pof_track_update then makes its position-only
+ *   update by itself).
+ * Rows k >= num_det of the six outputs are zeros, with det_prev = -1.
+ * State update, after every read of it: prev_centre = det_centre, prev_cand = the candidate flags (0 from num_det on),
+ *   prev_num = the clamped num_det.
+ * One workgroup per sensor that reads and writes only its own rows; no atomics, fixed order: the same bits in every
+ * run, at every batch position and in a graph replay.  N <= 4096 (POF_E_SHAPE beyond, nothing written); one wave per
+ * sensor up to N = 512.  POF_E_BADARG: a NULL pointer, reach not >= 0, min_points < 1, B < 0, N < 1.  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_person_motion(const float *ranges, const double *tab, const int32_t *instance_mask, const int32_t *num_det,
+                      const double *det_xy, const double *det_cls, const float *rot, const double *trans,
+                      double cls_thresh, double max_range, double reach, int min_points, int B, int N,
+                      double *prev_centre, uint8_t *prev_cand, int32_t *prev_num, double *det_xy_world,
+                      double *det_flow, double *det_centre, int32_t *det_count, uint8_t *det_valid, int32_t *det_prev,
+                      pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

@@ -55,6 +55,8 @@ SIGNATURES = {
                                 _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pof_keyframe_map_match": (_i, [_p, _p, _p, _p, _p, _d, _d, _i, _d, _d, _d, _i, _d, _d, _d, _d, _d, _d, _i, _d, _i,
                                     _i, _i] + [_p] * 25),
+    "pof_person_motion": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                               _p]),
     "pof_flow_errors": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "pof_band_correlation": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pof_band_correlation_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),

@@ -1465,6 +1465,93 @@ def track_update(det_xy_world, det_flow, det_valid, num_det, instance_mask, stat
     return state
 
 
+PersonMotion = collections.namedtuple("PersonMotion", ("det_xy_world", "det_flow", "det_centre", "det_count",
+                                                        "det_valid", "det_prev"))
+PersonMotionState = collections.namedtuple("PersonMotionState", ("prev_centre", "prev_cand", "prev_num"))
+_PERSON_MOTION_OUT = (("det_xy_world", torch.float64), ("det_flow", torch.float64), ("det_centre", torch.float64),
+                      ("det_count", torch.int32), ("det_valid", torch.uint8), ("det_prev", torch.int32))
+_PERSON_MOTION_STATE = (("prev_centre", torch.float64), ("prev_cand", torch.uint8), ("prev_num", torch.int32))
+
+
+def _person_motion_out_shapes(B, N):
+    return (B, N, 2), (B, N, 2), (B, N, 2), (B, N), (B, N), (B, N)
+
+
+def _person_motion_state_shapes(B, N):
+    return (B, N, 2), (B, N), (B,)
+
+
+def person_motion_buffers(B, N, device="cuda"):
+    """The six outputs of ``person_motion`` for B scans of N points, zero-filled, as its ``out=`` (allocate once,
+    before a graph capture)."""
+    return _zeros(PersonMotion, _PERSON_MOTION_OUT, _person_motion_out_shapes(B, N), device)
+
+
+def person_motion_state(B, N, device="cuda"):
+    """The persistent state of ``person_motion`` for B sensors of N points: no previous scan (allocate once, before a
+    graph capture).  -> ``PersonMotionState``."""
+    return _zeros(PersonMotionState, _PERSON_MOTION_STATE, _person_motion_state_shapes(B, N), device)
+
+
+def person_motion_reset(state):
+    """Forget the previous scan of every sensor, in place, with tensor ops on the current stream (no host sync): the
+    next ``person_motion`` seeds."""
+    state = PersonMotionState(*state)
+    for t in state:
+        t.zero_()
+    return state
+
+
+def person_motion(ranges, tab, instance_mask, num_det, det_xy, det_cls, rot, trans, state, *, cls_thresh=0.5,
+                  max_range=20.0, reach=0.5, min_points=3, out=None):
+    """N11: person motion without a flow net, one launch per batch (include/pof_abi.h states the rules in full).
+
+    ranges [B,N] f32, the current scan; tab the angle table; instance_mask [B,N] i32, num_det [B] i32, det_xy [B,N,2]
+    f64, det_cls [B,N] f64 as ``nms_predicted_center`` returns them; rot [B,2,2] (or [B,4]) f32 and trans [B,2] f64,
+    the sensor's pose at this scan as ``pose_advance`` and the keyframe matchers write it.  ``state``: a
+    ``PersonMotionState`` (``person_motion_state``), UPDATED IN PLACE; with ``prev_num`` 0 the launch only seeds.
+    Per detection the world-frame centroid of its own scan points (finite ranges < ``max_range``, summed in point
+    order) is paired with the previous scan's centroids by a strict mutual-nearest rule within ``reach`` metres; only
+    detections of score >= ``cls_thresh`` with at least ``min_points`` points take part.
+    -> ``PersonMotion``: det_xy_world [B,N,2] f64 and det_valid [B,N] u8 with the bits of ``person_flow``'s, det_flow
+    [B,N,2] f64 = the displacement since the previous scan (NaN without a partner: ``track_update`` then updates the
+    position only), det_centre [B,N,2] f64, det_count [B,N] i32, det_prev [B,N] i32 = the partner's row in the previous
+    scan or -1.  Rows >= num_det[b] are zeros (det_prev -1).  The same bits in every run.  ``out``: a ``PersonMotion``
+    of preallocated tensors (``person_motion_buffers``)."""
+    ranges = _dev(ranges, torch.float32, "ranges")
+    if ranges.dim() != 2:
+        raise ValueError("ranges must be [B,N]")
+    B, N = ranges.shape
+    dev = ranges.device
+    tab = _dev(tab, torch.float64, "tab")
+    instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
+    num_det = _dev(num_det, torch.int32, "num_det")
+    det_xy = _dev(det_xy, torch.float64, "det_xy")
+    det_cls = _dev(det_cls, torch.float64, "det_cls")
+    if tab.numel() != 3 * N:
+        raise ValueError("ranges must be [B,N] matching the angle table")
+    if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_xy.shape) != (B, N, 2) or \
+            tuple(det_cls.shape) != (B, N):
+        raise ValueError("instance_mask and det_cls must be [B,N], num_det [B] and det_xy [B,N,2]")
+    if rot is None or trans is None:
+        raise TypeError("rot and trans must be tensors on the HIP device (no CPU path)")
+    _check_pose_terms(B, rot, trans, None)
+    state = PersonMotionState(*state)
+    _check_fields(state, _PERSON_MOTION_STATE, _person_motion_state_shapes(B, N), "state")
+    if out is None:
+        out = person_motion_buffers(B, N, dev)
+    else:
+        out = PersonMotion(*out)
+        _check_fields(out, _PERSON_MOTION_OUT, _person_motion_out_shapes(B, N), "out")
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_person_motion", _ptr(ranges), _ptr(tab), _ptr(instance_mask), _ptr(num_det), _ptr(det_xy),
+                  _ptr(det_cls), _ptr(rot), _ptr(trans), float(cls_thresh), float(max_range), float(reach),
+                  int(min_points), B, N, *[_ptr(t) for t in state], *[_ptr(t) for t in out], _stream())
+    return out
+
+
 def flow_errors(pred, target, mask=None):
     """A12 reductions: returns (epe_sum [B], aae_sum [B] radians, count [B]) float64."""
     pred = _dev(pred, torch.float32, "pred")

@@ -461,6 +461,49 @@ class PersonTracker:
         return h["det_track"][:m], tracks
 
 
+class PersonMotion:
+    """Per-person displacement from the scans alone, scan after scan (``ops.person_motion``, one launch per scan; the
+    reference has nothing of the kind): the world-frame centroid of every detection's own scan points, paired with the
+    previous scan's centroids by a strict mutual-nearest rule.  ``pm = PersonMotion(scan_phi, reach=0.5, ...)`` with
+    the settings of ``ops.person_motion`` (``cls_thresh``, ``max_range``, ``reach``, ``min_points``) and min_dist (0.5,
+    the NMS distance); ``res = pm.update(scan, pred_cls, pred_reg, odom)`` per scan, ``pm.reset()`` between sequences.
+
+    ``update``: NumPy in and NumPy out.  scan [N], pred_cls [N,1] (sigmoid scores), pred_reg [N,2]; odom = the
+    sensor's world (x, y, phi) at this scan (None: scanner frame).  The centre NMS runs first.  -> dict with the
+    per-detection keys of ``person_flow`` -- dets_xy_world [M,2], dets_cls [M,1], person_flow [M,2] (the displacement
+    since the previous scan, NaN without a partner), count [M], valid [M] -- and centre [M,2], prev [M] (the partner's
+    row in the previous result or -1) and instance_mask [N]; ``PersonTracker.update`` takes it as it is."""
+
+    def __init__(self, scan_phi, **kw):
+        self._tab = _table_for(scan_phi)
+        self._n = self._tab.numel() // 3
+        self._min_dist = kw.pop("min_dist", 0.5)
+        unknown = set(kw) - {"cls_thresh", "max_range", "reach", "min_points"}
+        if unknown:
+            raise ValueError("unknown person_motion settings: %s" % sorted(unknown))
+        self._kw = kw
+        self._state = ops.person_motion_state(1, self._n, self._tab.device)
+
+    def reset(self):
+        ops.person_motion_reset(self._state)
+
+    def update(self, scan, pred_cls, pred_reg, odom=None):
+        pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
+        assert pc.ndim == 2 and pc.shape[1] == 1
+        cur = _to_dev(scan, torch.float32).reshape(1, -1)
+        xy, dc, num, inst = ops.nms_predicted_center(cur, self._tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
+                                                     _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), self._min_dist)
+        rot, trans, _ = _pose_terms(None if odom is None else np.asarray(odom, dtype=np.float64)[None])
+        out = ops.person_motion(cur, self._tab, inst, num, xy, dc, _to_dev(rot, torch.float32),
+                                _to_dev(trans, torch.float64), self._state, **self._kw)
+        m = int(num[0].item())
+        host = lambda t: t[0].cpu().numpy()
+        return {"dets_xy_world": host(out.det_xy_world)[:m], "dets_cls": host(dc)[:m].reshape(-1, 1).astype(pc.dtype),
+                "person_flow": host(out.det_flow)[:m], "count": host(out.det_count)[:m],
+                "valid": host(out.det_valid)[:m].astype(bool), "centre": host(out.det_centre)[:m],
+                "prev": host(out.det_prev)[:m], "instance_mask": host(inst)}
+
+
 class KeyframeOdometry:
     """The sensor's pose from its scans alone, scan after scan, without the drift of composing one scan-to-scan fit
     per scan (``ops.keyframe_match``, one launch per scan; the reference has no scan matcher): every scan is matched

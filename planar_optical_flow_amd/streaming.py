@@ -26,6 +26,9 @@ the device, so the pose of a sensor that stands still or works in one place does
 With ``ego_motion=dict(method="keyframe_map")`` the sensor keeps a ring of keyframes (``ops.keyframe_map_match``, DESIGN
 8, N10): coming back to a stored keyframe switches to it instead of storing a new one, and the next match re-anchors
 the pose there -- still one launch, every decision on the device.
+With ``person_motion`` and no flow net the step ends in ``ops.person_motion``: per detection the
+world-frame centroid of its own scan points, paired with the previous scan's centroids on the device; the difference
+stands in for the per-person flow, and with ``tracks`` it feeds ``ops.track_update`` in the same chain.
 """
 import numpy as np
 import torch
@@ -83,13 +86,21 @@ class StreamingDetector:
     ``ops.keyframe_map_match``: a ring of ``keys`` keyframes per sensor, and a sensor that returns to within ``revisit``
     times ``key_dist`` / ``key_rot`` of a stored keyframe switches to it, so the next match re-anchors the pose on it.
 
-    ``tracks`` (needs ``flow_model``): None, or a dict of ``max_tracks`` (64) and the settings of ``ops.track_update``
+    ``tracks`` (needs ``flow_model`` or ``person_motion``): None, or a dict of ``max_tracks`` (64) and the settings of ``ops.track_update``
     (``gate``, ``q``, ``r_pos``, ``r_vel``, ``v0_var``, ``max_misses``, ``min_hits``).  The step then ends in the track
     update on the per-person result: ``tracks()`` returns the live tracks and the track id of every detection from the
-    second scan of a sequence on, and ``reset()`` forgets them (ids restart at 1)."""
+    second scan of a sequence on, and ``reset()`` forgets them (ids restart at 1).
+
+    ``person_motion`` (needs ``nms_min_dist``, excludes ``flow_model``): None, or a dict of ``reach`` (0.5),
+    ``min_points`` (3) and ``max_range`` (20.0) of ``ops.person_motion``.  Every step, the first of a sequence included,
+    then ends in that launch behind the pose launch: with ``method="scan_match"`` ``ops.pose_advance`` writes the pose
+    terms it reads, with ``"keyframe"`` / ``"keyframe_map"`` the keyframe launch does, and without ``ego_motion``
+    ``det(scan, pose=...)`` supplies the frame as with a flow model.  ``person_motion()`` returns the per-person result
+    from the first scan on (the displacements are NaN there), ``tracks`` is accepted without a flow model and is fed by
+    it, and ``reset()`` forgets the previous scan's centroids."""
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
-                 nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None):
+                 nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -119,7 +130,12 @@ class StreamingDetector:
         self.template = None            # fixed buffer once the first scan has been seen
         self._have_template = False
         self.feat_fused = self.pred_cls = self.pred_reg = None
-        self._flow_model = self._ego_kw = self._match_kw = self._key_kw = None
+        self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = None
+        if person_motion is not None:
+            if flow_model is not None:
+                raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
+            if self._nms is None:
+                raise ValueError("person_motion needs nms_min_dist: the centroids are taken over the NMS masks")
         method = "flow" if ego_motion is None else dict(ego_motion).get("method", "flow")
         if method not in ("flow", "scan_match", "keyframe", "keyframe_map"):
             raise ValueError("ego_motion method must be 'flow', 'scan_match', 'keyframe' or 'keyframe_map'")
@@ -127,7 +143,7 @@ class StreamingDetector:
             raise ValueError("ego_motion needs flow_model: the motion is fitted to the flow field "
                              "(method='scan_match' and method='keyframe' match the scans themselves)")
         self._cls_thresh = float(cls_thresh)
-        if tracks is not None and flow_model is None:
+        if tracks is not None and flow_model is None and person_motion is None:
             raise ValueError("tracks needs flow_model: the tracks are fed by the per-person flow")
         if flow_model is not None:
             if self._nms is None:
@@ -136,14 +152,7 @@ class StreamingDetector:
             # everything the tail of the step touches is allocated here, before any capture
             self._prev_scan = torch.zeros((self.B, self.N, 1), dtype=torch.float32, device=dev)
             self._pf_out = ops.person_flow_buffers(self.B, self.N, dev)
-            # trans | flow_trans | rot of every sensor in one buffer: one small copy per scan from a pinned staging
-            # buffer allocated once (an event keeps the host from refilling it while its last copy is in flight)
-            self._pose_dev = torch.zeros(self.B * 48, dtype=torch.uint8, device=dev)
-            self._pose_trans, self._pose_flow_trans, self._pose_rot = self._pose_views(self._pose_dev)
-            self._pose_host = torch.zeros(self.B * 48, dtype=torch.uint8).pin_memory()
-            self._pose_host_np = tuple(v.numpy() for v in self._pose_views(self._pose_host))
-            self._pose_copied = torch.cuda.Event()
-            self._prev_pose = None
+            self._alloc_pose_terms(dev)
             self._have_prev = self._have_flow = False
             if ego_motion is not None and method == "flow":
                 self._ego_kw = _ego_settings(ego_motion, huber_delta=0.02, iters=4, max_range=20.0,
@@ -151,14 +160,7 @@ class StreamingDetector:
                 self._ego_out = ops.ego_motion_buffers(self.B, self.N, dev)
                 self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
             if tracks is not None:
-                kw = dict(max_tracks=64, gate=0.5, q=1e-4, r_pos=2.5e-3, r_vel=2.5e-3, v0_var=0.25, max_misses=3,
-                          min_hits=3)
-                unknown = set(tracks) - set(kw)
-                if unknown:
-                    raise ValueError("unknown tracks settings: %s" % sorted(unknown))
-                kw.update(tracks)
-                self._track_state = ops.track_buffers(self.B, kw.pop("max_tracks"), self.N, dev)
-                self._track_kw = kw
+                self._alloc_tracks(tracks, dev)
         if method == "scan_match":
             self._match_kw = _ego_settings(ego_motion, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16,
                                            eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, max_range=20.0,
@@ -190,6 +192,45 @@ class StreamingDetector:
             self._key_kw = kw
             self._pose_state = self._key_state.pose
             self._key_seen = False
+        if person_motion is not None:
+            kw = dict(reach=0.5, min_points=3, max_range=20.0)
+            unknown = set(person_motion) - set(kw)
+            if unknown:
+                raise ValueError("unknown person_motion settings: %s" % sorted(unknown))
+            kw.update(person_motion)
+            if not float(kw["reach"]) >= 0.0 or int(kw["min_points"]) < 1:
+                raise ValueError("reach must be >= 0 and min_points >= 1")
+            # the outputs, the previous scan's centroids and the pose terms, before any capture
+            self._pm_kw = dict(kw, cls_thresh=self._cls_thresh)
+            self._pm_out = ops.person_motion_buffers(self.B, self.N, dev)
+            self._pm_state = ops.person_motion_state(self.B, self.N, dev)
+            self._pm_scans = 0
+            self._alloc_pose_terms(dev)
+            if self._match_kw is not None:
+                # the first scan of a sequence has no pair to match: a pose launch without ok writes the pose terms
+                self._pm_no_ok = torch.zeros(self.B, dtype=torch.uint8, device=dev)
+            if tracks is not None:
+                self._alloc_tracks(tracks, dev)
+
+    def _alloc_pose_terms(self, dev):
+        # trans | flow_trans | rot of every sensor in one buffer: one small copy per scan from a pinned staging
+        # buffer allocated once (an event keeps the host from refilling it while its last copy is in flight)
+        self._pose_dev = torch.zeros(self.B * 48, dtype=torch.uint8, device=dev)
+        self._pose_trans, self._pose_flow_trans, self._pose_rot = self._pose_views(self._pose_dev)
+        self._pose_host = torch.zeros(self.B * 48, dtype=torch.uint8).pin_memory()
+        self._pose_host_np = tuple(v.numpy() for v in self._pose_views(self._pose_host))
+        self._pose_copied = torch.cuda.Event()
+        self._prev_pose = None
+
+    def _alloc_tracks(self, tracks, dev):
+        kw = dict(max_tracks=64, gate=0.5, q=1e-4, r_pos=2.5e-3, r_vel=2.5e-3, v0_var=0.25, max_misses=3,
+                  min_hits=3)
+        unknown = set(tracks) - set(kw)
+        if unknown:
+            raise ValueError("unknown tracks settings: %s" % sorted(unknown))
+        kw.update(tracks)
+        self._track_state = ops.track_buffers(self.B, kw.pop("max_tracks"), self.N, dev)
+        self._track_kw = kw
 
     @staticmethod
     def _refuse_float16(model):
@@ -210,8 +251,11 @@ class StreamingDetector:
         if pose is not None and not self._dead_reckons():
             raise ValueError("reset(pose=...) is only used with ego_motion")
         self._have_template = False
-        if self._flow_model is not None:
+        if self._flow_model is not None or self._pm_kw is not None:
             self._prev_pose = None
+        if self._pm_kw is not None:
+            ops.person_motion_reset(self._pm_state)   # the next scan seeds the centroids
+            self._pm_scans = 0
         if self._has_tail():
             self._have_prev = self._have_flow = False
         if self._match_kw is not None:
@@ -280,7 +324,11 @@ class StreamingDetector:
                 m = ops.scan_match(self._prev_scan.view(self.B, self.N), self._scan[:, 0], self.tab,
                                    init=self._match_out.motion, out=self._match_out, **gate, **self._match_kw)
                 if self._flow_model is None:
-                    ops.pose_advance(m.motion, m.ok, self._pose_state)
+                    if self._pm_kw is None:
+                        ops.pose_advance(m.motion, m.ok, self._pose_state)
+                    else:
+                        ops.pose_advance(m.motion, m.ok, self._pose_state, self._pose_rot, self._pose_trans,
+                                         self._pose_flow_trans)
                     return
                 ops.pose_advance(m.motion, m.ok, self._pose_state, self._pose_rot, self._pose_trans,
                                  self._pose_flow_trans)
@@ -301,6 +349,15 @@ class StreamingDetector:
                 ops.track_update(o.det_xy_world, o.det_flow, o.det_valid, num, inst, self._track_state,
                                  **self._track_kw)
 
+    # tail of a step with person_motion: behind the pose launch, on every scan of a sequence (the first one seeds), on
+    # the same stream; then the track update on its result.  Writes only the fixed buffers.
+    def _motion_tail(self):
+        xy, conf, num, inst = self._dets
+        o = ops.person_motion(self._scan[:, 0], self.tab, inst, num, xy, conf, self._pose_rot, self._pose_trans,
+                              self._pm_state, out=self._pm_out, **self._pm_kw)
+        if self._has_tracks():
+            ops.track_update(o.det_xy_world, o.det_flow, o.det_valid, num, inst, self._track_state, **self._track_kw)
+
     # the keyframe launch: runs on every scan, the first of a sequence included (it seeds there); with a flow model it
     # stands in front of the tail and writes the pose terms the per-person launch reads
     def _key_step(self):
@@ -309,7 +366,7 @@ class StreamingDetector:
             _, conf, num, inst = self._dets
             gate = dict(instance_mask=inst, num_det=num, det_cls=conf)
         terms = {}
-        if self._flow_model is not None:
+        if self._flow_model is not None or self._pm_kw is not None:
             terms = dict(rot=self._pose_rot, trans=self._pose_trans, flow_trans=self._pose_flow_trans)
         self._key_match(self._scan[:, 0], self.tab, self._key_state, out=self._key_out, **gate, **terms, **self._key_kw)
 
@@ -347,12 +404,15 @@ class StreamingDetector:
             motion = None if self._match_kw is None else self._match_out.motion.clone()
             tracks = [t.clone() for t in self._track_state] if self._has_tracks() else None
             key = None if self._key_kw is None else [t.clone() for t in self._key_state]
+            centres = None if self._pm_kw is None else [t.clone() for t in self._pm_state]
             for _ in range(2):
                 self._step(False)
                 if key is not None:
                     self._key_step()
                 if self._has_tail():
                     self._flow_tail()             # reads the previous scan, writes only the output buffers
+                if centres is not None:
+                    self._motion_tail()
             if pose is not None:
                 self._pose_state.copy_(pose)      # ... and the pose state, which the warm-up must not advance
             if motion is not None:
@@ -363,6 +423,9 @@ class StreamingDetector:
             if key is not None:                   # ... nor the keyframe, its age and the pose
                 for t, saved in zip(self._key_state, key):
                     t.copy_(saved)
+            if centres is not None:               # ... nor the previous scan's centroids
+                for t, saved in zip(self._pm_state, centres):
+                    t.copy_(saved)
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -372,6 +435,9 @@ class StreamingDetector:
                 self._key_step()
             if self._has_tail():
                 self._flow_tail()
+            if self._pm_kw is not None:
+                self._motion_tail()
+            if self._has_tail():
                 self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
         self._graph, self._out, self._graph_dets = g, (cls, reg, fused), self._dets
 
@@ -382,7 +448,7 @@ class StreamingDetector:
         if self._dead_reckons():
             if pose is not None:
                 raise ValueError("an ego_motion detector takes no pose: it dead-reckons its own (reset(pose=...))")
-        elif self._flow_model is not None:
+        elif self._flow_model is not None or self._pm_kw is not None:
             self._set_pose(pose)
         elif pose is not None:
             raise ValueError("pose is only used with a flow_model")
@@ -409,6 +475,13 @@ class StreamingDetector:
             if self._have_prev:
                 self._flow_tail()
             self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
+        if self._pm_kw is not None:
+            if not replayed:
+                if self._match_kw is not None and not self._have_prev:
+                    ops.pose_advance(self._match_out.motion, self._pm_no_ok, self._pose_state, self._pose_rot,
+                                     self._pose_trans, self._pose_flow_trans)
+                self._motion_tail()
+            self._pm_scans = min(self._pm_scans + 1, 2)
         if self._has_tail():
             self._have_flow, self._have_prev = self._have_prev, True
         self.pred_cls, self.pred_reg, self.feat_fused = cls, reg, fused
@@ -438,6 +511,22 @@ class StreamingDetector:
                  "person_flow": host(o.det_flow, b, m), "person_rgb": host(o.det_rgb, b, m),
                  "count": host(o.det_count, b, m), "valid": host(o.det_valid, b, m).astype(bool)}
                 for b, m in enumerate(num.cpu().numpy())], o
+
+    def person_motion(self):
+        """-> list (one dict per sensor) of the last step's per-person result, with the per-detection keys of
+        ``person_flow()`` -- dets_xy_world [M,2], dets_cls [M], person_flow [M,2] (the displacement since the previous
+        scan; NaN without a partner, so on the first scan of a sequence), count [M], valid [M] -- and centre [M,2], prev
+        [M] (the partner's row in the previous scan or -1); and the device-resident outputs (``ops.PersonMotion``, valid
+        until the next call).  Needs ``person_motion`` and one scan.  Reads the counts back, i.e. synchronises."""
+        if self._pm_kw is None or self._pm_scans < 1:
+            raise RuntimeError("construct the detector with person_motion and feed it a scan first")
+        _, conf, num, _ = self._dets
+        o = self._pm_out
+        host = lambda t, b, m: t[b, :m].cpu().numpy()
+        return [{"dets_xy_world": host(o.det_xy_world, b, m), "dets_cls": host(conf, b, m),
+                 "person_flow": host(o.det_flow, b, m), "count": host(o.det_count, b, m),
+                 "valid": host(o.det_valid, b, m).astype(bool), "centre": host(o.det_centre, b, m),
+                 "prev": host(o.det_prev, b, m)} for b, m in enumerate(num.cpu().numpy())], o
 
     def ego_motion(self):
         """-> list (one dict per sensor) of the last step's fit: motion [3] = (theta, u_x, u_y) since the previous
@@ -484,7 +573,7 @@ class StreamingDetector:
         step or -1;  det_track, one array per sensor with the track id of every row of ``person_flow()``;  the
         device-resident ``ops.TrackState``, valid until the next call).  Needs ``tracks`` and two scans of a sequence.
         Reads the state back, i.e. synchronises."""
-        if not self._has_tracks() or not self._have_flow:
+        if not self._has_tracks() or not (self._pm_scans >= 2 if self._pm_kw is not None else self._have_flow):
             raise RuntimeError("construct the detector with tracks and feed it two scans of a sequence first")
         s = self._track_state
         h = {k: getattr(s, k).cpu().numpy() for k in s._fields}

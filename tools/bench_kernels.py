@@ -184,6 +184,10 @@ if "person" in which:
     ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out)
     tracks = {M: ops.track_buffers(B, M, N, dev) for M in (64, 256)}
     track = lambda M: ops.track_update(out.det_xy_world, out.det_flow, out.det_valid, num, inst, tracks[M])
+    # N11: person motion on the same scans, NMS results and pose.  The same scan every call: after the first one every
+    # candidate finds its own centroid of the call before -- the steady state, both pairwise searches run in full
+    pm_state, pm_out = ops.person_motion_state(B, N, dev), ops.person_motion_buffers(B, N, dev)
+    motion = lambda: ops.person_motion(scans, tab, inst, num, xy, dc, rot, trans, pm_state, out=pm_out)
     for rep in range(3):                                   # alternating, to see the spread
         ms_nms = timeit(lambda: ops.nms_predicted_center(scans, tab, cls, reg, 0.5), iters=50)
         ms_pf = timeit(lambda: ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out), iters=50)
@@ -207,6 +211,9 @@ if "person" in which:
                   % (K, ms_k1, ms_k16, km_out.iters_used.float().mean().item(), km_out.count.float().mean().item(),
                      int(km_out.ok.sum().item()), B, int(km_out.key_replaced.sum().item()),
                      int(km_out.key_switched.sum().item())))
+        ms_pm = timeit(motion, iters=50)
+        print("   person_motion %.3f ms next to person flow %.3f ms (%.0f candidates per scan, %.0f paired)"
+              % (ms_pm, ms_pf, pm_state.prev_cand.sum().item() / B, (pm_out.det_prev >= 0).sum().item() / B))
         ms_t = {M: timeit(lambda: track(M), iters=50) for M in tracks}
         print("   track_update (%.0f candidates per scan): %s" % (out.det_valid.sum().item() / B, ", ".join(
             "max_tracks %d: %.3f ms, %.0f live tracks per sensor" % (M, ms_t[M], (tracks[M].track_id > 0).sum().item() / B)

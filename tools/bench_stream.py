@@ -1,5 +1,5 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
@@ -12,7 +12,10 @@ and the scan matcher in front of the per-person flow, alternating repeats.
 --ego=keyframe: as --ego=scan_match with the keyframe matcher (ego_motion=dict(method="keyframe")) as one more step
 next to the scan matcher's, so one process gives the bare step, scan_match and keyframe.
 --ego=keyframe_map: as --ego=keyframe with the keyframe map (ego_motion=dict(method="keyframe_map")) as one more step
-next to the keyframe matcher's, so one process gives the bare step, scan_match, keyframe and keyframe_map."""
+next to the keyframe matcher's, so one process gives the bare step, scan_match, keyframe and keyframe_map.
+--person-motion (with --ego=scan_match|keyframe|keyframe_map, without --flow; implies --nms for every step of the
+process): two more steps next to those, the chosen method's with person_motion=dict() as its tail and that one with
+tracks=dict() behind it, so one process gives the step without and with the person motion."""
 import faulthandler, os, sys, time
 faulthandler.dump_traceback_later(90, exit=True)       # a stuck step reports where it is instead of hanging the box
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,7 +27,8 @@ from planar_optical_flow_amd.src.depracted.model.dr_spaam import SpatialDROW
 EMBED = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--embed=")] or ["library"])[0]
 STORAGE = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--storage=")] or ["float32"])[0]
 FLOW = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--flow=")] or [None])[0]
-NMS = 0.5 if (FLOW or "--nms" in sys.argv) else None
+PERSON_MOTION = "--person-motion" in sys.argv
+NMS = 0.5 if (FLOW or "--nms" in sys.argv or PERSON_MOTION) else None
 EGO_METHOD = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--ego=")] or ["flow"])[0]
 EGO = any(a == "--ego" or a.startswith("--ego=") for a in sys.argv)
 MATCH = dict(method="scan_match")
@@ -32,7 +36,7 @@ KEYFRAME = dict(method="keyframe")
 KEYFRAME_MAP = dict(method="keyframe_map")
 KEYED = ("keyframe", "keyframe_map")
 TRACKS = "--tracks" in sys.argv
-sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks"))]
+sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--person-motion"))]
 
 
 class DiffFlow(torch.nn.Module):
@@ -69,6 +73,12 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             if EGO_METHOD == "keyframe_map":
                 mapped = mk(ego_motion=KEYFRAME_MAP)
                 steps["keyframe_map"] = lambda t: mapped(scans[:, t])
+            if PERSON_MOTION:
+                chosen = {"scan_match": MATCH, "keyframe": KEYFRAME, "keyframe_map": KEYFRAME_MAP}[EGO_METHOD]
+                moved = mk(ego_motion=chosen, person_motion=dict())
+                followed = mk(ego_motion=chosen, person_motion=dict(), tracks=dict())
+                steps[EGO_METHOD + " + person_motion"] = lambda t: moved(scans[:, t])
+                steps[EGO_METHOD + " + person_motion + tracks"] = lambda t: followed(scans[:, t])
         else:
             posed, ego = mk(), mk(ego_motion=dict())
             steps = {"pose=": lambda t: posed(scans[:, t], pose=poses[t]), "ego_motion": lambda t: ego(scans[:, t])}
@@ -107,6 +117,12 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             fits, _ = matched.ego_motion()
             print("   scan_match at the last scan: iterations %s, matched %s, ok %s"
                   % ([f["iters_used"] for f in fits], [f["count"] for f in fits], [f["ok"] for f in fits]))
+        if PERSON_MOTION and EGO_METHOD in ("scan_match",) + KEYED and flow_model is None:
+            people, _ = moved.person_motion()
+            live, _, state = followed.tracks()
+            print("   person_motion at the last scan: detections %s, paired %s; tracks: %s live, next_id %s"
+                  % ([len(p["prev"]) for p in people], [int((p["prev"] >= 0).sum()) for p in people],
+                     [len(l) for l in live], state.next_id.tolist()))
         if TRACKS:
             live, _, state = tracked.tracks()
             print("   tracks after 40 scans: %s live, next_id %s" % ([len(l) for l in live], state.next_id.tolist()))
