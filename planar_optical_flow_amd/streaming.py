@@ -10,6 +10,13 @@ issues one graph launch per scan instead of thirty kernel launches.  Measured on
 step is host-bound at one sensor and took 0.60 to 2.35 ms on different boxes.  Outputs are bit-identical to the eager step.
 A model fused with ``embed="hip"`` has its gate embedding as one HIP node for the scan and the template, and may keep
 float16 storage (float16 cutout and template).
+
+Behind the trunk (cutout, model, NMS) a scan runs the stages its detector was built with, always in this order and on
+one stream, so a capture stays one linear chain: the keyframe launch; the scan matcher and its pose launch; the flow
+net; the flow fit and its pose launch; the per-person flow; the person motion; the track update; the copy of the scan
+into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a capture's warm-up
+and the captured region are each a loop over it, the warm-up puts back exactly the state the table names, and
+``reset()`` clears exactly that ("The stage table").  The paragraphs below say what each stage is.
 With a ``flow_model`` the step ends in the per-person flow (``ops.person_flow``): a flow net on the previous
 and the current scan, then one launch that turns its output, the NMS masks and the sensor pose into one world-frame
 flow vector and colour per detection -- still one replay per scan, nothing per point crosses to the host.
@@ -30,6 +37,8 @@ With ``person_motion`` and no flow net the step ends in ``ops.person_motion`` (D
 world-frame centroid of its own scan points, paired with the previous scan's centroids on the device; the difference
 stands in for the per-person flow, and with ``tracks`` it feeds ``ops.track_update`` in the same chain.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -39,13 +48,13 @@ _DEFAULT_CUTOUT = dict(fixed=True, centered=True, window_width=1.0, window_depth
                        padding_val=29.99, area_mode=True)
 
 
-def _ego_settings(ego_motion, **defaults):
-    """The defaults of a method, overridden by the ``ego_motion`` dict less its ``method``; any other key raises."""
-    unknown = set(ego_motion) - set(defaults) - {"method"}
+def _settings(name, given, **defaults):
+    """The defaults of the argument ``name``, overridden by the dict it was given; a key without a default raises."""
+    unknown = set(given) - set(defaults)
     if unknown:
-        raise ValueError("unknown ego_motion settings: %s" % sorted(unknown))
-    defaults.update({k: v for k, v in ego_motion.items() if k != "method"})
-    return defaults
+        raise ValueError("unknown %s settings: %s" % (name, sorted(unknown)))
+    return dict(defaults, **given)
+
 
 class StreamingDetector:
     """``det = StreamingDetector(model)``; ``pred_cls, pred_reg = det(scan)`` per incoming scan.
@@ -99,6 +108,12 @@ class StreamingDetector:
     from the first scan on (the displacements are NaN there), ``tracks`` is accepted without a flow model and is fed by
     it, and ``reset()`` forgets the previous scan's centroids."""
 
+    # One stage of a scan behind the trunk.  launch(first) enqueues it on the current stream (first: the first scan of a
+    # sequence) and writes only fixed buffers; state: the tensors it advances, which a capture's warm-up puts back;
+    # reset: forgets them at the start of a sequence; from_first: the first scan of a sequence runs it; warm_up: a
+    # capture's warm-up runs it.
+    _Stage = namedtuple("_Stage", "launch state reset from_first warm_up", defaults=((), None, True, True))
+
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
                  nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None):
         if not torch.cuda.is_available():
@@ -128,9 +143,11 @@ class StreamingDetector:
         self._dets = None
         self._graph = None
         self.template = None            # fixed buffer once the first scan has been seen
-        self._have_template = False
+        self._seen = 0                  # scans since reset(), saturating at 2
         self.feat_fused = self.pred_cls = self.pred_reg = None
-        self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = None
+        # what a feature was built with, None without it; _filter_kw: the settings of ops.track_update (a detector
+        # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
+        self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
@@ -145,40 +162,27 @@ class StreamingDetector:
         self._cls_thresh = float(cls_thresh)
         if tracks is not None and flow_model is None and person_motion is None:
             raise ValueError("tracks needs flow_model: the tracks are fed by the per-person flow")
-        if flow_model is not None:
-            if self._nms is None:
-                raise ValueError("flow_model needs nms_min_dist: the per-person flow is aggregated over the NMS masks")
-            self._flow_model = flow_model.to(dev).eval()
-            # everything the tail of the step touches is allocated here, before any capture
-            self._prev_scan = torch.zeros((self.B, self.N, 1), dtype=torch.float32, device=dev)
-            self._pf_out = ops.person_flow_buffers(self.B, self.N, dev)
-            self._alloc_pose_terms(dev)
-            self._have_prev = self._have_flow = False
-            if ego_motion is not None and method == "flow":
-                self._ego_kw = _ego_settings(ego_motion, huber_delta=0.02, iters=4, max_range=20.0,
-                                             cls_thresh=self._cls_thresh)
-                self._ego_out = ops.ego_motion_buffers(self.B, self.N, dev)
-                self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
-            if tracks is not None:
-                self._alloc_tracks(tracks, dev)
-        if method == "scan_match":
-            self._match_kw = _ego_settings(ego_motion, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16,
-                                           eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, max_range=20.0,
-                                           cls_thresh=self._cls_thresh)
-            # everything the matching tail touches, before any capture; the motion buffer is also the next step's init
-            if flow_model is None:
-                self._prev_scan = torch.zeros((self.B, self.N, 1), dtype=torch.float32, device=dev)
-                self._have_prev = self._have_flow = False
-            self._match_out = ops.scan_match_buffers(self.B, self.N, dev)
-            self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
+        if flow_model is not None and self._nms is None:
+            raise ValueError("flow_model needs nms_min_dist: the per-person flow is aggregated over the NMS masks")
+        ego = {k: v for k, v in (ego_motion or {}).items() if k != "method"}
+        match = dict(window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16, eps_theta=1e-7, eps_u=1e-7,
+                     min_pivot=1e-6, max_range=20.0, cls_thresh=self._cls_thresh)     # of the three scan matchers
         self._key_map = method == "keyframe_map"
+
+        # Everything a stage touches is allocated here, before any capture, and the stages are listed in the order a
+        # scan runs them.
+        self._terms = ()                # (rot, trans, flow_trans) where a per-person stage reads them
+        self._prev_pose = None
+        if flow_model is not None or person_motion is not None:
+            self._alloc_pose_terms(dev)
+        keeps_scan = flow_model is not None or method == "scan_match"
+        if keeps_scan:
+            self._prev_scan = torch.zeros((self.B, self.N, 1), dtype=torch.float32, device=dev)
+        Stage, stages = self._Stage, []
         if method == "keyframe" or self._key_map:
-            kw = _ego_settings(ego_motion, window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16,
-                               eps_theta=1e-7, eps_u=1e-7, min_pivot=1e-6, max_range=20.0, cls_thresh=self._cls_thresh,
-                               key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2,
-                               **(dict(keys=16, revisit=0.5) if self._key_map else {}))
-            # the keyframe (or the ring of them), its bookkeeping and the pose live on the device, allocated before
-            # any capture
+            kw = _settings("ego_motion", ego, **match, key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2,
+                           **(dict(keys=16, revisit=0.5) if self._key_map else {}))
+            # the keyframe (or the ring of them), its bookkeeping and the pose live on the device
             if self._key_map:
                 self._key_state = ops.keyframe_map_buffers(self.B, self.N, kw.pop("keys"), dev)
                 self._key_out = ops.keyframe_map_match_buffers(self.B, self.N, dev)
@@ -190,47 +194,60 @@ class StreamingDetector:
                 self._key_out = ops.keyframe_match_buffers(self.B, self.N, dev)
                 self._key_match, self._key_reset = ops.keyframe_match, ops.keyframe_reset
             self._key_kw = kw
+            self._key_terms = dict(zip(("rot", "trans", "flow_trans"), self._terms))
             self._pose_state = self._key_state.pose
-            self._key_seen = False
+            stages.append(Stage(self._keyframe_stage, tuple(self._key_state),
+                                lambda: self._key_reset(self._key_state)))        # the next scan becomes the keyframe
+        if method == "scan_match":
+            self._match_kw = _settings("ego_motion", ego, **match)
+            self._match_out = ops.scan_match_buffers(self.B, self.N, dev)     # its motion is also the next step's init
+            self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
+            if person_motion is not None:
+                # the first scan of a sequence has no pair to match: a pose launch without ok writes the pose terms
+                self._pm_no_ok = torch.zeros(self.B, dtype=torch.uint8, device=dev)
+            stages.append(Stage(self._match_stage, (self._match_out.motion, self._pose_state),
+                                self._match_out.motion.zero_,                    # the first pair starts from rest
+                                from_first=person_motion is not None))
+        if flow_model is not None:
+            self._flow_model = flow_model.to(dev).eval()
+            self._pf_out = ops.person_flow_buffers(self.B, self.N, dev)
+            if ego_motion is not None and method == "flow":
+                self._ego_kw = _settings("ego_motion", ego, huber_delta=0.02, iters=4, max_range=20.0,
+                                         cls_thresh=self._cls_thresh)
+                self._ego_out = ops.ego_motion_buffers(self.B, self.N, dev)
+                self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
+            stages.append(Stage(self._flow_stage, () if self._ego_kw is None else (self._pose_state,),
+                                from_first=False))
         if person_motion is not None:
-            kw = dict(reach=0.5, min_points=3, max_range=20.0)
-            unknown = set(person_motion) - set(kw)
-            if unknown:
-                raise ValueError("unknown person_motion settings: %s" % sorted(unknown))
-            kw.update(person_motion)
+            kw = _settings("person_motion", person_motion, reach=0.5, min_points=3, max_range=20.0)
             if not float(kw["reach"]) >= 0.0 or int(kw["min_points"]) < 1:
                 raise ValueError("reach must be >= 0 and min_points >= 1")
-            # the outputs, the previous scan's centroids and the pose terms, before any capture
             self._pm_kw = dict(kw, cls_thresh=self._cls_thresh)
             self._pm_out = ops.person_motion_buffers(self.B, self.N, dev)
             self._pm_state = ops.person_motion_state(self.B, self.N, dev)
-            self._pm_scans = 0
-            self._alloc_pose_terms(dev)
-            if self._match_kw is not None:
-                # the first scan of a sequence has no pair to match: a pose launch without ok writes the pose terms
-                self._pm_no_ok = torch.zeros(self.B, dtype=torch.uint8, device=dev)
-            if tracks is not None:
-                self._alloc_tracks(tracks, dev)
+            stages.append(Stage(self._motion_stage, tuple(self._pm_state),
+                                lambda: ops.person_motion_reset(self._pm_state)))  # the next scan seeds the centroids
+        if tracks is not None:
+            kw = _settings("tracks", tracks, max_tracks=64, gate=0.5, q=1e-4, r_pos=2.5e-3, r_vel=2.5e-3, v0_var=0.25,
+                           max_misses=3, min_hits=3)
+            self._track_state = ops.track_buffers(self.B, kw.pop("max_tracks"), self.N, dev)
+            self._filter_kw = kw
+            stages.append(Stage(self._track_stage, tuple(self._track_state),
+                                lambda: ops.track_reset(self._track_state), from_first=person_motion is not None))
+        if keeps_scan:
+            # not in a warm-up: the captured step behind it reads the scan before this one
+            stages.append(Stage(self._keep_scan, warm_up=False))
+        self._stages = tuple(stages)
 
     def _alloc_pose_terms(self, dev):
         # trans | flow_trans | rot of every sensor in one buffer: one small copy per scan from a pinned staging
         # buffer allocated once (an event keeps the host from refilling it while its last copy is in flight)
         self._pose_dev = torch.zeros(self.B * 48, dtype=torch.uint8, device=dev)
         self._pose_trans, self._pose_flow_trans, self._pose_rot = self._pose_views(self._pose_dev)
+        self._terms = (self._pose_rot, self._pose_trans, self._pose_flow_trans)
         self._pose_host = torch.zeros(self.B * 48, dtype=torch.uint8).pin_memory()
         self._pose_host_np = tuple(v.numpy() for v in self._pose_views(self._pose_host))
         self._pose_copied = torch.cuda.Event()
-        self._prev_pose = None
-
-    def _alloc_tracks(self, tracks, dev):
-        kw = dict(max_tracks=64, gate=0.5, q=1e-4, r_pos=2.5e-3, r_vel=2.5e-3, v0_var=0.25, max_misses=3,
-                  min_hits=3)
-        unknown = set(tracks) - set(kw)
-        if unknown:
-            raise ValueError("unknown tracks settings: %s" % sorted(unknown))
-        kw.update(tracks)
-        self._track_state = ops.track_buffers(self.B, kw.pop("max_tracks"), self.N, dev)
-        self._track_kw = kw
 
     @staticmethod
     def _refuse_float16(model):
@@ -250,37 +267,22 @@ class StreamingDetector:
         dead reckoning starts from; zeros by default."""
         if pose is not None and not self._dead_reckons():
             raise ValueError("reset(pose=...) is only used with ego_motion")
-        self._have_template = False
-        if self._flow_model is not None or self._pm_kw is not None:
-            self._prev_pose = None
-        if self._pm_kw is not None:
-            ops.person_motion_reset(self._pm_state)   # the next scan seeds the centroids
-            self._pm_scans = 0
-        if self._has_tail():
-            self._have_prev = self._have_flow = False
-        if self._match_kw is not None:
-            self._match_out.motion.zero_()            # the first pair of a sequence starts from rest
-        if self._key_kw is not None:
-            # the next scan becomes the keyframe
-            self._key_reset(self._key_state)
-            self._key_seen = False
+        self._seen = 0
+        self._prev_pose = None
+        for stage in self._stages:
+            if stage.reset is not None:
+                stage.reset()
         if self._dead_reckons():
             start = np.zeros((self.B, 3)) if pose is None else np.broadcast_to(
                 np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose,
                            dtype=np.float64).reshape(-1, 3), (self.B, 3)).copy()
             self._pose_state.copy_(torch.from_numpy(start))
-        if self._has_tracks():
-            ops.track_reset(self._track_state)
 
     def _has_tracks(self):
-        return getattr(self, "_track_kw", None) is not None
+        return self._filter_kw is not None
 
     def _dead_reckons(self):
         return self._ego_kw is not None or self._match_kw is not None or self._key_kw is not None
-
-    def _has_tail(self):
-        """The step has a tail that reads the previous scan: a flow model, the scan matcher, or both."""
-        return self._flow_model is not None or self._match_kw is not None
 
     def _ensure_fused(self):
         """The model was re-fused (new checkpoint) or left eval mode since the last step: fuse again if needed
@@ -310,65 +312,56 @@ class StreamingDetector:
                 self._dets = ops.nms_predicted_center(self._scan[:, 0], self.tab, conf, reg.double().contiguous(), self._nms)
         return cls, reg, tmpl, fused
 
-    # tail of a step with a flow model: flow net on (previous, current) scan, then the per-person launch.  Same
-    # stream as the step, so a capture stays one linear chain; writes only the fixed output buffers.
-    def _flow_tail(self):
+    def _match_gate(self):
+        """With the NMS the points of this scan's confident detections do not vote in a scan match."""
+        if self._dets is None:
+            return {}
+        _, conf, num, inst = self._dets
+        return dict(instance_mask=inst, num_det=num, det_cls=conf)
+
+    # The keyframe launch runs on every scan, the first of a sequence included (it seeds there); in front of a
+    # per-person stage it writes the pose terms that stage reads.
+    def _keyframe_stage(self, first):
+        self._key_match(self._scan[:, 0], self.tab, self._key_state, out=self._key_out, **self._match_gate(),
+                        **self._key_terms, **self._key_kw)
+
+    # The motion from the two scans alone, started from the previous step's (a NaN row, a failed pair, counts as zeros
+    # in the kernel), then the pose and, in front of a per-person stage, the pose terms.  The first scan of a sequence
+    # has no pair: in front of person_motion a pose launch without ok writes the pose terms.
+    def _match_stage(self, first):
+        if first:
+            ops.pose_advance(self._match_out.motion, self._pm_no_ok, self._pose_state, *self._terms)
+        else:
+            m = ops.scan_match(self._prev_scan.view(self.B, self.N), self._scan[:, 0], self.tab,
+                               init=self._match_out.motion, out=self._match_out, **self._match_gate(), **self._match_kw)
+            ops.pose_advance(m.motion, m.ok, self._pose_state, *self._terms)
+
+    # The flow net on (previous, current) scan; with method="flow" the sensor's motion from the flow outside this scan's
+    # confident detections, then the pose launch, which writes the pose terms; then the per-person launch, which reads
+    # them.
+    def _flow_stage(self, first):
+        xy, conf, num, inst = self._dets
         with torch.no_grad():
-            if self._match_kw is not None:
-                # the motion from the two scans alone, started from the previous step's (a NaN row, a failed pair,
-                # counts as zeros in the kernel), then the pose; with the NMS the confident detections do not vote
-                gate = {}
-                if self._dets is not None:
-                    _, conf, num, inst = self._dets
-                    gate = dict(instance_mask=inst, num_det=num, det_cls=conf)
-                m = ops.scan_match(self._prev_scan.view(self.B, self.N), self._scan[:, 0], self.tab,
-                                   init=self._match_out.motion, out=self._match_out, **gate, **self._match_kw)
-                if self._flow_model is None:
-                    if self._pm_kw is None:
-                        ops.pose_advance(m.motion, m.ok, self._pose_state)
-                    else:
-                        ops.pose_advance(m.motion, m.ok, self._pose_state, self._pose_rot, self._pose_trans,
-                                         self._pose_flow_trans)
-                    return
-                ops.pose_advance(m.motion, m.ok, self._pose_state, self._pose_rot, self._pose_trans,
-                                 self._pose_flow_trans)
-            flow = self._flow_model(self._prev_scan, self._scan.view(self.B, self.N, 1))
-            xy, conf, num, inst = self._dets
-            flow = flow.float().contiguous()
+            flow = self._flow_model(self._prev_scan, self._scan.view(self.B, self.N, 1)).float().contiguous()
             if self._ego_kw is not None:
-                # the sensor's motion from the flow outside this scan's confident detections, then the pose: the
-                # second launch writes the rot / trans / flow_trans buffers the per-person launch reads
                 ego = ops.ego_motion(self._scan[:, 0], self.tab, flow, instance_mask=inst, num_det=num, det_cls=conf,
                                      out=self._ego_out, **self._ego_kw)
-                ops.pose_advance(ego.motion, ego.ok, self._pose_state, self._pose_rot, self._pose_trans,
-                                 self._pose_flow_trans)
-            ops.person_flow(flow, self.tab, inst, num, xy, conf, self._pose_rot, self._pose_trans,
-                            self._pose_flow_trans, self._cls_thresh, out=self._pf_out)
-            if self._has_tracks():
-                o = self._pf_out
-                ops.track_update(o.det_xy_world, o.det_flow, o.det_valid, num, inst, self._track_state,
-                                 **self._track_kw)
+                ops.pose_advance(ego.motion, ego.ok, self._pose_state, *self._terms)
+            ops.person_flow(flow, self.tab, inst, num, xy, conf, *self._terms, self._cls_thresh, out=self._pf_out)
 
-    # tail of a step with person_motion: behind the pose launch, on every scan of a sequence (the first one seeds), on
-    # the same stream; then the track update on its result.  Writes only the fixed buffers.
-    def _motion_tail(self):
+    # Behind the pose launch, on every scan of a sequence (the first one seeds).
+    def _motion_stage(self, first):
         xy, conf, num, inst = self._dets
-        o = ops.person_motion(self._scan[:, 0], self.tab, inst, num, xy, conf, self._pose_rot, self._pose_trans,
-                              self._pm_state, out=self._pm_out, **self._pm_kw)
-        if self._has_tracks():
-            ops.track_update(o.det_xy_world, o.det_flow, o.det_valid, num, inst, self._track_state, **self._track_kw)
+        ops.person_motion(self._scan[:, 0], self.tab, inst, num, xy, conf, self._pose_rot, self._pose_trans,
+                          self._pm_state, out=self._pm_out, **self._pm_kw)
 
-    # the keyframe launch: runs on every scan, the first of a sequence included (it seeds there); with a flow model it
-    # stands in front of the tail and writes the pose terms the per-person launch reads
-    def _key_step(self):
-        gate = {}
-        if self._dets is not None:
-            _, conf, num, inst = self._dets
-            gate = dict(instance_mask=inst, num_det=num, det_cls=conf)
-        terms = {}
-        if self._flow_model is not None or self._pm_kw is not None:
-            terms = dict(rot=self._pose_rot, trans=self._pose_trans, flow_trans=self._pose_flow_trans)
-        self._key_match(self._scan[:, 0], self.tab, self._key_state, out=self._key_out, **gate, **terms, **self._key_kw)
+    # On the result of whichever per-person stage the detector has.
+    def _track_stage(self, first):
+        o, (_, _, num, inst) = self._pf_out if self._pm_kw is None else self._pm_out, self._dets
+        ops.track_update(o.det_xy_world, o.det_flow, o.det_valid, num, inst, self._track_state, **self._filter_kw)
+
+    def _keep_scan(self, first):
+        self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
 
     def _pose_views(self, buf):
         nb = self.B
@@ -400,51 +393,29 @@ class StreamingDetector:
         side = torch.cuda.Stream(device=self._scan.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                 # warm-up off the capture: library handles, lazy inits
-            pose = self._pose_state.clone() if self._dead_reckons() else None
-            motion = None if self._match_kw is None else self._match_out.motion.clone()
-            tracks = [t.clone() for t in self._track_state] if self._has_tracks() else None
-            key = None if self._key_kw is None else [t.clone() for t in self._key_state]
-            centres = None if self._pm_kw is None else [t.clone() for t in self._pm_state]
+            # it reads the template and the previous scan and writes the output buffers; what it advances besides --
+            # pose, match move, keyframe, centroids, tracks (ids and ages would run ahead) -- is put back
+            state = [t for stage in self._stages for t in stage.state]
+            saved = [t.clone() for t in state]
             for _ in range(2):
                 self._step(False)
-                if key is not None:
-                    self._key_step()
-                if self._has_tail():
-                    self._flow_tail()             # reads the previous scan, writes only the output buffers
-                if centres is not None:
-                    self._motion_tail()
-            if pose is not None:
-                self._pose_state.copy_(pose)      # ... and the pose state, which the warm-up must not advance
-            if motion is not None:
-                self._match_out.motion.copy_(motion)      # ... nor the start of the next match move
-            if tracks is not None:                # ... nor the tracks: ids and ages would run ahead
-                for t, saved in zip(self._track_state, tracks):
-                    t.copy_(saved)
-            if key is not None:                   # ... nor the keyframe, its age and the pose
-                for t, saved in zip(self._key_state, key):
-                    t.copy_(saved)
-            if centres is not None:               # ... nor the previous scan's centroids
-                for t, saved in zip(self._pm_state, centres):
-                    t.copy_(saved)
+                for stage in self._stages:
+                    if stage.warm_up:
+                        stage.launch(False)
+            for t, was in zip(state, saved):
+                t.copy_(was)
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             cls, reg, tmpl, fused = self._step(False)
             self.template.copy_(tmpl)                 # feed the fused template back in place
-            if self._key_kw is not None:
-                self._key_step()
-            if self._has_tail():
-                self._flow_tail()
-            if self._pm_kw is not None:
-                self._motion_tail()
-            if self._has_tail():
-                self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
+            for stage in self._stages:
+                stage.launch(False)
         self._graph, self._out, self._graph_dets = g, (cls, reg, fused), self._dets
 
     def __call__(self, scan, pose=None):
         scan = torch.as_tensor(scan, dtype=torch.float32)
         self._ensure_fused()
-        replayed = False
         if self._dead_reckons():
             if pose is not None:
                 raise ValueError("an ego_motion detector takes no pose: it dead-reckons its own (reset(pose=...))")
@@ -453,37 +424,20 @@ class StreamingDetector:
         elif pose is not None:
             raise ValueError("pose is only used with a flow_model")
         self._scan.copy_(scan.reshape(self.B, 1, self.N), non_blocking=True)
-        if not self._have_template:                   # first scan of a sequence: eager, template = its own features
-            cls, reg, tmpl, fused = self._step(True)
+        first = self._seen == 0                       # first scan of a sequence: eager, template = its own features
+        if first or not self._use_graph:
+            cls, reg, tmpl, fused = self._step(first)
             self._store_template(tmpl)
-            self._have_template = True
-        elif not self._use_graph:
-            cls, reg, tmpl, fused = self._step(False)
-            self._store_template(tmpl)
+            for stage in self._stages:
+                if stage.from_first or not first:
+                    stage.launch(first)
         else:
             if self._graph is None:
                 self._capture()                       # warm-up steps read the template, nothing writes it
-            self._graph.replay()
+            self._graph.replay()                      # the captured step holds the stages itself
             cls, reg, fused = self._out
             self._dets = self._graph_dets
-            replayed = True
-        if self._key_kw is not None:
-            if not replayed:
-                self._key_step()
-            self._key_seen = True
-        if self._has_tail() and not replayed:                 # the captured step holds this tail itself
-            if self._have_prev:
-                self._flow_tail()
-            self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
-        if self._pm_kw is not None:
-            if not replayed:
-                if self._match_kw is not None and not self._have_prev:
-                    ops.pose_advance(self._match_out.motion, self._pm_no_ok, self._pose_state, self._pose_rot,
-                                     self._pose_trans, self._pose_flow_trans)
-                self._motion_tail()
-            self._pm_scans = min(self._pm_scans + 1, 2)
-        if self._has_tail():
-            self._have_flow, self._have_prev = self._have_prev, True
+        self._seen = min(self._seen + 1, 2)
         self.pred_cls, self.pred_reg, self.feat_fused = cls, reg, fused
         return cls, reg
 
@@ -496,21 +450,24 @@ class StreamingDetector:
         counts = num.cpu().numpy()
         return [(xy[b, :m].cpu().numpy(), conf[b, :m].cpu().numpy()) for b, m in enumerate(counts)], inst.cpu().numpy()
 
+    def _per_detection(self, o, **fields):
+        """One dict per sensor of the rows of its detections: the scores, and under every key the field of ``o`` it
+        names."""
+        _, conf, num, _ = self._dets
+        host = lambda t, b, m: t[b, :m].cpu().numpy()
+        return [dict({k: host(getattr(o, f), b, m) for k, f in fields.items()}, dets_cls=host(conf, b, m),
+                     valid=host(o.det_valid, b, m).astype(bool)) for b, m in enumerate(num.cpu().numpy())]
+
     def person_flow(self):
         """-> list (one dict per sensor) of the last step's per-person result, as ``utils.person_flow`` returns it
         without the per-point entries: dets_xy_world [M,2], dets_cls [M], person_flow [M,2], person_rgb [M,3],
         count [M], valid [M]; and the device-resident per-point outputs (``ops.PersonFlow``, valid until the next
         call).  Needs ``flow_model`` and two scans of a sequence: the first one has no predecessor (the reference
         skips that frame too).  Reads the counts back, i.e. synchronises."""
-        if self._flow_model is None or not self._have_flow:
+        if self._flow_model is None or self._seen < 2:
             raise RuntimeError("construct the detector with flow_model and feed it two scans of a sequence first")
-        _, conf, num, _ = self._dets
-        o = self._pf_out
-        host = lambda t, b, m: t[b, :m].cpu().numpy()
-        return [{"dets_xy_world": host(o.det_xy_world, b, m), "dets_cls": host(conf, b, m),
-                 "person_flow": host(o.det_flow, b, m), "person_rgb": host(o.det_rgb, b, m),
-                 "count": host(o.det_count, b, m), "valid": host(o.det_valid, b, m).astype(bool)}
-                for b, m in enumerate(num.cpu().numpy())], o
+        return self._per_detection(self._pf_out, dets_xy_world="det_xy_world", person_flow="det_flow",
+                                   person_rgb="det_rgb", count="det_count"), self._pf_out
 
     def person_motion(self):
         """-> list (one dict per sensor) of the last step's per-person result, with the per-detection keys of
@@ -518,15 +475,10 @@ class StreamingDetector:
         scan; NaN without a partner, so on the first scan of a sequence), count [M], valid [M] -- and centre [M,2], prev
         [M] (the partner's row in the previous scan or -1); and the device-resident outputs (``ops.PersonMotion``, valid
         until the next call).  Needs ``person_motion`` and one scan.  Reads the counts back, i.e. synchronises."""
-        if self._pm_kw is None or self._pm_scans < 1:
+        if self._pm_kw is None or self._seen < 1:
             raise RuntimeError("construct the detector with person_motion and feed it a scan first")
-        _, conf, num, _ = self._dets
-        o = self._pm_out
-        host = lambda t, b, m: t[b, :m].cpu().numpy()
-        return [{"dets_xy_world": host(o.det_xy_world, b, m), "dets_cls": host(conf, b, m),
-                 "person_flow": host(o.det_flow, b, m), "count": host(o.det_count, b, m),
-                 "valid": host(o.det_valid, b, m).astype(bool), "centre": host(o.det_centre, b, m),
-                 "prev": host(o.det_prev, b, m)} for b, m in enumerate(num.cpu().numpy())], o
+        return self._per_detection(self._pm_out, dets_xy_world="det_xy_world", person_flow="det_flow", count="det_count",
+                                   centre="det_centre", prev="det_prev"), self._pm_out
 
     def ego_motion(self):
         """-> list (one dict per sensor) of the last step's fit: motion [3] = (theta, u_x, u_y) since the previous
@@ -539,32 +491,28 @@ class StreamingDetector:
         slot's, and the outputs are an ``ops.KeyframeMapMatch``.
         Synchronises."""
         if self._key_kw is not None:
-            if not self._key_seen:
+            if self._seen < 1:
                 raise RuntimeError("feed the detector a scan first")
-            o, s = self._key_out, self._key_state
-            host = [t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, o.iters_used, o.obs, s.pose,
-                                              o.key_replaced, s.key_age, s.key_pose)]
-            fits = [{"motion": host[0][b], "ok": bool(host[1][b]), "count": int(host[2][b]), "rms": float(host[3][b]),
-                     "iters_used": int(host[4][b]), "obs": float(host[5][b]), "pose": host[6][b],
-                     "key_replaced": bool(host[7][b]), "key_age": int(host[8][b]), "key_pose": host[9][b]}
-                    for b in range(self.B)]
-            if self._key_map:
-                switched, slot = o.key_switched.cpu().numpy(), o.key_slot.cpu().numpy()
-                for b, fit in enumerate(fits):
-                    fit.update(key_pose=host[9][b, slot[b]], key_switched=bool(switched[b]), key_slot=int(slot[b]))
-            return fits, o
-        if not self._dead_reckons() or not self._have_flow:
+        elif not self._dead_reckons() or self._seen < 2:
             raise RuntimeError("construct the detector with ego_motion and feed it two scans of a sequence first")
-        if self._match_kw is not None:
-            o = self._match_out
-            host = [t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, o.iters_used, o.obs, self._pose_state)]
-            return [{"motion": host[0][b], "ok": bool(host[1][b]), "count": int(host[2][b]), "rms": float(host[3][b]),
-                     "iters_used": int(host[4][b]), "obs": float(host[5][b]), "pose": host[6][b]}
-                    for b in range(self.B)], o
-        o = self._ego_out
-        motion, ok, count, rms, pose = (t.cpu().numpy() for t in (o.motion, o.ok, o.count, o.rms, self._pose_state))
-        return [{"motion": motion[b], "ok": bool(ok[b]), "count": int(count[b]), "rms": float(rms[b]), "pose": pose[b]}
-                for b in range(self.B)], o
+        o = self._key_out if self._key_kw is not None else self._match_out if self._match_kw is not None \
+            else self._ego_out
+        row = lambda v: v
+        fields = [("motion", o.motion, row), ("ok", o.ok, bool), ("count", o.count, int), ("rms", o.rms, float)]
+        if self._ego_kw is None:                      # the scan matchers
+            fields += [("iters_used", o.iters_used, int), ("obs", o.obs, float)]
+        fields.append(("pose", self._pose_state, row))
+        if self._key_kw is not None:
+            s = self._key_state
+            fields += [("key_replaced", o.key_replaced, bool), ("key_age", s.key_age, int), ("key_pose", s.key_pose, row)]
+        if self._key_map:
+            fields += [("key_switched", o.key_switched, bool), ("key_slot", o.key_slot, int)]
+        host = [(k, t.cpu().numpy(), as_type) for k, t, as_type in fields]
+        fits = [{k: as_type(h[b]) for k, h, as_type in host} for b in range(self.B)]
+        if self._key_map:
+            for fit in fits:
+                fit["key_pose"] = fit["key_pose"][fit["key_slot"]]        # of the ring's poses, the active slot's
+        return fits, o
 
     def tracks(self):
         """-> (list with one list per sensor of the live tracks, in slot order: dicts of id, xy [2], velocity [2] in
@@ -573,7 +521,7 @@ class StreamingDetector:
         step or -1;  det_track, one array per sensor with the track id of every row of ``person_flow()``;  the
         device-resident ``ops.TrackState``, valid until the next call).  Needs ``tracks`` and two scans of a sequence.
         Reads the state back, i.e. synchronises."""
-        if not self._has_tracks() or not (self._pm_scans >= 2 if self._pm_kw is not None else self._have_flow):
+        if not self._has_tracks() or self._seen < 2:
             raise RuntimeError("construct the detector with tracks and feed it two scans of a sequence first")
         s = self._track_state
         h = {k: getattr(s, k).cpu().numpy() for k in s._fields}
