@@ -580,6 +580,55 @@ int pof_person_motion(const float *ranges, const double *tab, const int32_t *ins
                       pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N12 occupancy grid map: a log-odds grid per sensor, updated by every scan from the scan and the pose terms.  It says
+ * which cells were seen free and which occupied, and per scan point what its cell held before this scan: a walking
+ * person's points land on cells that were seen free, the points of a static object do not.  The reference has nothing
+ * of the kind; the specification is this comment (restated in float64 NumPy by tests/test_grid_map.py).  One sensor
+ * per batch entry, two launches on the stream (the points, then the cells).
+ * State per sensor, persistent, updated in place, allocated by the caller: grid [B][H][W] int16, the log-odds in integer
+ *   counts, 0 = unknown, row iy is y and column ix is x; origin [B][2] float64 = (o_x, o_y), the world position of the
+ *   lower corner of cell (0, 0), read only.  A reset state is all zeros.
+ * Inputs: ranges [B][N] float32, the current scan; tab the angle table (its cosines and sines lie in [-1, 1], as those
+ *   of pof_laser_phi do); the pose terms as pof_pose_advance and the keyframe launches write them, rot [B][4] float32
+ *   row-major = (R00, R01, R10, R11) and trans [B][2] = (t_x, t_y): world = R p + t; optionally the NMS results
+ *   instance_mask [B][N], num_det [B] (clamped to [0, N]) and det_cls [B][N], all three or none (NULL).
+ * Per beam i, float64, plain multiplies and adds (no FMA):  r = (double)ranges[i].  The beam is a HIT when r is finite
+ *   and 0 < r < max_range.  p = (r cos_i, r sin_i), w_x = ((double)R00 p_x + (double)R01 p_y) + t_x,
+ *   w_y = ((double)R10 p_x + (double)R11 p_y) + t_y (N11's expressions), g_x = floor((w_x - o_x) / res), g_y =
+ *   floor((w_y - o_y) / res) with a true division.  The endpoint is INSIDE when 0 <= g_x < W and 0 <= g_y < H, compared
+ *   in double (a NaN is outside).  A beam is a PERSON's point when the NMS results are given, id = instance_mask[i]
+ *   has 1 <= id <= num_det and det_cls[id - 1] >= cls_thresh (pof_ego_motion's gate): persons are never burned in.
+ *     point_cell  [B][N] int32 = g_y W + g_x for a hit inside the grid, else -1;
+ *     point_prior [B][N] int16 = the grid value of that cell BEFORE this call's update, -32768 where point_cell is -1;
+ *     point_mark  [B][N] uint8 = 1 for a hit inside the grid that is no person's point, else 0.
+ * Per detection row k < num_det (NMS results given):  det_points [B][N] int32 = the number of hits inside the grid with
+ *   instance_mask = k + 1, det_free [B][N] int32 = how many of them have point_prior <= -free_thresh.  Rows >= num_det,
+ *   and every row without NMS results, are zeros.
+ * Per cell (ix, iy):  c_x = o_x + ((double)ix + 0.5) res, c_y = o_y + ((double)iy + 0.5) res, d = c - t; in the sensor
+ *   frame s_x = (double)R00 d_x + (double)R10 d_y, s_y = (double)R01 d_x + (double)R11 d_y, rho = sqrt(s_x s_x + s_y s_y);
+ *   its beam m = rint((atan2(s_y, s_x) - tab[0]) / dphi) with dphi = tab[1] - tab[0] (0 for N = 1), the expression of
+ *   the keyframe matcher's window centre; m outside [0, N) (a NaN or an infinity included; no wrap-around) frees nothing.
+ *   A beam j is VALID when ranges[j] is not NaN and > 0; then r_eff(j) = min((double)ranges[j], max_range): a beam
+ *   without a return frees up to max_range.
+ *     1. some beam with point_mark = 1 has this cell as point_cell:                      delta = +hit
+ *     2. else beam m is valid and rho + tol < f, f = the smallest r_eff of the valid beams among m - 1, m, m + 1 inside
+ *        [0, N) (the neighbours keep a cell beside an occlusion edge from being freed):   delta = -miss
+ *     3. else                                                                            delta = 0
+ *   grid = (int16)clamp((int)grid + delta, lo, hi) where delta != 0; a cell with delta = 0 keeps its bits.
+ * Gather form, no global atomics: the same bits in every run, at every batch position and in a graph replay.
+ * POF_E_BADARG (checked first; nothing written): a NULL required pointer, NMS pointers given in part, res not > 0, tol
+ *   not >= 0, max_range not > 0, hit < 0, miss < 0, lo outside [-32767, 0], hi outside [0, 32767], free_thresh < 0,
+ *   B < 0, N < 1.  POF_E_SHAPE (nothing written): N > 4096, H or W not a multiple of 64 or outside [64, 2048], grid
+ *   not 16-byte aligned, B H W / 4096 >= 2^31.  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_grid_map_update(const float *ranges, const double *tab, const float *rot, const double *trans,
+                        const int32_t *instance_mask, const int32_t *num_det, const double *det_cls, double res,
+                        double tol, double max_range, double cls_thresh, int hit, int miss, int lo, int hi,
+                        int free_thresh, int B, int N, int H, int W, int16_t *grid, const double *origin,
+                        int32_t *point_cell, uint8_t *point_mark, int16_t *point_prior, int32_t *det_points,
+                        int32_t *det_free, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

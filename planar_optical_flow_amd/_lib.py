@@ -57,6 +57,7 @@ SIGNATURES = {
                                     _i, _i] + [_p] * 25),
     "pof_person_motion": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                _p]),
+    "pof_grid_map_update": (_i, [_p] * 7 + [_d] * 4 + [_i] * 9 + [_p] * 8),
     "pof_flow_errors": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "pof_band_correlation": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pof_band_correlation_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),

@@ -1552,6 +1552,93 @@ def person_motion(ranges, tab, instance_mask, num_det, det_xy, det_cls, rot, tra
     return out
 
 
+GridMapState = collections.namedtuple("GridMapState", ("grid", "origin"))
+GridMapOut = collections.namedtuple("GridMapOut", ("point_cell", "point_mark", "point_prior", "det_points", "det_free"))
+_GRID_MAP_STATE = (("grid", torch.int16), ("origin", torch.float64))
+_GRID_MAP_OUT = (("point_cell", torch.int32), ("point_mark", torch.uint8), ("point_prior", torch.int16),
+                 ("det_points", torch.int32), ("det_free", torch.int32))
+
+
+def grid_map_buffers(B, N, device="cuda"):
+    """The five outputs of ``grid_map_update`` for B scans of N points, zero-filled, as its ``out=`` (allocate once,
+    before a graph capture)."""
+    return _zeros(GridMapOut, _GRID_MAP_OUT, ((B, N),) * 5, device)
+
+
+def grid_map_state(B, H, W, device="cuda"):
+    """The persistent state of ``grid_map_update`` for B sensors: a grid of H x W cells, all unknown, with its lower
+    corner at the world origin (allocate once, before a graph capture).  -> ``GridMapState``."""
+    return _zeros(GridMapState, _GRID_MAP_STATE, ((B, H, W), (B, 2)), device)
+
+
+def grid_map_reset(state, origin=None):
+    """Every cell unknown again, in place, with tensor ops on the current stream (no host sync).  origin ([2] or [B,2],
+    numbers or a device tensor): the world position of the lower corner of cell (0, 0); zeros by default."""
+    state = GridMapState(*state)
+    state.grid.zero_()
+    if origin is None:
+        state.origin.zero_()
+    else:
+        origin = torch.as_tensor(origin, dtype=torch.float64).reshape(-1, 2)
+        state.origin.copy_(origin.expand(state.origin.shape[0], 2), non_blocking=True)
+    return state
+
+
+def grid_map_update(ranges, tab, rot, trans, state, *, res, instance_mask=None, num_det=None, det_cls=None,
+                    cls_thresh=0.5, max_range=20.0, tol=None, hit=17, miss=8, lo=-40, hi=70, free_thresh=16, out=None):
+    """N12: one scan into the occupancy grid of every sensor, two launches per batch (include/pof_abi.h states the
+    rules in full).
+
+    ranges [B,N] f32, the current scan; tab the angle table; rot [B,2,2] (or [B,4]) f32 and trans [B,2] f64, the
+    sensor's pose at this scan as ``pose_advance`` and the keyframe matchers write it.  ``state``: a ``GridMapState``
+    (``grid_map_state``): grid [B,H,W] i16, the log-odds in integer counts (0 = unknown), UPDATED IN PLACE, and origin
+    [B,2] f64, the world position of the grid's lower corner; H and W multiples of 64 in [64, 2048].  ``res``: metres
+    per cell.  A cell that holds the endpoint of a beam (finite, 0 < r < ``max_range``) gains ``hit``; otherwise a cell
+    whose beam and its two neighbours all pass it by more than ``tol`` (None: ``res``) loses ``miss``; the value stays
+    in [``lo``, ``hi``].  The defaults read as counts of 0.05 nat.  With the NMS results instance_mask [B,N] i32,
+    num_det [B] i32, det_cls [B,N] f64 (all three or none) the points of detections of score >= ``cls_thresh`` are
+    never burned in.
+    -> ``GridMapOut``: point_cell [B,N] i32 (the cell iy W + ix of every endpoint, -1 without one inside the grid),
+    point_mark [B,N] u8 (the endpoint was burned in), point_prior [B,N] i16 (what its cell held before this scan,
+    -32768 without one), det_points / det_free [B,N] i32 (per detection row the endpoints inside the grid and how many
+    of them lie on cells that held <= -``free_thresh``; zeros without the NMS results).  The same bits in every run.
+    ``out``: a ``GridMapOut`` of preallocated tensors (``grid_map_buffers``)."""
+    ranges = _dev(ranges, torch.float32, "ranges")
+    if ranges.dim() != 2:
+        raise ValueError("ranges must be [B,N]")
+    B, N = ranges.shape
+    dev = ranges.device
+    tab = _dev(tab, torch.float64, "tab")
+    if tab.numel() != 3 * N:
+        raise ValueError("ranges must be [B,N] matching the angle table")
+    if rot is None or trans is None:
+        raise TypeError("rot and trans must be tensors on the HIP device (no CPU path)")
+    _check_pose_terms(B, rot, trans, None)
+    gate = (instance_mask, num_det, det_cls)
+    if any(t is not None for t in gate):
+        if any(t is None for t in gate):
+            raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
+        gate = _nms_gate(*gate, B, N)
+    state = GridMapState(*state)
+    if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
+        raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
+    H, W = state.grid.shape[1:]
+    _check_fields(state, _GRID_MAP_STATE, ((B, H, W), (B, 2)), "state")
+    if out is None:
+        out = grid_map_buffers(B, N, dev)
+    else:
+        out = GridMapOut(*out)
+        _check_fields(out, _GRID_MAP_OUT, ((B, N),) * 5, "out")
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_grid_map_update", _ptr(ranges), _ptr(tab), _ptr(rot), _ptr(trans), *[_ptr(t) for t in gate],
+                  float(res), float(res if tol is None else tol), float(max_range), float(cls_thresh), int(hit),
+                  int(miss), int(lo), int(hi), int(free_thresh), B, N, H, W, *[_ptr(t) for t in state],
+                  *[_ptr(t) for t in out], _stream())
+    return out
+
+
 def flow_errors(pred, target, mask=None):
     """A12 reductions: returns (epe_sum [B], aae_sum [B] radians, count [B]) float64."""
     pred = _dev(pred, torch.float32, "pred")

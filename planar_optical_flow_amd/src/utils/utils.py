@@ -589,6 +589,81 @@ class KeyframeMapOdometry(KeyframeOdometry):
         return d
 
 
+class OccupancyGrid:
+    """An occupancy grid map of what one sensor has seen, scan after scan (``ops.grid_map_update``, two launches per
+    scan; the reference has nothing of the kind): an int16 log-odds grid of ``size`` x ``size`` cells (or ``size`` =
+    (H, W); multiples of 64) of ``res`` metres, kept on the device.  ``og = OccupancyGrid(scan_phi, res=0.1, size=512,
+    ...)`` with the settings of ``ops.grid_map_update`` (``cls_thresh``, ``max_range``, ``tol``, ``hit``, ``miss``,
+    ``lo``, ``hi``, ``free_thresh``) and min_dist (0.5, the NMS distance); ``res = og.update(scan, odom, pred_cls,
+    pred_reg)`` per scan, ``og.reset(origin)`` between sequences.
+
+    ``update``: NumPy in and NumPy out.  scan [N]; odom = the sensor's world (x, y, phi) at this scan (None: the world
+    origin).  With pred_cls [N,1] (sigmoid scores) and pred_reg [N,2] the centre NMS runs first and the points of
+    detections with a score >= cls_thresh are not burned in.  -> dict: point_cell [N], point_mark [N] (bool),
+    point_prior [N], and with predictions det_points [M], det_free [M], dets_cls [M,1] and instance_mask [N].
+    ``reset(origin)``: every cell unknown; origin [2] = the world position of the grid's lower corner -- by default the
+    next update puts its pose in the middle of the grid.  ``logodds`` is the grid [H,W] int16 on the host,
+    ``probability(unit)`` the occupancy probability of a count worth ``unit`` nat."""
+
+    def __init__(self, scan_phi, res=0.1, size=512, **kw):
+        # the settings first: a wrong one raises before anything touches the device
+        self._min_dist = kw.pop("min_dist", 0.5)
+        unknown = set(kw) - {"cls_thresh", "max_range", "tol", "hit", "miss", "lo", "hi", "free_thresh"}
+        if unknown:
+            raise ValueError("unknown grid_map settings: %s" % sorted(unknown))
+        H, W = (size, size) if np.ndim(size) == 0 else size
+        self.res, self.shape = float(res), (int(H), int(W))
+        if not self.res > 0.0:
+            raise ValueError("res must be > 0")
+        if any(s % 64 or not 64 <= s <= 2048 for s in self.shape):
+            raise ValueError("size must be a multiple of 64 in [64, 2048]")
+        self._kw = kw
+        self._tab = _table_for(scan_phi)
+        self._n = self._tab.numel() // 3
+        self._state = ops.grid_map_state(1, *self.shape, self._tab.device)
+        self._centre = True
+
+    def reset(self, origin=None):
+        ops.grid_map_reset(self._state, origin)
+        self._centre = origin is None
+
+    def update(self, scan, odom=None, pred_cls=None, pred_reg=None):
+        cur = _to_dev(scan, torch.float32).reshape(1, -1)
+        gate, dc = {}, None
+        if pred_cls is not None and pred_reg is not None:
+            pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
+            assert pc.ndim == 2 and pc.shape[1] == 1
+            _, dc, num, inst = ops.nms_predicted_center(cur, self._tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
+                                                        _to_dev(pred_reg, torch.float64).reshape(1, -1, 2),
+                                                        self._min_dist)
+            gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
+        rot, trans, _ = _pose_terms(None if odom is None else np.asarray(odom, dtype=np.float64)[None])
+        if self._centre:                                       # the first pose of a sequence in the middle of the grid
+            ops.grid_map_reset(self._state, trans[0] - 0.5 * self.res * np.array(self.shape[::-1], dtype=np.float64))
+            self._centre = False
+        out = ops.grid_map_update(cur, self._tab, _to_dev(rot, torch.float32), _to_dev(trans, torch.float64),
+                                  self._state, res=self.res, **gate, **self._kw)
+        host = lambda t: t[0].cpu().numpy()
+        result = {"point_cell": host(out.point_cell), "point_mark": host(out.point_mark).astype(bool),
+                  "point_prior": host(out.point_prior)}
+        if dc is not None:
+            m = int(num[0].item())
+            result.update(det_points=host(out.det_points)[:m], det_free=host(out.det_free)[:m],
+                          dets_cls=host(dc)[:m].reshape(-1, 1).astype(pc.dtype), instance_mask=host(inst))
+        return result
+
+    @property
+    def origin(self):
+        return self._state.origin[0].cpu().numpy()
+
+    @property
+    def logodds(self):
+        return self._state.grid[0].cpu().numpy()
+
+    def probability(self, unit=0.05):
+        return 1.0 / (1.0 + np.exp(-float(unit) * self.logodds.astype(np.float64)))
+
+
 def _pose_terms(odom1, odom0=None, batch=1):
     """Host side of ``person_flow`` for B sensors at once: (rot [B,2,2] float32, trans [B,2], flow_trans [B,2]) of the
     poses odom1 [B,3] = (x, y, phi) and the previous ones odom0, as infer_person_flow.py:114-117,145-146 forms them

@@ -13,9 +13,9 @@ float16 storage (float16 cutout and template).
 
 Behind the trunk (cutout, model, NMS) a scan runs the stages its detector was built with, always in this order and on
 one stream, so a capture stays one linear chain: the keyframe launch; the scan matcher and its pose launch; the flow
-net; the flow fit and its pose launch; the per-person flow; the person motion; the track update; the copy of the scan
-into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a capture's warm-up
-and the captured region are each a loop over it, the warm-up puts back exactly the state the table names, and
+net; the flow fit and its pose launch; the per-person flow; the person motion; the track update; the grid map; the
+copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
+capture's warm-up and the captured region are each a loop over it, the warm-up puts back exactly the state the table names, and
 ``reset()`` clears exactly that ("The stage table").  The paragraphs below say what each stage is.
 With a ``flow_model`` the step ends in the per-person flow (``ops.person_flow``): a flow net on the previous
 and the current scan, then one launch that turns its output, the NMS masks and the sensor pose into one world-frame
@@ -36,6 +36,8 @@ the pose there -- still one launch, every decision on the device.
 With ``person_motion`` and no flow net the step ends in ``ops.person_motion``: per detection the
 world-frame centroid of its own scan points, paired with the previous scan's centroids on the device; the difference
 stands in for the per-person flow, and with ``tracks`` it feeds ``ops.track_update`` in the same chain.
+With ``grid_map`` the chain also holds ``ops.grid_map_update``: every scan is entered at the step's
+pose into an occupancy grid per sensor that stays on the device, and every scan point learns what its cell held before.
 """
 from collections import namedtuple
 
@@ -106,7 +108,16 @@ class StreamingDetector:
     terms it reads, with ``"keyframe"`` / ``"keyframe_map"`` the keyframe launch does, and without ``ego_motion``
     ``det(scan, pose=...)`` supplies the frame as with a flow model.  ``person_motion()`` returns the per-person result
     from the first scan on (the displacements are NaN there), ``tracks`` is accepted without a flow model and is fed by
-    it, and ``reset()`` forgets the previous scan's centroids."""
+    it, and ``reset()`` forgets the previous scan's centroids.
+
+    ``grid_map`` (needs a pose: ``ego_motion`` with ``method="scan_match"``, ``"keyframe"`` or ``"keyframe_map"``, or no
+    ``ego_motion`` and ``det(scan, pose=...)``; ``method="flow"`` is refused): None, or a dict of ``res`` (0.1 m per
+    cell), ``size`` (512 cells; or (H, W); multiples of 64) and ``max_range``, ``tol``, ``hit``, ``miss``, ``lo``,
+    ``hi``, ``free_thresh`` of ``ops.grid_map_update``.  Every step, the first of a sequence included, then enters the
+    scan into an occupancy grid per sensor at the step's pose; with ``nms_min_dist`` the points of this scan's
+    confident detections are not burned in and ``det_points`` / ``det_free`` say per detection how many of its points
+    lie on cells seen free.  ``grid_map()`` returns the grid and the per-point outputs, and ``reset()`` empties the
+    grid and puts the start pose in its middle."""
 
     # One stage of a scan behind the trunk.  launch(first) enqueues it on the current stream (first: the first scan of a
     # sequence) and writes only fixed buffers; state: the tensors it advances, which a capture's warm-up puts back;
@@ -115,7 +126,8 @@ class StreamingDetector:
     _Stage = namedtuple("_Stage", "launch state reset from_first warm_up", defaults=((), None, True, True))
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
-                 nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None):
+                 nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None,
+                 grid_map=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -148,6 +160,7 @@ class StreamingDetector:
         # what a feature was built with, None without it; _filter_kw: the settings of ops.track_update (a detector
         # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
+        self._gm_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
@@ -159,6 +172,9 @@ class StreamingDetector:
         if ego_motion is not None and method == "flow" and flow_model is None:
             raise ValueError("ego_motion needs flow_model: the motion is fitted to the flow field "
                              "(method='scan_match' and method='keyframe' match the scans themselves)")
+        if grid_map is not None and ego_motion is not None and method == "flow":
+            raise ValueError("grid_map with ego_motion method='flow' is not built: use 'scan_match', 'keyframe' or "
+                             "'keyframe_map', or no ego_motion and det(scan, pose=...)")
         self._cls_thresh = float(cls_thresh)
         if tracks is not None and flow_model is None and person_motion is None:
             raise ValueError("tracks needs flow_model: the tracks are fed by the per-person flow")
@@ -173,7 +189,7 @@ class StreamingDetector:
         # scan runs them.
         self._terms = ()                # (rot, trans, flow_trans) where a per-person stage reads them
         self._prev_pose = None
-        if flow_model is not None or person_motion is not None:
+        if flow_model is not None or person_motion is not None or grid_map is not None:
             self._alloc_pose_terms(dev)
         keeps_scan = flow_model is not None or method == "scan_match"
         if keeps_scan:
@@ -202,12 +218,13 @@ class StreamingDetector:
             self._match_kw = _settings("ego_motion", ego, **match)
             self._match_out = ops.scan_match_buffers(self.B, self.N, dev)     # its motion is also the next step's init
             self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
-            if person_motion is not None:
+            from_first = person_motion is not None or grid_map is not None
+            if from_first:
                 # the first scan of a sequence has no pair to match: a pose launch without ok writes the pose terms
                 self._pm_no_ok = torch.zeros(self.B, dtype=torch.uint8, device=dev)
             stages.append(Stage(self._match_stage, (self._match_out.motion, self._pose_state),
                                 self._match_out.motion.zero_,                    # the first pair starts from rest
-                                from_first=person_motion is not None))
+                                from_first=from_first))
         if flow_model is not None:
             self._flow_model = flow_model.to(dev).eval()
             self._pf_out = ops.person_flow_buffers(self.B, self.N, dev)
@@ -234,6 +251,20 @@ class StreamingDetector:
             self._filter_kw = kw
             stages.append(Stage(self._track_stage, tuple(self._track_state),
                                 lambda: ops.track_reset(self._track_state), from_first=person_motion is not None))
+        if grid_map is not None:
+            kw = _settings("grid_map", grid_map, res=0.1, size=512, max_range=20.0, tol=None, hit=17, miss=8, lo=-40,
+                           hi=70, free_thresh=16)
+            size = kw.pop("size")
+            shape = tuple(int(s) for s in ((size, size) if np.ndim(size) == 0 else size))
+            if len(shape) != 2 or any(s % 64 or not 64 <= s <= 2048 for s in shape):
+                raise ValueError("grid_map size must be a multiple of 64 in [64, 2048] (or two of them, (H, W))")
+            if not float(kw["res"]) > 0.0:
+                raise ValueError("grid_map res must be > 0")
+            self._gm_kw = dict(kw, cls_thresh=self._cls_thresh)
+            self._gm_state = ops.grid_map_state(self.B, *shape, dev)
+            self._gm_out = ops.grid_map_buffers(self.B, self.N, dev)
+            self._gm_centre(np.zeros((self.B, 2)))
+            stages.append(Stage(self._grid_stage, tuple(self._gm_state), self._gm_state.grid.zero_))
         if keeps_scan:
             # not in a warm-up: the captured step behind it reads the scan before this one
             stages.append(Stage(self._keep_scan, warm_up=False))
@@ -277,6 +308,9 @@ class StreamingDetector:
                 np.asarray(pose.detach().cpu().numpy() if isinstance(pose, torch.Tensor) else pose,
                            dtype=np.float64).reshape(-1, 3), (self.B, 3)).copy()
             self._pose_state.copy_(torch.from_numpy(start))
+        if self._gm_kw is not None:
+            # a detector that is given its pose centres the grid again on the first pose of the sequence (_set_pose)
+            self._gm_centre(start[:, :2] if self._dead_reckons() else np.zeros((self.B, 2)))
 
     def _has_tracks(self):
         return self._filter_kw is not None
@@ -360,6 +394,17 @@ class StreamingDetector:
         o, (_, _, num, inst) = self._pf_out if self._pm_kw is None else self._pm_out, self._dets
         ops.track_update(o.det_xy_world, o.det_flow, o.det_valid, num, inst, self._track_state, **self._filter_kw)
 
+    # Behind the pose launch, on every scan of a sequence: the scan into the grid at this step's pose.
+    def _grid_stage(self, first):
+        ops.grid_map_update(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._gm_state,
+                            out=self._gm_out, **self._match_gate(), **self._gm_kw)
+
+    def _gm_centre(self, xy):
+        """The origin that puts the world positions xy [B,2] in the middle of their grids."""
+        H, W = self._gm_state.grid.shape[1:]
+        origin = np.asarray(xy, dtype=np.float64) - 0.5 * float(self._gm_kw["res"]) * np.array([W, H], dtype=np.float64)
+        self._gm_state.origin.copy_(torch.from_numpy(origin))
+
     def _keep_scan(self, first):
         self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
 
@@ -377,6 +422,8 @@ class StreamingDetector:
             cur = np.broadcast_to(cur.reshape(-1, 3), (self.B, 3)).copy()
         terms = _pose_terms(cur, self._prev_pose if cur is not None else None, batch=self.B)
         self._prev_pose = cur
+        if self._gm_kw is not None and self._seen == 0:
+            self._gm_centre(np.zeros((self.B, 2)) if cur is None else cur[:, :2])
         self._pose_copied.synchronize()               # the staging buffer's previous copy has left it
         for dst, src in zip(self._pose_host_np, (terms[1], terms[2], terms[0])):
             dst[...] = src
@@ -419,7 +466,7 @@ class StreamingDetector:
         if self._dead_reckons():
             if pose is not None:
                 raise ValueError("an ego_motion detector takes no pose: it dead-reckons its own (reset(pose=...))")
-        elif self._flow_model is not None or self._pm_kw is not None:
+        elif self._flow_model is not None or self._pm_kw is not None or self._gm_kw is not None:
             self._set_pose(pose)
         elif pose is not None:
             raise ValueError("pose is only used with a flow_model")
@@ -479,6 +526,15 @@ class StreamingDetector:
             raise RuntimeError("construct the detector with person_motion and feed it a scan first")
         return self._per_detection(self._pm_out, dets_xy_world="det_xy_world", person_flow="det_flow", count="det_count",
                                    centre="det_centre", prev="det_prev"), self._pm_out
+
+    def grid_map(self):
+        """-> (the device-resident ``ops.GridMapState``: grid [B,H,W] int16 log-odds counts and origin [B,2];  the
+        last step's ``ops.GridMapOut``: point_cell, point_mark, point_prior [B,N] and det_points, det_free [B,N] in
+        the row order of ``detections()``, valid until the next call).  Needs ``grid_map`` and one scan.  No
+        synchronisation: the tensors stay on the device."""
+        if self._gm_kw is None or self._seen < 1:
+            raise RuntimeError("construct the detector with grid_map and feed it a scan first")
+        return self._gm_state, self._gm_out
 
     def ego_motion(self):
         """-> list (one dict per sensor) of the last step's fit: motion [3] = (theta, u_x, u_y) since the previous

@@ -1,5 +1,5 @@
 """Per-kernel timing on the GPU box (events on torch's current stream, which is the
-stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] ..."""
+stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -219,3 +219,43 @@ if "person" in which:
             "max_tracks %d: %.3f ms, %.0f live tracks per sensor" % (M, ms_t[M], (tracks[M].track_id > 0).sum().item() / B)
             for M in tracks)))
 
+if "grid" in which:
+    # N12: the occupancy grid map, 450 beams into 512 x 512 cells of 0.1 m per sensor, for 1024, 8 and 1 sensors, next
+    # to person_motion on the same scans, NMS results and pose (alternating, three repeats of 50 launches).  The same
+    # scan every call, with lo / hi at the int16 limits so that no cell saturates inside the run and every launch
+    # stores what a first scan would.  Bytes: 2 * H * W * 2 per sensor is the bound of a launch that loads and stores
+    # the whole grid; `changed` counts the 16-byte runs one launch really stored, `near` the share of tiles that are
+    # not left at once (nearest point within max_range, or inside the box of the endpoints).
+    N, H, W, RES = 450, 512, 512, 0.1
+    rng = np.random.default_rng(1701)
+    tab = ops.phi_table()
+    for B in (1024, 8, 1):
+        scans = torch.from_numpy(synth.make_batch(seed=3, B=B, T=1).scans[:, 0].copy()).to(dev)
+        logit = np.stack([rng.permutation(N) for _ in range(B)]).astype(np.float64) / N * 8.0 - 4.0
+        cls = torch.from_numpy(1.0 / (1.0 + np.exp(-logit))).to(dev)
+        reg = torch.from_numpy(rng.normal(0, 0.3, (B, N, 2))).to(dev)
+        ang = rng.uniform(-np.pi, np.pi, B)
+        rot = torch.from_numpy(np.stack([np.cos(ang), -np.sin(ang), np.sin(ang), np.cos(ang)], 1).astype(np.float32)).to(dev)
+        trans = torch.from_numpy(rng.uniform(40, 120, (B, 2))).to(dev)
+        xy, dc, num, inst = ops.nms_predicted_center(scans, tab, cls, reg, 0.5)
+        pm_state, pm_out = ops.person_motion_state(B, N, dev), ops.person_motion_buffers(B, N, dev)
+        motion = lambda: ops.person_motion(scans, tab, inst, num, xy, dc, rot, trans, pm_state, out=pm_out)
+        gm_state, gm_out = ops.grid_map_state(B, H, W, dev), ops.grid_map_buffers(B, N, dev)
+        ops.grid_map_reset(gm_state, trans - 0.5 * RES * torch.tensor([W, H], dtype=torch.float64, device=dev))
+        grid = lambda: ops.grid_map_update(scans, tab, rot, trans, gm_state, res=RES, instance_mask=inst, num_det=num,
+                                           det_cls=dc, lo=-32767, hi=32767, out=gm_out)
+        grid()
+        before = gm_state.grid.clone()
+        grid()
+        runs = int((gm_state.grid != before).view(B, H, W // 8, 8).any(dim=3).sum().item())
+        touched = (gm_state.grid != 0).view(B, H // 64, 64, W // 64, 64).any(dim=4).any(dim=2).float().mean().item()
+        del before
+        for rep in range(3):
+            ms_g, ms_pm = timeit(grid, iters=50), timeit(motion, iters=50)
+            bound = B * 2 * H * W * 2
+            print("grid B=%d N=%d %dx%d at %.2f m: grid_map_update %.3f ms (%.2f us per sensor) next to person_motion %.3f ms; "
+                  "%.0f GB/s against the bound of 2*H*W*2 bytes per sensor, %.1f MB really stored (%d changed 16-byte runs), "
+                  "%.2f of the tiles hold a known cell; %.0f marked points per scan"
+                  % (B, N, H, W, RES, ms_g, ms_g / B * 1e3, ms_pm, bound / ms_g / 1e6, runs * 16 / 1e6, runs, touched,
+                     gm_out.point_mark.sum().item() / B))
+        del gm_state

@@ -1,5 +1,5 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
@@ -15,7 +15,9 @@ next to the scan matcher's, so one process gives the bare step, scan_match and k
 next to the keyframe matcher's, so one process gives the bare step, scan_match, keyframe and keyframe_map.
 --person-motion (with --ego=scan_match|keyframe|keyframe_map, without --flow; implies --nms for every step of the
 process): two more steps next to those, the chosen method's with person_motion=dict() as its tail and that one with
-tracks=dict() behind it, so one process gives the step without and with the person motion."""
+tracks=dict() behind it, so one process gives the step without and with the person motion.
+--grid (alone or with --nms): the replayed step with ego_motion=dict(method="keyframe") without and with
+grid_map=dict() (512 x 512 cells of 0.1 m per sensor) as its last stage, alternating repeats in one process."""
 import faulthandler, os, sys, time
 faulthandler.dump_traceback_later(90, exit=True)       # a stuck step reports where it is instead of hanging the box
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -36,7 +38,8 @@ KEYFRAME = dict(method="keyframe")
 KEYFRAME_MAP = dict(method="keyframe_map")
 KEYED = ("keyframe", "keyframe_map")
 TRACKS = "--tracks" in sys.argv
-sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--person-motion"))]
+GRID = "--grid" in sys.argv
+sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--person-motion", "--grid"))]
 
 
 class DiffFlow(torch.nn.Module):
@@ -56,10 +59,13 @@ model = SpatialDROW(num_scans=5, num_pts=56, alpha=0.5, window_size=11, pedestri
 model.fuse_for_inference(storage={"float32": torch.float32, "float16": torch.float16}[STORAGE], embed=EMBED)
 for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
     scans = torch.from_numpy(synth.make_batch(seed=9, B=B, T=40).scans).cuda()     # [B, 40, 450]
-    if EGO or TRACKS:
+    if EGO or TRACKS or GRID:
         poses = np.cumsum(np.random.default_rng(4).normal(0, 0.05, (40, B, 3)), axis=0)
         mk = lambda **kw: StreamingDetector(model, batch=B, nms_min_dist=NMS, flow_model=flow_model, **kw)
-        if TRACKS:
+        if GRID:
+            keyed_only, gridded = mk(ego_motion=KEYFRAME), mk(ego_motion=KEYFRAME, grid_map=dict())
+            steps = {"keyframe": lambda t: keyed_only(scans[:, t]), "keyframe + grid_map": lambda t: gridded(scans[:, t])}
+        elif TRACKS:
             kw = dict(ego_motion={"scan_match": MATCH, "keyframe": KEYFRAME, "keyframe_map": KEYFRAME_MAP}.get(EGO_METHOD, dict())) if EGO else {}
             plain, tracked = mk(tracks=None, **kw), mk(tracks=dict(), **kw)
             call = (lambda det, t: det(scans[:, t])) if EGO else (lambda det, t: det(scans[:, t], pose=poses[t]))
@@ -123,7 +129,12 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             print("   person_motion at the last scan: detections %s, paired %s; tracks: %s live, next_id %s"
                   % ([len(p["prev"]) for p in people], [int((p["prev"] >= 0).sum()) for p in people],
                      [len(l) for l in live], state.next_id.tolist()))
-        if TRACKS:
+        if GRID:
+            state, out = gridded.grid_map()
+            print("   grid_map after 40 scans: occupied cells %s, free cells %s, marked points of the last scan %s"
+                  % ((state.grid > 0).sum(dim=(1, 2)).tolist(), (state.grid < 0).sum(dim=(1, 2)).tolist(),
+                     out.point_mark.sum(dim=1).tolist()))
+        if TRACKS and not GRID:
             live, _, state = tracked.tracks()
             print("   tracks after 40 scans: %s live, next_id %s" % ([len(l) for l in live], state.next_id.tolist()))
         print("streaming step B=%d [flow %s%s], hipGraph replay per scan, 4 alternating repeats of 32 steps: %s"
