@@ -14,7 +14,7 @@
 // A solve fails with fewer than two points of w > 0 or S_pp not > 0.  Huber: w = w0 * (|e| > delta ? delta / |e| : 1),
 // `iters` times, i.e. iters + 1 solves.
 //
-// Every sum has a FIXED ORDER and no atomics: thread t holds the points t, t + THREADS, ... in kSlots register slots
+// The per-sensor workgroup of pof_sensor.h: thread t holds the points t, t + THREADS, ... in kSlots register slots
 // (coalesced loads) and adds them in slot order; the 64 lanes of a wave meet in a float64 __shfl_xor butterfly.  A
 // butterfly stage adds the same two numbers in both lanes and IEEE addition is commutative, so all 64 lanes end with
 // the same bits and every lane solves redundantly -- no broadcast.
@@ -27,14 +27,12 @@
 // the three terms pof_person_flow reads.
 #include <cmath>
 
-#include "pof_common.h"
+#include "pof_sensor.h"
 
 namespace {
 
-constexpr int kSlots = 8;          // points per thread
-constexpr int kWaveMaxN = 64 * kSlots;
-constexpr int kGroupThreads = 512;
-constexpr int kGroupMaxN = kGroupThreads * kSlots;
+using namespace pof_sensor;
+
 constexpr int kMaxIters = 16;
 
 struct EgoMotionArgs {
@@ -42,9 +40,8 @@ struct EgoMotionArgs {
     const double *xy, *tab;
     const void *flow;
     const float *weight;
-    const int32_t *instance_mask, *num_det;
-    const double *det_cls;
-    double cls_thresh, max_range, huber_delta;
+    NmsGate gate;
+    double max_range, huber_delta;
     int flow_f64, canonical, sign, model, iters, N;
     double *motion;
     int32_t *count;
@@ -80,11 +77,7 @@ __global__ __launch_bounds__(THREADS) void ego_motion_kernel(EgoMotionArgs a)
     const int N = a.N, b = blockIdx.x, tid = threadIdx.x;
     const long long row = (long long)b * N;
     const double sgn = (double)a.sign;
-    int nd = 0;
-    if (a.instance_mask) {
-        nd = a.num_det[b];
-        nd = nd < 0 ? 0 : (nd > N ? N : nd);
-    }
+    const int nd = a.gate.num(b, N);
 
     // slot c of thread t: point t + THREADS * c.  p, h (= q = p + g for the rigid model, g for the linear one), the
     // base weight and the weight of the solve at hand
@@ -127,10 +120,7 @@ __global__ __launch_bounds__(THREADS) void ego_motion_kernel(EgoMotionArgs a)
                 fy = (double)f1;
             }
             if (!isfinite(fx) || !isfinite(fy) || !isfinite(px[c]) || !isfinite(py[c])) wt = 0.0;
-            if (a.instance_mask) {
-                const int id = a.instance_mask[p];
-                if (id >= 1 && id <= nd && a.det_cls[row + id - 1] >= a.cls_thresh) wt = 0.0;
-            }
+            if (a.gate.is_person(row, i, nd)) wt = 0.0;
             hx[c] = sgn * fx;
             hy[c] = sgn * fy;
             if (a.model == 0) {
@@ -273,8 +263,8 @@ extern "C" int pof_ego_motion(const float *ranges, const double *xy, const doubl
     if (N > kGroupMaxN) return POF_E_SHAPE;                    // the limit of pof_nms_predicted_center
     if (B == 0) return POF_OK;
     EgoMotionArgs a;
-    a.ranges = ranges; a.xy = xy; a.tab = tab; a.flow = flow; a.weight = weight; a.instance_mask = instance_mask;
-    a.num_det = num_det; a.det_cls = det_cls; a.cls_thresh = cls_thresh; a.max_range = max_range;
+    a.ranges = ranges; a.xy = xy; a.tab = tab; a.flow = flow; a.weight = weight;
+    a.gate = {instance_mask, num_det, det_cls, cls_thresh}; a.max_range = max_range;
     a.huber_delta = huber_delta; a.flow_f64 = flow_f64; a.canonical = canonical; a.sign = sign; a.model = model;
     a.iters = iters; a.N = N; a.motion = motion; a.count = count; a.rms = rms; a.ok = ok;
     a.flow_residual = flow_residual; a.weight_out = weight_out;

@@ -1,11 +1,11 @@
 // N12: occupancy grid map, a per-sensor int16 log-odds grid updated per scan.  One entry point, two launches on the
 // caller's stream; include/pof_abi.h has the contract.
 //
-// (a) grid_points_kernel, one workgroup per sensor (one wave up to N = 512, 512 threads up to 4096, beams t, t + THREADS,
-//     ... per thread as in person_motion_kernel): per beam the endpoint in the world frame by N11's expressions, its
+// (a) grid_points_kernel, the per-sensor workgroup of pof_sensor.h (one wave up to N = 512, 512 threads up to 4096, beams
+//     t, t + THREADS, ... per thread): per beam the endpoint in the world frame by N11's expression (SensorPose), its
 //     cell (true division, floor, compared in double), the grid value there as the grid stands -- the cells launch runs
 //     behind it on the stream -- and whether the beam marks its cell (a hit inside the grid that is no person's point,
-//     pof_ego_motion's gate).  det_points / det_free are counted with integer LDS atomics: integer sums have no order.
+//     pof_ego_motion's gate: NmsGate).  det_points / det_free are counted with integer LDS atomics: integer sums have no order.
 // (b) grid_cells_kernel, one workgroup of 256 threads per (sensor, tile of 64 x 64 cells): a row of a tile is one
 //     128-byte line of int16, a thread owns 8 neighbouring cells of a row (one 16-byte load and store) in each of the
 //     two passes of 32 rows.  The tile's hit flags are staged in LDS from point_cell / point_mark (N int32 + N uint8 from
@@ -31,14 +31,12 @@
 // A tile wholly outside the field of view is not detected (not built).
 #include <cmath>
 
-#include "pof_common.h"
+#include "pof_sensor.h"
 
 namespace {
 
-constexpr int kSlots = 8;                       // beams per thread of the points launch
-constexpr int kWaveMaxN = 64 * kSlots;
-constexpr int kGroupThreads = 512;
-constexpr int kGroupMaxN = kGroupThreads * kSlots;
+using namespace pof_sensor;
+
 constexpr int kTile = 64;                       // cells per tile side: a row of int16 is one 128-byte line
 constexpr int kCellThreads = 256;
 constexpr int kRun = 8;                         // neighbouring cells per thread: 16 bytes
@@ -49,9 +47,8 @@ struct GridMapArgs {
     const double *tab;
     const float *rot;
     const double *trans;
-    const int32_t *instance_mask, *num_det;
-    const double *det_cls;
-    double res, tol, max_range, cls_thresh;
+    NmsGate gate;
+    double res, tol, max_range;
     int hit, miss, lo, hi, free_thresh, N, H, W;
     int16_t *grid;
     const double *origin;
@@ -62,58 +59,40 @@ struct GridMapArgs {
 };
 
 template <int THREADS>
-__device__ __forceinline__ void grid_points_order()
-{
-    if (THREADS == 64) {
-        // same-wave LDS hand-off (person_motion_order)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-
-template <int THREADS>
 __global__ __launch_bounds__(THREADS) void grid_points_kernel(GridMapArgs a)
 {
     constexpr int kMaxN = THREADS * kSlots;
     __shared__ int s_points[kMaxN], s_free[kMaxN];
     const int N = a.N, H = a.H, W = a.W, b = blockIdx.x, tid = threadIdx.x;
     const long long row = (long long)b * N;
-    const bool gated = a.instance_mask != nullptr;
-    int nd = gated ? __builtin_amdgcn_readfirstlane(a.num_det[b]) : 0;
-    nd = nd < 0 ? 0 : (nd > N ? N : nd);
-    const float *R = a.rot + 4 * (long long)b;
-    const float r00 = R[0], r01 = R[1], r10 = R[2], r11 = R[3];
-    const double tx = a.trans[2 * b], ty = a.trans[2 * b + 1];
+    const int nd = a.gate.num(b, N);
+    const SensorPose pose(a.rot, a.trans, b);
     const double ox = a.origin[2 * b], oy = a.origin[2 * b + 1];
     const int16_t *grid = a.grid + (long long)b * H * W;
 
     for (int k = tid; k < N; k += THREADS) s_points[k] = s_free[k] = 0;
-    grid_points_order<THREADS>();
+    pof_lds_order<THREADS>();
     for (int i = tid; i < N; i += THREADS) {
         const double r = (double)a.ranges[row + i];
         const bool hit = isfinite(r) && r > 0.0 && r < a.max_range;
-        const double px = r * a.tab[N + 2 * i], py = r * a.tab[N + 2 * i + 1];
-        const double wx = ((double)r00 * px + (double)r01 * py) + tx;
-        const double wy = ((double)r10 * px + (double)r11 * py) + ty;
+        double wx, wy;
+        pose.point_to_world(r * a.tab[N + 2 * i], r * a.tab[N + 2 * i + 1], wx, wy);
         const double gx = floor((wx - ox) / a.res), gy = floor((wy - oy) / a.res);
         const bool inside = hit && gx >= 0.0 && gx < (double)W && gy >= 0.0 && gy < (double)H;    // a NaN is outside
         const int cell = inside ? (int)gy * W + (int)gx : -1;
         const int prior = inside ? (int)grid[cell] : -32768;
-        const int id = gated ? a.instance_mask[row + i] : 0;
-        const bool row_of = id >= 1 && id <= nd;
-        const bool person = row_of && a.det_cls[row + id - 1] >= a.cls_thresh;
+        const int id = a.gate.id_of(row, i);
+        const int k = a.gate.row_of(id, nd);
+        const bool person = a.gate.id_is_person(row, id, nd);
         a.point_cell[row + i] = cell;
         a.point_prior[row + i] = (int16_t)prior;
         a.point_mark[row + i] = inside && !person ? 1 : 0;
-        if (inside && row_of) {
-            atomicAdd(&s_points[id - 1], 1);
-            if (prior <= -a.free_thresh) atomicAdd(&s_free[id - 1], 1);
+        if (inside && k >= 0) {
+            atomicAdd(&s_points[k], 1);
+            if (prior <= -a.free_thresh) atomicAdd(&s_free[k], 1);
         }
     }
-    grid_points_order<THREADS>();
+    pof_lds_order<THREADS>();
     for (int k = tid; k < N; k += THREADS) {
         a.det_points[row + k] = k < nd ? s_points[k] : 0;
         a.det_free[row + k] = k < nd ? s_free[k] : 0;
@@ -251,8 +230,8 @@ extern "C" int pof_grid_map_update(const float *ranges, const double *tab, const
     if ((long long)B * tiles > 0x7fffffffLL) return POF_E_SHAPE;
     if (B == 0) return POF_OK;
     GridMapArgs a;
-    a.ranges = ranges; a.tab = tab; a.rot = rot; a.trans = trans; a.instance_mask = instance_mask; a.num_det = num_det;
-    a.det_cls = det_cls; a.res = res; a.tol = tol; a.max_range = max_range; a.cls_thresh = cls_thresh; a.hit = hit;
+    a.ranges = ranges; a.tab = tab; a.rot = rot; a.trans = trans; a.gate = {instance_mask, num_det, det_cls, cls_thresh};
+    a.res = res; a.tol = tol; a.max_range = max_range; a.hit = hit;
     a.miss = miss; a.lo = lo; a.hi = hi; a.free_thresh = free_thresh; a.N = N; a.H = H; a.W = W; a.grid = grid;
     a.origin = origin; a.point_cell = point_cell; a.point_mark = point_mark; a.point_prior = point_prior;
     a.det_points = det_points; a.det_free = det_free;

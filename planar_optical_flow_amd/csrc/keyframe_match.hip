@@ -284,7 +284,7 @@ int keyframe_args(KeyframeArgs &a, const float *ranges_cur, const double *tab, c
     if (check_settings(window, gate, max_gap, huber_delta, iters, instance_mask, num_det, det_cls, B, N) != POF_OK)
         return POF_E_BADARG;
     if (!(key_dist >= 0.0) || !(key_rot >= 0.0) || !(min_share >= 0.0) || max_misses < 0) return POF_E_BADARG;
-    a.in = {ranges_cur, tab, instance_mask, num_det, det_cls, cls_thresh, max_range};
+    a.in = {ranges_cur, tab, {instance_mask, num_det, det_cls, cls_thresh}, max_range};
     a.set = {gate * gate, max_gap * max_gap, huber_delta, eps_theta, eps_u, min_pivot, window, iters};
     a.key_rot = key_rot; a.key_dist2 = key_dist * key_dist; a.min_share = min_share; a.max_misses = max_misses; a.N = N;
     a.key_ranges = key_ranges; a.key_pose = key_pose; a.key_rel = key_rel; a.key_valid = key_valid;

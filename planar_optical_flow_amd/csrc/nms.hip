@@ -171,13 +171,6 @@ struct NmsSmallArgs {
     double s2_thr;      // dist < min_dist  <=>  dx*dx + dy*dy <= s2_thr
 };
 
-__device__ __forceinline__ void nms_lds_order()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(64) void nms_wave_kernel(NmsSmallArgs A)
 {
     __shared__ double s_key[kSmallMaxN];     // score, sorted
@@ -193,7 +186,7 @@ __global__ __launch_bounds__(64) void nms_wave_kernel(NmsSmallArgs A)
         s_key[i] = cls[i];
         s_ord[i] = i;
     }
-    nms_lds_order();
+    pof_lds_order<64>();
     // bitonic network, all-ascending form, on the total order "u comes before v": (score, point index)
     // descending; a NaN score comes after every number (NumPy sorts NaNs to the end of the ascending order, the
     // reference reverses it -- its NaNs lead; either way the order among NaNs is by point index and a scan with
@@ -221,13 +214,13 @@ __global__ __launch_bounds__(64) void nms_wave_kernel(NmsSmallArgs A)
             const int blk = t / hk, off = t - blk * hk;
             cmpx(blk * k + off, blk * k + k - 1 - off);
         }
-        nms_lds_order();
+        pof_lds_order<64>();
         for (int j = k >> 2; j > 0; j >>= 1) {
             for (int t = lane; t < half; t += 64) {
                 const int lo = 2 * j * (t / j) + (t % j);
                 cmpx(lo, lo + j);
             }
-            nms_lds_order();
+            pof_lds_order<64>();
         }
     }
     // centres of this lane's columns (sorted positions lane + 64 c)
@@ -254,7 +247,7 @@ __global__ __launch_bounds__(64) void nms_wave_kernel(NmsSmallArgs A)
         }
         alive[c] = __ballot(i < N);
     }
-    nms_lds_order();
+    pof_lds_order<64>();
     // greedy walk over the kept centres
     int nkept = 0;
     while (true) {
@@ -276,7 +269,7 @@ __global__ __launch_bounds__(64) void nms_wave_kernel(NmsSmallArgs A)
             if ((i >> 6) == c) alive[c] &= ~(1ull << (i & 63));
         }
     }
-    nms_lds_order();
+    pof_lds_order<64>();
     int32_t *inst = a.instance_mask + (long long)b * N;
 #pragma unroll
     for (int c = 0; c < kCols; ++c) {

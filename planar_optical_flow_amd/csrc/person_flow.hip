@@ -13,25 +13,19 @@
 // np.mean of an empty selection.
 //
 // The sums are SEQUENTIAL IN POINT ORDER with plain float64 adds: no atomics, nothing that depends on scheduling, so
-// a result is the same bits in every run and in a graph replay.  A workgroup stages (id, wx, wy, r, g, b) of up to
-// kChunk points in LDS; thread t owns the instances t, t + THREADS, ... (kSlots accumulators in registers); every
-// thread then walks the staged points in index order.  All lanes read the same LDS address each step -- a broadcast,
-// no bank conflict -- and the instance id is wave-uniform, so picking the accumulator is a scalar branch and only
-// the owning lane adds.  A wave none of whose lanes owns the id skips the point.
-//   N <= 512:  one wave per scan (THREADS = 64, 8 slots), wave-level ordering only, as nms_wave_kernel;
-//   N <= 4096: 512 threads per scan, points in chunks of 512 between workgroup barriers, same point order.
+// a result is the same bits in every run and in a graph replay.  The per-sensor workgroup of pof_sensor.h: it stages
+// (id, wx, wy, r, g, b) of up to kChunk points in LDS; thread t owns the instances t, t + THREADS, ... (kSlots
+// accumulators in registers); every wave then walks the staged points in index order and only the owning lane adds
+// (pof_sensor::row_sums).  One wave per scan up to N = 512, 512 threads and chunks of 512 points between workgroup
+// barriers up to N = 4096, the same point order in both.
 // Latency bound like the NMS it follows; reported in microseconds.
 #include <cmath>
 
-#include "pof_common.h"
+#include "pof_sensor.h"
 
 namespace {
 
-constexpr int kChunk = 512;        // points staged in LDS at a time
-constexpr int kSlots = 8;          // instances per thread
-constexpr int kWaveMaxN = 64 * kSlots;
-constexpr int kGroupThreads = 512;
-constexpr int kGroupMaxN = kGroupThreads * kSlots;
+using namespace pof_sensor;
 
 struct PersonFlowArgs {
     const float *flow_canonical;
@@ -73,29 +67,15 @@ __device__ __forceinline__ void flow_colour(double wx, double wy, double &cr, do
 }
 
 template <int THREADS>
-__device__ __forceinline__ void person_flow_order()
-{
-    if (THREADS == 64) {
-        // same-wave LDS hand-off (nms_lds_order): the hardware keeps a wave's LDS operations in order
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-
-template <int THREADS>
 __global__ __launch_bounds__(THREADS) void person_flow_kernel(PersonFlowArgs a)
 {
     __shared__ double s_v[5][kChunk];       // wx, wy, r, g, b of the staged points
     __shared__ int s_id[kChunk];
     const int N = a.N, b = blockIdx.x, tid = threadIdx.x;
     const long long row = (long long)b * N;
-    int nd = a.num_det[b];
-    nd = nd < 0 ? 0 : (nd > N ? N : nd);
-    const float *R = a.rot + 4 * (long long)b;                 // rot[b] row-major; Rt[r][c] = R[2 c + r]
-    const float r00 = R[0], r01 = R[1], r10 = R[2], r11 = R[3];
+    const int nd = clamped_num_det(a.num_det, b, N);
+    const SensorPose pose(a.rot, a.trans, b);                  // Rt[r][c] = rot[b][c][r]
+    const float r00 = pose.r00, r01 = pose.r01, r10 = pose.r10, r11 = pose.r11;
     const double ftx = a.flow_trans[2 * b], fty = a.flow_trans[2 * b + 1];
 
     double acc[kSlots][5];
@@ -106,9 +86,6 @@ __global__ __launch_bounds__(THREADS) void person_flow_kernel(PersonFlowArgs a)
 #pragma unroll
         for (int j = 0; j < 5; ++j) acc[c][j] = 0.0;
     }
-    // the wave that holds thread (k % THREADS) owns instance k
-    const int my_wave = tid >> 6;
-
     for (int base = 0; base < N; base += kChunk) {
         const int n = N - base < kChunk ? N - base : kChunk;
         for (int j = tid; j < n; j += THREADS) {
@@ -135,30 +112,11 @@ __global__ __launch_bounds__(THREADS) void person_flow_kernel(PersonFlowArgs a)
             s_v[4][j] = cb;
             s_id[j] = a.instance_mask[p];
         }
-        person_flow_order<THREADS>();
-        for (int j = 0; j < n; ++j) {
-            // every lane reads the same address: the id is wave-uniform, so it can live in a scalar register
-            const int k = __builtin_amdgcn_readfirstlane(s_id[j]) - 1;
-            if (k < 0 || k >= nd) continue;                    // id 0 (no centre) and ids beyond num_det
-            const int owner = k % THREADS, slot = k / THREADS;
-            if ((owner >> 6) != my_wave) continue;
-            const double v0 = s_v[0][j], v1 = s_v[1][j], v2 = s_v[2][j], v3 = s_v[3][j], v4 = s_v[4][j];
-#pragma unroll
-            for (int c = 0; c < kSlots; ++c) {
-                if (c == slot && tid == owner) {
-                    acc[c][0] += v0;
-                    acc[c][1] += v1;
-                    acc[c][2] += v2;
-                    acc[c][3] += v3;
-                    acc[c][4] += v4;
-                    ++cnt[c];
-                }
-            }
-        }
-        person_flow_order<THREADS>();                          // the next chunk overwrites the staged points
+        pof_lds_order<THREADS>();
+        row_sums<THREADS>(s_id, s_v, n, nd, acc, cnt);         // id 0 (no centre) and ids beyond num_det: nobody's
+        pof_lds_order<THREADS>();                              // the next chunk overwrites the staged points
     }
 
-    const double tx = a.trans[2 * b], ty = a.trans[2 * b + 1];
 #pragma unroll
     for (int c = 0; c < kSlots; ++c) {
         const int k = tid + THREADS * c;
@@ -168,9 +126,7 @@ __global__ __launch_bounds__(THREADS) void person_flow_kernel(PersonFlowArgs a)
         int count = 0;
         uint8_t valid = 0;
         if (k < nd) {
-            const double d0 = a.det_xy[2 * q], d1 = a.det_xy[2 * q + 1];
-            ox = fma(d1, (double)r01, d0 * (double)r00) + tx;
-            oy = fma(d1, (double)r11, d0 * (double)r10) + ty;
+            pose.det_to_world(a.det_xy[2 * q], a.det_xy[2 * q + 1], ox, oy);
             count = cnt[c];
             const double m = (double)count;                    // 0 / 0 -> NaN, like np.mean of nothing
 #pragma unroll

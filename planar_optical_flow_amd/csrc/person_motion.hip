@@ -6,17 +6,17 @@
 // so pof_track_update consumes it unchanged.  include/pof_abi.h has the contract.
 //   1. points: p = r (cos, sin) in float64 from tab, w = ((double)R00 p_x + (double)R01 p_y) + t_x (likewise y); a point
 //      counts for row k when instance_mask = k + 1 and r is finite and < max_range
-//   2. det_centre[k] = the sum of its points' w, added in ascending point index (the walk of person_flow_kernel),
-//      divided by det_count[k]; det_xy_world / det_valid by pof_person_flow's expressions
+//   2. det_centre[k] = the sum of its points' w, added in ascending point index (pof_sensor::row_sums, the walk of
+//      pof_person_flow), divided by det_count[k]; det_xy_world / det_valid by pof_person_flow's expressions
 //   3. candidates: det_valid, det_count >= min_points, a finite centre
 //   4. best(k) = the previous candidate j of smallest d2 = dx dx + dy dy, j upwards with a strict <, while d2 <= reach^2;
 //      every previous candidate has a best current candidate by the same rule, k upwards; a pair is mutual
 //   5. det_flow[k] = det_centre[k] - prev_centre[j], det_prev[k] = j; NaN and -1 without a pair
 //   6. after a barrier the state becomes this scan's centres, candidate flags and num_det
 //
-// Shape: thread t owns the rows t, t + THREADS, ... (kSlots of them, in registers) of this scan and of the previous one.
-// The points go through LDS in chunks of kChunk as in person_flow_kernel and are summed in its order: every wave steps
-// through the staged points in ascending index, the instance id is wave-uniform, only the owning lane adds.  The centres
+// Shape: the per-sensor workgroup of pof_sensor.h; thread t owns the rows t, t + THREADS, ... (kSlots of them, in
+// registers) of this scan and of the previous one.  The points go through LDS in chunks of kChunk and are summed per row
+// by row_sums: every wave steps through the staged points in ascending index, only the owning lane adds.  The centres
 // of both scans then stand whole in LDS, a row that is no candidate as NaN -- a NaN distance is never inside the reach,
 // so the search needs no flag -- and every thread goes over the other scan's candidate centres in row order for the
 // rows it owns.  Both walks take 64 entries at a time from LDS into a wave's registers and step through the set bits of
@@ -31,15 +31,11 @@
 // Latency bound like the launches it follows; the pairwise search is num_det * prev_num / THREADS distances per thread.
 #include <cmath>
 
-#include "pof_common.h"
+#include "pof_sensor.h"
 
 namespace {
 
-constexpr int kChunk = 512;        // points staged in LDS at a time
-constexpr int kSlots = 8;          // rows per thread
-constexpr int kWaveMaxN = 64 * kSlots;
-constexpr int kGroupThreads = 512;
-constexpr int kGroupMaxN = kGroupThreads * kSlots;
+using namespace pof_sensor;
 
 struct PersonMotionArgs {
     const float *ranges;
@@ -60,32 +56,6 @@ struct PersonMotionArgs {
 };
 
 template <int THREADS>
-__device__ __forceinline__ void person_motion_order()
-{
-    if (THREADS == 64) {
-        // same-wave LDS hand-off (person_flow_order): the hardware keeps a wave's LDS operations in order
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-
-// An empty statement the compiler may not speculate: a block that holds it stays behind its branch.  Without it the
-// compiler turns the wave-uniform tests on the register slot into selects and runs the float64 work of all kSlots slots
-// for every entry, which is most of the launch's time.
-__device__ __forceinline__ void keep_branch() { asm volatile(""); }
-
-// the value lane l of the wave holds; l is wave-uniform
-__device__ __forceinline__ double lane_value(double v, int l)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
-template <int THREADS>
 __global__ __launch_bounds__(THREADS) void person_motion_kernel(PersonMotionArgs a)
 {
     constexpr int kMaxN = THREADS * kSlots;
@@ -96,15 +66,10 @@ __global__ __launch_bounds__(THREADS) void person_motion_kernel(PersonMotionArgs
     __shared__ int s_back[kMaxN];           // previous row -> its best current row, or -1
     const int N = a.N, b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const long long row = (long long)b * N;
-    int nd = __builtin_amdgcn_readfirstlane(a.num_det[b]);     // one value for the workgroup: scalar loop bounds
-    nd = nd < 0 ? 0 : (nd > N ? N : nd);
-    int pn = __builtin_amdgcn_readfirstlane(a.prev_num[b]);
-    pn = pn < 0 ? 0 : (pn > N ? N : pn);
+    const int nd = clamped_num_det(a.num_det, b, N), pn = clamped_num_det(a.prev_num, b, N);   // scalar loop bounds
     // rows t, t + THREADS, ...: only the first ceil(rows / THREADS) register slots of a thread can hold a row
     const int cur_slots = (nd + THREADS - 1) / THREADS, prev_slots = (pn + THREADS - 1) / THREADS;
-    const float *R = a.rot + 4 * (long long)b;                 // rot[b] row-major
-    const float r00 = R[0], r01 = R[1], r10 = R[2], r11 = R[3];
-    const double tx = a.trans[2 * b], ty = a.trans[2 * b + 1];
+    const SensorPose pose(a.rot, a.trans, b);
     const double qnan = __builtin_nan(""), inf = __builtin_inf();
     const double reach2 = a.reach * a.reach;
 
@@ -115,50 +80,18 @@ __global__ __launch_bounds__(THREADS) void person_motion_kernel(PersonMotionArgs
         cnt[c] = 0;
         acc[c][0] = acc[c][1] = 0.0;
     }
-    // the wave that holds thread (k % THREADS) owns row k
-    const int my_wave = tid >> 6;
-
     // 1., 2. the sums of the points' world positions per row, in point order
     for (int base = 0; base < N; base += kChunk) {
         const int n = N - base < kChunk ? N - base : kChunk;
         for (int j = tid; j < n; j += THREADS) {
             const int i = base + j;
             const double r = (double)a.ranges[row + i];
-            const double px = r * a.tab[N + 2 * i], py = r * a.tab[N + 2 * i + 1];
-            s_prev[0][j] = ((double)r00 * px + (double)r01 * py) + tx;
-            s_prev[1][j] = ((double)r10 * px + (double)r11 * py) + ty;
-            s_id[j] = isfinite(r) && r < a.max_range ? a.instance_mask[row + i] : 0;
+            pose.point_to_world(r * a.tab[N + 2 * i], r * a.tab[N + 2 * i + 1], s_prev[0][j], s_prev[1][j]);
+            s_id[j] = isfinite(r) && r < a.max_range ? a.instance_mask[row + i] : 0;   // 0: left out
         }
-        person_motion_order<THREADS>();
-        // the walk of person_flow_kernel, point order kept, without an LDS round trip per point: a wave takes 64 staged
-        // points into registers at once -- lane l holds point j0 + l -- and steps through those that are somebody's in
-        // ascending l; id and position come out of the lane by v_readlane, so they are wave-uniform
-        for (int j0 = 0; j0 < n; j0 += 64) {
-            const int mine = j0 + lane;                        // < kChunk: j0 is a multiple of 64 below it
-            const int id = mine < n ? s_id[mine] : 0;
-            const double wx = s_prev[0][mine], wy = s_prev[1][mine];
-            unsigned long long todo = __ballot(id >= 1 && id <= nd);   // id 0 (no centre, or left out), ids beyond num_det
-            while (todo) {
-                const int l = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const int k = __builtin_amdgcn_readlane(id, l) - 1;
-                const int owner = k % THREADS, slot = k / THREADS;
-                if ((owner >> 6) != my_wave) continue;
-                const double v0 = lane_value(wx, l), v1 = lane_value(wy, l);
-#pragma unroll
-                for (int c = 0; c < kSlots; ++c) {
-                    if (c == slot) {                           // wave-uniform: a scalar branch
-                        keep_branch();
-                        if (tid == owner) {
-                            acc[c][0] += v0;
-                            acc[c][1] += v1;
-                            ++cnt[c];
-                        }
-                    }
-                }
-            }
-        }
-        person_motion_order<THREADS>();                        // the next chunk overwrites the staged points
+        pof_lds_order<THREADS>();
+        row_sums<THREADS>(s_id, s_prev, n, nd, acc, cnt);
+        pof_lds_order<THREADS>();                              // the next chunk overwrites the staged points
     }
 
     // 2., 3. the rows this thread owns: of this scan into registers and LDS, of the previous scan into LDS
@@ -175,9 +108,7 @@ __global__ __launch_bounds__(THREADS) void person_motion_kernel(PersonMotionArgs
         }
         const long long q = row + k;
         if (k < nd) {
-            const double d0 = a.det_xy[2 * q], d1 = a.det_xy[2 * q + 1];
-            ox[c] = fma(d1, (double)r01, d0 * (double)r00) + tx;
-            oy[c] = fma(d1, (double)r11, d0 * (double)r10) + ty;
+            pose.det_to_world(a.det_xy[2 * q], a.det_xy[2 * q + 1], ox[c], oy[c]);
             const double m = (double)cnt[c];                   // 0 / 0 -> NaN, like np.mean of nothing
             cx[c] = acc[c][0] / m;
             cy[c] = acc[c][1] / m;
@@ -192,7 +123,7 @@ __global__ __launch_bounds__(THREADS) void person_motion_kernel(PersonMotionArgs
         s_prev[0][k] = was ? a.prev_centre[2 * q] : qnan;
         s_prev[1][k] = was ? a.prev_centre[2 * q + 1] : qnan;
     }
-    person_motion_order<THREADS>();
+    pof_lds_order<THREADS>();
 
     // 4. the best previous row of every row this thread owns: j upwards, strict <
     double bd[kSlots];
@@ -274,7 +205,7 @@ __global__ __launch_bounds__(THREADS) void person_motion_kernel(PersonMotionArgs
             if (j < N) s_back[j] = rk[c];
         }
     }
-    person_motion_order<THREADS>();
+    pof_lds_order<THREADS>();
 
     // 5. the outputs of the rows this thread owns
     double fx[kSlots], fy[kSlots];
@@ -293,7 +224,7 @@ __global__ __launch_bounds__(THREADS) void person_motion_kernel(PersonMotionArgs
             partner[c] = j;
         }
     }
-    person_motion_order<THREADS>();                            // 6. every read of the state is behind this barrier
+    pof_lds_order<THREADS>();                                  // 6. every read of the state is behind this barrier
 #pragma unroll
     for (int c = 0; c < kSlots; ++c) {
         const int k = tid + THREADS * c;

@@ -84,6 +84,22 @@ __device__ __forceinline__ void pof_write_pose_terms(int b, double x, double y, 
     }
 }
 
+// Orders the LDS traffic of a workgroup of THREADS: what a thread wrote in front of it, every thread reads behind it.
+// A workgroup of one wave needs no s_barrier for that: the hardware executes a wave's LDS operations in program
+// order, so it is enough that the compiler neither moves them across this point (the two fences) nor lets the lanes
+// of the wave drift apart around it (wave_barrier).  More than one wave meet in __syncthreads().
+template <int THREADS>
+__device__ __forceinline__ void pof_lds_order()
+{
+    if (THREADS == 64) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+
 __device__ __forceinline__ double wave_max_f64(double v)
 {
 #pragma unroll

@@ -36,20 +36,19 @@
 //
 // The reference vertices are staged once in LDS (two doubles per beam, NaN = not valid; 64 KB at N = 4096).  Thread t
 // holds the points t, t + THREADS, ... in kSlots register slots and adds them in slot order; the sums meet in
-// group_sum (pof_common.h): a FIXED ORDER, no atomics, and with -ffp-contract=off no FMA.  Every lane ends with the
-// same bits, solves redundantly, and the iteration loop and its exit are uniform.
-//   N <= 512:  one wave per workgroup;   N <= 4096: 512 threads per workgroup.
+// group_sum (pof_common.h): the per-sensor workgroup of pof_sensor.h, its slot layout, launch forms and fixed order.
+// Every lane ends with the same bits, solves redundantly, and the iteration loop and its exit are uniform.
 #pragma once
 #include <cmath>
 
-#include "pof_common.h"
+#include "pof_sensor.h"
 
 namespace pof_icp {
 
-constexpr int kSlots = 8;          // points per thread
-constexpr int kWaveMaxN = 64 * kSlots;
-constexpr int kGroupThreads = 512;
-constexpr int kGroupMaxN = kGroupThreads * kSlots;
+using pof_sensor::kGroupMaxN;
+using pof_sensor::kGroupThreads;
+using pof_sensor::kSlots;
+using pof_sensor::kWaveMaxN;
 constexpr int kMaxIters = 32;
 constexpr int kMaxWindow = 64;
 constexpr int kSums = 12;
@@ -58,9 +57,8 @@ constexpr int kSums = 12;
 struct Input {
     const float *ranges_cur;
     const double *tab;
-    const int32_t *instance_mask, *num_det;
-    const double *det_cls;
-    double cls_thresh, max_range;
+    pof_sensor::NmsGate gate;
+    double max_range;
 };
 
 // Input and Settings are passed by value, and window / gate2 / gap2 to `correspond` as scalars: through references the
@@ -106,11 +104,7 @@ __device__ __forceinline__ double stage(const Input in, const float *ranges_ref,
     const int tid = threadIdx.x;
     const long long row = (long long)b * N;
     const double qnan = __builtin_nan("");
-    int nd = 0;
-    if (in.instance_mask) {
-        nd = in.num_det[b];
-        nd = nd < 0 ? 0 : (nd > N ? N : nd);
-    }
+    const int nd = in.gate.num(b, N);
     double votes = 0.0;
 #pragma unroll
     for (int c = 0; c < kSlots; ++c) {
@@ -124,10 +118,7 @@ __device__ __forceinline__ double stage(const Input in, const float *ranges_ref,
             ax[i] = v0 ? (double)r0 * cs : qnan;
             ay[i] = v0 ? (double)r0 * sn : qnan;
             bool v1 = isfinite(r1) && (double)r1 < in.max_range;
-            if (in.instance_mask) {
-                const int id = in.instance_mask[row + i];
-                if (id >= 1 && id <= nd && in.det_cls[row + id - 1] >= in.cls_thresh) v1 = false;
-            }
+            if (in.gate.is_person(row, i, nd)) v1 = false;
             px[c] = (double)r1 * cs;
             py[c] = (double)r1 * sn;
             valid[c] = v1;

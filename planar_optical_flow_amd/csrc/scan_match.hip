@@ -114,7 +114,7 @@ extern "C" int pof_scan_match(const float *ranges_prev, const float *ranges_cur,
     if (N > kGroupMaxN) return POF_E_SHAPE;                    // the limit of pof_ego_motion and the NMS
     if (B == 0) return POF_OK;
     ScanMatchArgs a;
-    a.in = {ranges_cur, tab, instance_mask, num_det, det_cls, cls_thresh, max_range};
+    a.in = {ranges_cur, tab, {instance_mask, num_det, det_cls, cls_thresh}, max_range};
     a.set = {gate * gate, max_gap * max_gap, huber_delta, eps_theta, eps_u, min_pivot, window, iters};
     a.ranges_prev = ranges_prev; a.init = init; a.N = N;
     a.motion = motion; a.count = count; a.rms = rms; a.ok = ok; a.iters_used = iters_used; a.obs = obs; a.corr = corr;

@@ -75,19 +75,13 @@ __device__ __forceinline__ int block_exclusive(int cnt, int *s_part, int tid, in
 // mirrors the upper half, so every compare-exchange puts the smaller value at the lower index): with that form
 // the padding to a power of two is virtual -- a pair whose upper index is >= n is skipped, as if +inf sat there
 // -- and the copy needs exactly the segment's own slots of a scratch row shared by the workgroup (segments are
-// disjoint).  45 steps x 4 pairs per lane for n = 400.  One wave: its LDS operations are ordered, no barrier.
-__device__ __forceinline__ void wave_lds_order()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
+// disjoint).  45 steps x 4 pairs per lane for n = 400.  One wave: its LDS operations are ordered, no barrier
+// (pof_lds_order<64>).
 __device__ __forceinline__ double wave_median(const double *v, double *scratch, int p0, int n, int lane)
 {
     double *w = scratch + p0;
     for (int i = lane; i < n; i += POF_WAVE) w[i] = v[p0 + i];
-    wave_lds_order();
+    pof_lds_order<POF_WAVE>();
     int npad = 1;
     while (npad < n) npad <<= 1;
     const int half = npad >> 1;
@@ -106,17 +100,17 @@ __device__ __forceinline__ double wave_median(const double *v, double *scratch, 
             const int blk = t / hk, off = t - blk * hk;
             cmpx(blk * k + off, blk * k + k - 1 - off);
         }
-        wave_lds_order();
+        pof_lds_order<POF_WAVE>();
         for (int j = k >> 2; j > 0; j >>= 1) {                 // half cleaners
             for (int t = lane; t < half; t += POF_WAVE) {
                 const int lo = 2 * j * (t / j) + (t % j);
                 cmpx(lo, lo + j);
             }
-            wave_lds_order();
+            pof_lds_order<POF_WAVE>();
         }
     }
     const double m = (w[(n - 1) >> 1] + w[n >> 1]) / 2.0;      // NumPy: mean of the two middle elements
-    wave_lds_order();
+    pof_lds_order<POF_WAVE>();
     return m;
 }
 

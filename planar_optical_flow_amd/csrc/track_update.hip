@@ -26,7 +26,7 @@
 #include <climits>
 #include <cmath>
 
-#include "pof_common.h"
+#include "pof_sensor.h"                                         // clamped_num_det only: the slot scheme here is its own
 
 namespace {
 
@@ -62,8 +62,7 @@ __global__ __launch_bounds__(64) void track_update_kernel(TrackArgs a)
     const unsigned long long below = (1ull << lane) - 1ull;
     const double qnan = __builtin_nan(""), inf = __builtin_inf();
     const double gate2 = a.gate * a.gate;
-    int nd = a.num_det[b];
-    nd = nd < 0 ? 0 : (nd > N ? N : nd);
+    const int nd = pof_sensor::clamped_num_det(a.num_det, b, N);
     const int first_id = a.next_id[b];
 
     int id[J], hits[J], misses[J], age[J], match[J], bi[J];

@@ -150,8 +150,8 @@ def _table(N):
 
 def _synthetic(N, seed):
     """B = 3 scans with synthetic masks.  Scan 0: one instance owns every point.  Scan 1: every point its own
-    instance, in a shuffled order (num_det = N).  Scan 2: ids drawn from [0, nd + 2] with num_det = nd -- id 0 and
-    ids above num_det occur, and id 2 never does (an instance without points)."""
+    instance, in a shuffled order (num_det = N).  Scan 2: ids drawn from [0, nd + 2] with num_det = nd -- id 0, one
+    negative id and ids above num_det occur, and id 2 never does (an instance without points)."""
     rng = np.random.default_rng(seed)
     inst = np.zeros((3, N), np.int32)
     inst[0] = 1
@@ -161,6 +161,7 @@ def _synthetic(N, seed):
     ids[ids == 2] = 3 if nd >= 3 else 0
     if N >= 8:
         ids[:5] = (0, nd + 1, nd + 2, 1, 3)
+        ids[5] = -3
     inst[2] = ids
     num = np.array([1, N, nd], np.int32)
     flow = rng.normal(0, 0.05, (3, N, 2)).astype(np.float32)
@@ -176,10 +177,11 @@ def _synthetic(N, seed):
     return inst, num, flow, det_xy, det_cls, rot, trans, ftr
 
 
-@pytest.mark.parametrize("N", [1, 64, 65, 450, 512, 513])
+@pytest.mark.parametrize("N", [1, 64, 65, 450, 512, 513, 577])
 def test_wave_and_workgroup_forms_at_their_sizes(ops, u, N):
     """N <= 512 is the one-wave form (partial last column at 65 and 450, full columns at 64 and 512), 513 the
-    workgroup form with a second chunk of one point."""
+    workgroup form with a second chunk of one point, 577 with a second chunk of 65: a wave's walk takes one full group
+    of 64 staged points and a group of one."""
     inst, num, flow, det_xy, det_cls, rot, trans, ftr = _synthetic(N, 40 + N)
     phi, tab = _table(N)
     args = (_cuda(flow), _cuda(tab), _cuda(inst), _cuda(num), _cuda(det_xy), _cuda(det_cls), _cuda(rot), _cuda(trans),
