@@ -7,6 +7,8 @@ tensor raises.
 """
 import collections
 import ctypes as C
+import functools
+import inspect
 
 import numpy as np
 import torch
@@ -917,18 +919,98 @@ def nms_predicted_center(ranges, tab, pred_cls, pred_reg, min_dist=0.5):
     return det_xy, det_cls, num, inst
 
 
-PersonFlow = collections.namedtuple("PersonFlow", ("flow_global", "flow_world", "rgb", "det_xy_world", "det_flow",
-                                                    "det_rgb", "det_count", "det_valid"))
-_PERSON_FLOW_OUT = (("flow_global", torch.float32, 2), ("flow_world", torch.float64, 2), ("rgb", torch.float64, 3),
-                    ("det_xy_world", torch.float64, 2), ("det_flow", torch.float64, 2), ("det_rgb", torch.float64, 3),
-                    ("det_count", torch.int32, 0), ("det_valid", torch.uint8, 0))
+# ---------------------------------------------------------------------------------------------------------------------
+# The per-scan stages N5-N12.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
+# a dtype and a symbolic shape per field.  ``_zeros_of`` allocates a record, ``_checked`` takes a caller's and
+# ``_out_of`` does whichever an ``out=`` needs; ``stage_settings`` reads a wrapper's tunable scalars off its signature.
+def _record(name, persistent=None, **fields):
+    """The namedtuple class ``name`` with one field per keyword, in their order: field=(dtype, *dims), a dim being a
+    number or the name of a size ("B" sensors, "N" points, "K" keys, "M" track slots, "H" x "W" cells).  The fields of
+    the dict ``persistent`` come first and are the ones that carry over from scan to scan (``cls.persistent``, their
+    names); ``cls.spec`` is the (dtype, dims) of every field."""
+    fields = dict(persistent or {}, **fields)
+    cls = collections.namedtuple(name, tuple(fields))
+    cls.spec = tuple((dt, dims) for dt, *dims in fields.values())
+    cls.persistent = tuple(persistent or ())
+    return cls
+
+
+@functools.lru_cache(maxsize=256)
+def _shapes_of(cls, **sizes):
+    """The shape of every field of the record ``cls`` for the given sizes (B=..., N=...).  Cached: a stage is called
+    with the same sizes scan after scan, and the per-call checks then resolve no name."""
+    return tuple(tuple(sizes.get(d, d) for d in dims) for _, dims in cls.spec)
+
+
+def _zeros_of(cls, device, **sizes):
+    """The record ``cls`` of zero-filled tensors for the given sizes."""
+    return cls(*(torch.zeros(shape, dtype=dt, device=device)
+                 for (dt, _), shape in zip(cls.spec, _shapes_of(cls, **sizes))))
+
+
+def _checked(cls, tensors, prefix, **sizes):
+    """A caller's tensors as the record ``cls``: each on the device, of its dtype, contiguous and of its shape for the
+    given sizes; an error names ``prefix.field``."""
+    rec = tensors if type(tensors) is cls else cls(*tensors)
+    for name, (dt, _), shape, t in zip(cls._fields, cls.spec, _shapes_of(cls, **sizes), rec):
+        _dev(t, dt, prefix + "." + name)
+        if t.shape != shape:
+            raise ValueError("%s.%s has the wrong shape" % (prefix, name))
+    return rec
+
+
+def _out_of(cls, out, device, **sizes):
+    """A stage's ``out=``: the caller's record, checked, or a fresh one."""
+    return _zeros_of(cls, device, **sizes) if out is None else _checked(cls, out, "out", **sizes)
+
+
+_STAGE_TENSORS = frozenset(("init", "xy", "weight", "instance_mask", "num_det", "det_cls", "out", "rot", "trans",
+                            "flow_trans"))
+REQUIRED = inspect.Parameter.empty
+
+
+def stage_settings(wrapper):
+    """The settings of a per-scan stage -- the keyword-only arguments of its wrapper (``scan_match``, ``track_update``,
+    ...) that are scalars a user tunes, not tensors -- with the defaults its signature gives them: a fresh {name:
+    default}, ``REQUIRED`` for a setting without one.  What wraps a stage (``StreamingDetector``, the classes of
+    ``utils``) takes its known names and defaults from here."""
+    return {k: p.default for k, p in inspect.signature(wrapper).parameters.items()
+            if p.kind is p.KEYWORD_ONLY and k not in _STAGE_TENSORS}
+
+
+def _scan_input(ranges, tab, name="ranges", least=0):
+    """ranges [B,N] float32 (N >= ``least``) matching the angle table -> (ranges, tab, B, N, device)."""
+    ranges = _dev(ranges, torch.float32, name)
+    if ranges.dim() != 2:
+        raise ValueError("%s must be [B,N]" % name)
+    B, N = ranges.shape
+    if N < least or _dev(tab, torch.float64, "tab").numel() != 3 * N:
+        raise ValueError("%s must be [B,N] matching the angle table" % name)
+    return ranges, tab, B, N, ranges.device
+
+
+def _nms_results(instance_mask, num_det, det_xy, det_cls, B, N):
+    """The four results of ``nms_predicted_center`` a per-person stage needs, checked for B scans of N points."""
+    instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
+    num_det = _dev(num_det, torch.int32, "num_det")
+    det_xy = _dev(det_xy, torch.float64, "det_xy")
+    det_cls = _dev(det_cls, torch.float64, "det_cls")
+    if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_xy.shape) != (B, N, 2) or \
+            tuple(det_cls.shape) != (B, N):
+        raise ValueError("instance_mask and det_cls must be [B,N], num_det [B] and det_xy [B,N,2]")
+    return instance_mask, num_det, det_xy, det_cls
+
+
+_F32, _F64, _I32, _I16, _U8 = torch.float32, torch.float64, torch.int32, torch.int16, torch.uint8
+PersonFlow = _record("PersonFlow", flow_global=(_F32, "B", "N", 2), flow_world=(_F64, "B", "N", 2),
+                     rgb=(_F64, "B", "N", 3), det_xy_world=(_F64, "B", "N", 2), det_flow=(_F64, "B", "N", 2),
+                     det_rgb=(_F64, "B", "N", 3), det_count=(_I32, "B", "N"), det_valid=(_U8, "B", "N"))
 
 
 def person_flow_buffers(B, N, device="cuda"):
     """The eight outputs of ``person_flow`` for B scans of N points, zero-filled, as its ``out=`` (allocate once,
     before a graph capture)."""
-    return PersonFlow(*(torch.zeros((B, N) + ((w,) if w else ()), dtype=dt, device=device)
-                        for _, dt, w in _PERSON_FLOW_OUT))
+    return _zeros_of(PersonFlow, device, B=B, N=N)
 
 
 def person_flow(flow_canonical, tab, instance_mask, num_det, det_xy, det_cls, rot=None, trans=None, flow_trans=None,
@@ -949,38 +1031,19 @@ def person_flow(flow_canonical, tab, instance_mask, num_det, det_xy, det_cls, ro
         raise ValueError("flow_canonical must be [B,N,2]")
     B, N = flow_canonical.shape[:2]
     dev = flow_canonical.device
-    tab = _dev(tab, torch.float64, "tab")
-    instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
-    num_det = _dev(num_det, torch.int32, "num_det")
-    det_xy = _dev(det_xy, torch.float64, "det_xy")
-    det_cls = _dev(det_cls, torch.float64, "det_cls")
-    if tab.numel() != 3 * N:
+    if _dev(tab, torch.float64, "tab").numel() != 3 * N:
         raise ValueError("flow_canonical must be [B,N,2] matching the angle table")
-    if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_xy.shape) != (B, N, 2) or \
-            tuple(det_cls.shape) != (B, N):
-        raise ValueError("instance_mask and det_cls must be [B,N], num_det [B] and det_xy [B,N,2]")
+    instance_mask, num_det, det_xy, det_cls = _nms_results(instance_mask, num_det, det_xy, det_cls, B, N)
+    _check_pose_terms(B, rot, trans, flow_trans)
     if rot is None:
         rot = torch.eye(2, dtype=torch.float32, device=dev).repeat(B, 1, 1)
-    rot = _dev(rot, torch.float32, "rot")
-    if tuple(rot.shape) not in ((B, 2, 2), (B, 4)):
-        raise ValueError("rot must be [B,2,2] (or [B,4] row-major)")
-    pose = []
-    for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
-        t = torch.zeros((B, 2), dtype=torch.float64, device=dev) if t is None else _dev(t, torch.float64, name)
-        if tuple(t.shape) != (B, 2):
-            raise ValueError("%s must be [B,2]" % name)
-        pose.append(t)
-    if out is None:
-        out = person_flow_buffers(B, N, dev)
-    else:
-        out = PersonFlow(*out)
-        for (name, dt, w), t in zip(_PERSON_FLOW_OUT, out):
-            _dev(t, dt, "out." + name)
-            if tuple(t.shape) != (B, N) + ((w,) if w else ()):
-                raise ValueError("out.%s has the wrong shape" % name)
+    trans, flow_trans = (torch.zeros((B, 2), dtype=torch.float64, device=dev) if t is None else t
+                         for t in (trans, flow_trans))
+    out = _out_of(PersonFlow, out, dev, B=B, N=N)
+    # no early return at B == 0, unlike the stages below: an empty batch goes to the launcher, as it always has
     with torch.cuda.device(dev):
         _lib.call("pof_person_flow", _ptr(flow_canonical), _ptr(tab), _ptr(instance_mask), _ptr(num_det), _ptr(det_xy),
-                  _ptr(det_cls), _ptr(rot), _ptr(pose[0]), _ptr(pose[1]), float(cls_thresh), B, N,
+                  _ptr(det_cls), _ptr(rot), _ptr(trans), _ptr(flow_trans), float(cls_thresh), B, N,
                   *[_ptr(t) for t in out], _stream())
     return out
 
@@ -1000,19 +1063,6 @@ def _nms_gate(instance_mask, num_det, det_cls, B=None, N=None):
     if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_cls.shape) != (B, N):
         raise ValueError("instance_mask and det_cls must be [B,N] and num_det [B]")
     return instance_mask, num_det, det_cls
-
-
-def _check_fields(tensors, fields, shapes, prefix):
-    """The tensors of a namedtuple against its fields (name, dtype, ...) and shapes; an error names ``prefix.name``."""
-    for (name, dt, *_), shape, t in zip(fields, shapes, tensors):
-        _dev(t, dt, prefix + "." + name)
-        if tuple(t.shape) != shape:
-            raise ValueError("%s.%s has the wrong shape" % (prefix, name))
-
-
-def _zeros(cls, fields, shapes, device):
-    """The namedtuple ``cls`` of zero-filled tensors: one per field (name, dtype, ...), of the shape beside it."""
-    return cls(*(torch.zeros(shape, dtype=dt, device=device) for (_, dt, *_), shape in zip(fields, shapes)))
 
 
 def _check_pose_terms(B, rot, trans, flow_trans):
@@ -1035,20 +1085,18 @@ def _check_matcher_settings(window, iters, **not_negative):
             raise ValueError("%s must be >= 0" % name)
 
 
-EgoMotion = collections.namedtuple("EgoMotion", ("motion", "count", "rms", "ok", "flow_residual", "weight"))
-_EGO_MOTION_OUT = (("motion", torch.float64), ("count", torch.int32), ("rms", torch.float64), ("ok", torch.uint8),
-                   ("flow_residual", torch.float64), ("weight", torch.float32))
+# what every motion fit reports per scan; the two scan matchers' part; what they report per point
+_FIT = dict(motion=(_F64, "B", 3), count=(_I32, "B"), rms=(_F64, "B"), ok=(_U8, "B"))
+_ICP = dict(_FIT, iters_used=(_I32, "B"), obs=(_F64, "B"))
+_ICP_POINTS = dict(corr=(_I32, "B", "N"), flow_residual=(_F64, "B", "N", 2))
+EgoMotion = _record("EgoMotion", **_FIT, flow_residual=(_F64, "B", "N", 2), weight=(_F32, "B", "N"))
 _EGO_MODELS = {"rigid": 0, "linear": 1}
-
-
-def _ego_motion_shapes(B, N):
-    return (B, 3), (B,), (B,), (B,), (B, N, 2), (B, N)
 
 
 def ego_motion_buffers(B, N, device="cuda"):
     """The six outputs of ``ego_motion`` for B scans of N points, zero-filled, as its ``out=`` (allocate once, before
     a graph capture)."""
-    return _zeros(EgoMotion, _EGO_MOTION_OUT, _ego_motion_shapes(B, N), device)
+    return _zeros_of(EgoMotion, device, B=B, N=N)
 
 
 def ego_motion(ranges, tab, flow, *, xy=None, canonical=True, sign=-1, model="rigid", weight=None, instance_mask=None,
@@ -1077,6 +1125,7 @@ def ego_motion(ranges, tab, flow, *, xy=None, canonical=True, sign=-1, model="ri
     if not 0 <= int(iters) <= 16:
         raise ValueError("iters must be in [0, 16]")
     _nms_gate(instance_mask, num_det, det_cls)
+    # the one stage whose batch is sized by the flow, float32 or float64: the ranges are optional beside ``xy``
     if not isinstance(flow, torch.Tensor) or flow.dtype not in (torch.float32, torch.float64):
         raise TypeError("flow must be a float32 or float64 tensor on the HIP device (no CPU path)")
     flow = _dev(flow, flow.dtype, "flow")
@@ -1096,11 +1145,7 @@ def ego_motion(ranges, tab, flow, *, xy=None, canonical=True, sign=-1, model="ri
     if weight is not None and tuple(_dev(weight, torch.float32, "weight").shape) != (B, N):
         raise ValueError("weight must be [B,N]")
     instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
-    if out is None:
-        out = ego_motion_buffers(B, N, dev)
-    else:
-        out = EgoMotion(*out)
-        _check_fields(out, _EGO_MOTION_OUT, _ego_motion_shapes(B, N), "out")
+    out = _out_of(EgoMotion, out, dev, B=B, N=N)
     if B == 0:
         return out
     with torch.cuda.device(dev):
@@ -1131,21 +1176,13 @@ def pose_advance(motion, ok, pose, rot=None, trans=None, flow_trans=None):
     return pose
 
 
-ScanMatch = collections.namedtuple("ScanMatch", ("motion", "count", "rms", "ok", "iters_used", "obs", "corr",
-                                                  "flow_residual"))
-_SCAN_MATCH_OUT = (("motion", torch.float64), ("count", torch.int32), ("rms", torch.float64), ("ok", torch.uint8),
-                   ("iters_used", torch.int32), ("obs", torch.float64), ("corr", torch.int32),
-                   ("flow_residual", torch.float64))
-
-
-def _scan_match_shapes(B, N):
-    return (B, 3), (B,), (B,), (B,), (B,), (B,), (B, N), (B, N, 2)
+ScanMatch = _record("ScanMatch", **_ICP, **_ICP_POINTS)
 
 
 def scan_match_buffers(B, N, device="cuda"):
     """The eight outputs of ``scan_match`` for B scan pairs of N points, zero-filled, as its ``out=`` (allocate once,
     before a graph capture)."""
-    return _zeros(ScanMatch, _SCAN_MATCH_OUT, _scan_match_shapes(B, N), device)
+    return _zeros_of(ScanMatch, device, B=B, N=N)
 
 
 def scan_match(ranges_prev, ranges_cur, tab, *, init=None, instance_mask=None, num_det=None, det_cls=None,
@@ -1172,20 +1209,13 @@ def scan_match(ranges_prev, ranges_cur, tab, *, init=None, instance_mask=None, n
     _nms_gate(instance_mask, num_det, det_cls)
     ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
     ranges_prev = _dev(ranges_prev, torch.float32, "ranges_prev")
-    if ranges_cur.dim() != 2 or ranges_prev.shape != ranges_cur.shape:
+    if ranges_prev.shape != ranges_cur.shape:
         raise ValueError("ranges_prev and ranges_cur must be [B,N]")
-    B, N = ranges_cur.shape
-    dev = ranges_cur.device
-    if N < 1 or _dev(tab, torch.float64, "tab").numel() != 3 * N:
-        raise ValueError("the ranges must be [B,N] matching the angle table")
+    ranges_cur, tab, B, N, dev = _scan_input(ranges_cur, tab, "ranges_cur", least=1)    # a matcher refuses N < 1
     if init is not None and tuple(_dev(init, torch.float64, "init").shape) != (B, 3):
         raise ValueError("init must be [B,3]")
     instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
-    if out is None:
-        out = scan_match_buffers(B, N, dev)
-    else:
-        out = ScanMatch(*out)
-        _check_fields(out, _SCAN_MATCH_OUT, _scan_match_shapes(B, N), "out")
+    out = _out_of(ScanMatch, out, dev, B=B, N=N)
     if B == 0:
         return out
     with torch.cuda.device(dev):
@@ -1196,24 +1226,9 @@ def scan_match(ranges_prev, ranges_cur, tab, *, init=None, instance_mask=None, n
     return out
 
 
-KeyframeState = collections.namedtuple("KeyframeState", ("key_ranges", "key_pose", "key_rel", "key_valid", "key_age",
-                                                          "key_misses", "pose"))
-KeyframeMatch = collections.namedtuple("KeyframeMatch", ("motion", "count", "rms", "ok", "iters_used", "obs",
-                                                          "key_replaced", "corr", "flow_residual"))
-_KEYFRAME_STATE = (("key_ranges", torch.float32), ("key_pose", torch.float64), ("key_rel", torch.float64),
-                   ("key_valid", torch.uint8), ("key_age", torch.int32), ("key_misses", torch.int32),
-                   ("pose", torch.float64))
-_KEYFRAME_OUT = (("motion", torch.float64), ("count", torch.int32), ("rms", torch.float64), ("ok", torch.uint8),
-                 ("iters_used", torch.int32), ("obs", torch.float64), ("key_replaced", torch.uint8),
-                 ("corr", torch.int32), ("flow_residual", torch.float64))
-
-
-def _keyframe_state_shapes(B, N):
-    return (B, N), (B, 3), (B, 3), (B,), (B,), (B,), (B, 3)
-
-
-def _keyframe_out_shapes(B, N):
-    return (B, 3), (B,), (B,), (B,), (B,), (B,), (B,), (B, N), (B, N, 2)
+KeyframeState = _record("KeyframeState", key_ranges=(_F32, "B", "N"), key_pose=(_F64, "B", 3), key_rel=(_F64, "B", 3),
+                        key_valid=(_U8, "B"), key_age=(_I32, "B"), key_misses=(_I32, "B"), pose=(_F64, "B", 3))
+KeyframeMatch = _record("KeyframeMatch", **_ICP, key_replaced=(_U8, "B"), **_ICP_POINTS)
 
 
 def _keyframe_reset(state, pose):
@@ -1228,13 +1243,12 @@ def _keyframe_reset(state, pose):
     return state
 
 
-def _keyframe_step(entry, state_spec, out_spec, ranges_cur, tab, state, instance_mask, num_det, det_cls, cls_thresh,
+def _keyframe_step(entry, State, Out, ranges_cur, tab, state, instance_mask, num_det, det_cls, cls_thresh,
                    max_range, window, gate, max_gap, huber_delta, iters, eps_theta, eps_u, min_pivot, key_dist, key_rot,
                    min_share, max_misses, out, rot, trans, flow_trans, revisit=None):
-    """``keyframe_match`` (``revisit`` None) and ``keyframe_map_match``: the checks and the call of ``entry``.  A spec
-    is (namedtuple class, field table, shapes function).  With a ring the state's shapes also take K, read off
-    state.key_ranges [B,K,N], and the entry point takes ``revisit`` in front of B and K behind N."""
-    (State, state_fields, state_shapes), (Out, out_fields, out_shapes) = state_spec, out_spec
+    """``keyframe_match`` (``revisit`` None) and ``keyframe_map_match``: the checks and the call of ``entry``, for the
+    records ``State`` and ``Out``.  With a ring the state's shapes also take K, read off state.key_ranges [B,K,N], and
+    the entry point takes ``revisit`` in front of B and K behind N."""
     _check_matcher_settings(window, iters, gate=gate, max_gap=max_gap, huber_delta=huber_delta, key_dist=key_dist,
                             key_rot=key_rot, min_share=min_share)
     if int(max_misses) < 0:
@@ -1242,26 +1256,16 @@ def _keyframe_step(entry, state_spec, out_spec, ranges_cur, tab, state, instance
     if revisit is not None and not 0.0 <= float(revisit) <= 1.0:
         raise ValueError("revisit must be in [0, 1]")
     _nms_gate(instance_mask, num_det, det_cls)
-    ranges_cur = _dev(ranges_cur, torch.float32, "ranges_cur")
-    if ranges_cur.dim() != 2:
-        raise ValueError("ranges_cur must be [B,N]")
-    B, N = ranges_cur.shape
-    dev = ranges_cur.device
-    if N < 1 or _dev(tab, torch.float64, "tab").numel() != 3 * N:
-        raise ValueError("the ranges must be [B,N] matching the angle table")
+    ranges_cur, tab, B, N, dev = _scan_input(ranges_cur, tab, "ranges_cur", least=1)    # a matcher refuses N < 1
     state = State(*state)
-    ring = ()
+    ring = {}
     if revisit is not None:
         if not isinstance(state.key_ranges, torch.Tensor) or state.key_ranges.dim() != 3:
             raise ValueError("state.key_ranges must be [B,K,N]")
-        ring = (_check_keys(state.key_ranges.shape[1]),)
-    _check_fields(state, state_fields, state_shapes(B, N, *ring), "state")
+        ring = dict(K=_check_keys(state.key_ranges.shape[1]))
+    state = _checked(State, state, "state", B=B, N=N, **ring)
     instance_mask, num_det, det_cls = _nms_gate(instance_mask, num_det, det_cls, B, N)
-    if out is None:
-        out = _zeros(Out, out_fields, out_shapes(B, N), dev)
-    else:
-        out = Out(*out)
-        _check_fields(out, out_fields, out_shapes(B, N), "out")
+    out = _out_of(Out, out, dev, B=B, N=N)
     _check_pose_terms(B, rot, trans, flow_trans)
     if B == 0:
         return out
@@ -1269,7 +1273,7 @@ def _keyframe_step(entry, state_spec, out_spec, ranges_cur, tab, state, instance
         _lib.call(entry, _ptr(ranges_cur), _ptr(tab), _ptr(instance_mask), _ptr(num_det), _ptr(det_cls),
                   float(cls_thresh), float(max_range), int(window), float(gate), float(max_gap), float(huber_delta),
                   int(iters), float(eps_theta), float(eps_u), float(min_pivot), float(key_dist), float(key_rot),
-                  float(min_share), int(max_misses), *(() if revisit is None else (float(revisit),)), B, N, *ring,
+                  float(min_share), int(max_misses), *(() if revisit is None else (float(revisit),)), B, N, *ring.values(),
                   *[_ptr(t) for t in state], *[_ptr(t) for t in out], _ptr(rot), _ptr(trans), _ptr(flow_trans),
                   _stream())
     return out
@@ -1278,12 +1282,12 @@ def _keyframe_step(entry, state_spec, out_spec, ranges_cur, tab, state, instance
 def keyframe_buffers(B, N, device="cuda"):
     """The persistent state of ``keyframe_match`` for B sensors of N points: no keyframe yet, the pose at zero
     (allocate once, before a graph capture).  -> ``KeyframeState``."""
-    return _zeros(KeyframeState, _KEYFRAME_STATE, _keyframe_state_shapes(B, N), device)
+    return _zeros_of(KeyframeState, device, B=B, N=N)
 
 
 def keyframe_match_buffers(B, N, device="cuda"):
     """The nine outputs of ``keyframe_match``, zero-filled, as its ``out=``."""
-    return _zeros(KeyframeMatch, _KEYFRAME_OUT, _keyframe_out_shapes(B, N), device)
+    return _zeros_of(KeyframeMatch, device, B=B, N=N)
 
 
 def keyframe_reset(state, pose=None):
@@ -1312,34 +1316,17 @@ def keyframe_match(ranges_cur, tab, state, *, instance_mask=None, num_det=None, 
     ``out``: a ``KeyframeMatch`` of preallocated tensors (``keyframe_match_buffers``).  ``rot`` [B,2,2] (or [B,4]) f32,
     ``trans`` [B,2] f64, ``flow_trans`` [B,2] f64: the pose terms ``person_flow`` reads, as ``pose_advance`` writes
     them."""
-    return _keyframe_step("pof_keyframe_match", (KeyframeState, _KEYFRAME_STATE, _keyframe_state_shapes),
-                          (KeyframeMatch, _KEYFRAME_OUT, _keyframe_out_shapes), ranges_cur, tab, state, instance_mask,
+    return _keyframe_step("pof_keyframe_match", KeyframeState, KeyframeMatch, ranges_cur, tab, state, instance_mask,
                           num_det, det_cls, cls_thresh, max_range, window, gate, max_gap, huber_delta, iters, eps_theta,
                           eps_u, min_pivot, key_dist, key_rot, min_share, max_misses, out, rot, trans, flow_trans)
 
 
-KeyframeMapState = collections.namedtuple("KeyframeMapState", ("key_ranges", "key_pose", "key_valid", "key_stamp",
-                                                                "key_active", "key_rel", "key_age", "key_misses", "step",
-                                                                "pose"))
-KeyframeMapMatch = collections.namedtuple("KeyframeMapMatch", ("motion", "count", "rms", "ok", "iters_used", "obs",
-                                                                "key_replaced", "key_switched", "key_slot", "corr",
-                                                                "flow_residual"))
-_KEYFRAME_MAP_STATE = (("key_ranges", torch.float32), ("key_pose", torch.float64), ("key_valid", torch.uint8),
-                       ("key_stamp", torch.int32), ("key_active", torch.int32), ("key_rel", torch.float64),
-                       ("key_age", torch.int32), ("key_misses", torch.int32), ("step", torch.int32),
-                       ("pose", torch.float64))
-_KEYFRAME_MAP_OUT = (("motion", torch.float64), ("count", torch.int32), ("rms", torch.float64), ("ok", torch.uint8),
-                     ("iters_used", torch.int32), ("obs", torch.float64), ("key_replaced", torch.uint8),
-                     ("key_switched", torch.uint8), ("key_slot", torch.int32), ("corr", torch.int32),
-                     ("flow_residual", torch.float64))
-
-
-def _keyframe_map_state_shapes(B, N, K):
-    return (B, K, N), (B, K, 3), (B, K), (B, K), (B,), (B, 3), (B,), (B,), (B,), (B, 3)
-
-
-def _keyframe_map_out_shapes(B, N):
-    return (B, 3), (B,), (B,), (B,), (B,), (B,), (B,), (B,), (B,), (B, N), (B, N, 2)
+KeyframeMapState = _record("KeyframeMapState", key_ranges=(_F32, "B", "K", "N"), key_pose=(_F64, "B", "K", 3),
+                           key_valid=(_U8, "B", "K"), key_stamp=(_I32, "B", "K"), key_active=(_I32, "B"),
+                           key_rel=(_F64, "B", 3), key_age=(_I32, "B"), key_misses=(_I32, "B"), step=(_I32, "B"),
+                           pose=(_F64, "B", 3))
+KeyframeMapMatch = _record("KeyframeMapMatch", **_ICP, key_replaced=(_U8, "B"), key_switched=(_U8, "B"),
+                           key_slot=(_I32, "B"), **_ICP_POINTS)
 
 
 def _check_keys(keys):
@@ -1352,12 +1339,12 @@ def keyframe_map_buffers(B, N, keys=16, device="cuda"):
     """The persistent state of ``keyframe_map_match`` for B sensors of N points and a ring of ``keys`` (1..64)
     keyframes each: no keyframe yet, slot 0 active, the pose at zero (allocate once, before a graph capture).
     -> ``KeyframeMapState``."""
-    return _zeros(KeyframeMapState, _KEYFRAME_MAP_STATE, _keyframe_map_state_shapes(B, N, _check_keys(keys)), device)
+    return _zeros_of(KeyframeMapState, device, B=B, N=N, K=_check_keys(keys))
 
 
 def keyframe_map_match_buffers(B, N, device="cuda"):
     """The eleven outputs of ``keyframe_map_match``, zero-filled, as its ``out=``."""
-    return _zeros(KeyframeMapMatch, _KEYFRAME_MAP_OUT, _keyframe_map_out_shapes(B, N), device)
+    return _zeros_of(KeyframeMapMatch, device, B=B, N=N)
 
 
 def keyframe_map_reset(state, pose=None):
@@ -1384,36 +1371,25 @@ def keyframe_map_match(ranges_cur, tab, state, *, instance_mask=None, num_det=No
     -> ``KeyframeMapMatch``: the outputs of ``keyframe_match`` and key_switched [B] u8, key_slot [B] i32 (the active
     slot after the step).  ``out``: a ``KeyframeMapMatch`` of preallocated tensors (``keyframe_map_match_buffers``);
     ``rot``, ``trans``, ``flow_trans`` as ``keyframe_match``."""
-    return _keyframe_step("pof_keyframe_map_match",
-                          (KeyframeMapState, _KEYFRAME_MAP_STATE, _keyframe_map_state_shapes),
-                          (KeyframeMapMatch, _KEYFRAME_MAP_OUT, _keyframe_map_out_shapes), ranges_cur, tab, state,
+    return _keyframe_step("pof_keyframe_map_match", KeyframeMapState, KeyframeMapMatch, ranges_cur, tab, state,
                           instance_mask, num_det, det_cls, cls_thresh, max_range, window, gate, max_gap, huber_delta,
                           iters, eps_theta, eps_u, min_pivot, key_dist, key_rot, min_share, max_misses, out, rot, trans,
                           flow_trans, revisit=revisit)
 
 
-TrackState = collections.namedtuple("TrackState", ("track_id", "track_state", "track_cov", "track_hits", "track_misses",
-                                                    "track_age", "next_id", "track_det", "track_confirmed",
-                                                    "det_track", "point_track", "dropped"))
-# name, dtype, per ("M": slot, "N": detection row / point, "B": sensor), trailing width
-_TRACK_FIELDS = (("track_id", torch.int32, "M", 0), ("track_state", torch.float64, "M", 4),
-                 ("track_cov", torch.float64, "M", 3), ("track_hits", torch.int32, "M", 0),
-                 ("track_misses", torch.int32, "M", 0), ("track_age", torch.int32, "M", 0),
-                 ("next_id", torch.int32, "B", 0), ("track_det", torch.int32, "M", 0),
-                 ("track_confirmed", torch.uint8, "M", 0), ("det_track", torch.int32, "N", 0),
-                 ("point_track", torch.int32, "N", 0), ("dropped", torch.int32, "B", 0))
-_TRACK_PERSISTENT = ("track_id", "track_state", "track_cov", "track_hits", "track_misses", "track_age", "next_id")
-
-
-def _track_shape(per, w, B, M, N):
-    return ((B,) if per == "B" else (B, M if per == "M" else N)) + ((w,) if w else ())
+# the tracks themselves carry over from scan to scan; the rest describes one step (M: slot, N: detection row / point)
+TrackState = _record("TrackState",
+                     persistent=dict(track_id=(_I32, "B", "M"), track_state=(_F64, "B", "M", 4),
+                                     track_cov=(_F64, "B", "M", 3), track_hits=(_I32, "B", "M"),
+                                     track_misses=(_I32, "B", "M"), track_age=(_I32, "B", "M"), next_id=(_I32, "B")),
+                     track_det=(_I32, "B", "M"), track_confirmed=(_U8, "B", "M"), det_track=(_I32, "B", "N"),
+                     point_track=(_I32, "B", "N"), dropped=(_I32, "B"))
 
 
 def track_buffers(B, max_tracks, N, device="cuda"):
     """The state and the outputs of ``track_update`` for B sensors, ``max_tracks`` slots and N detection rows: a
     ``TrackState`` of zeros with ``next_id`` = 1 (allocate once, before a graph capture)."""
-    state = TrackState(*(torch.zeros(_track_shape(per, w, B, int(max_tracks), N), dtype=dt, device=device)
-                         for _, dt, per, w in _TRACK_FIELDS))
+    state = _zeros_of(TrackState, device, B=B, M=int(max_tracks), N=N)
     state.next_id.fill_(1)
     return state
 
@@ -1455,7 +1431,7 @@ def track_update(det_xy_world, det_flow, det_valid, num_det, instance_mask, stat
     if state.track_id.dim() != 2:
         raise ValueError("state.track_id must be [B,max_tracks]")
     M = state.track_id.shape[1]
-    _check_fields(state, _TRACK_FIELDS, [_track_shape(per, w, B, M, N) for _, _, per, w in _TRACK_FIELDS], "state")
+    state = _checked(TrackState, state, "state", B=B, M=M, N=N)
     if B == 0:
         return state
     with torch.cuda.device(det_xy_world.device):
@@ -1465,32 +1441,23 @@ def track_update(det_xy_world, det_flow, det_valid, num_det, instance_mask, stat
     return state
 
 
-PersonMotion = collections.namedtuple("PersonMotion", ("det_xy_world", "det_flow", "det_centre", "det_count",
-                                                        "det_valid", "det_prev"))
-PersonMotionState = collections.namedtuple("PersonMotionState", ("prev_centre", "prev_cand", "prev_num"))
-_PERSON_MOTION_OUT = (("det_xy_world", torch.float64), ("det_flow", torch.float64), ("det_centre", torch.float64),
-                      ("det_count", torch.int32), ("det_valid", torch.uint8), ("det_prev", torch.int32))
-_PERSON_MOTION_STATE = (("prev_centre", torch.float64), ("prev_cand", torch.uint8), ("prev_num", torch.int32))
-
-
-def _person_motion_out_shapes(B, N):
-    return (B, N, 2), (B, N, 2), (B, N, 2), (B, N), (B, N), (B, N)
-
-
-def _person_motion_state_shapes(B, N):
-    return (B, N, 2), (B, N), (B,)
+PersonMotion = _record("PersonMotion", det_xy_world=(_F64, "B", "N", 2), det_flow=(_F64, "B", "N", 2),
+                       det_centre=(_F64, "B", "N", 2), det_count=(_I32, "B", "N"), det_valid=(_U8, "B", "N"),
+                       det_prev=(_I32, "B", "N"))
+PersonMotionState = _record("PersonMotionState", prev_centre=(_F64, "B", "N", 2), prev_cand=(_U8, "B", "N"),
+                            prev_num=(_I32, "B"))
 
 
 def person_motion_buffers(B, N, device="cuda"):
     """The six outputs of ``person_motion`` for B scans of N points, zero-filled, as its ``out=`` (allocate once,
     before a graph capture)."""
-    return _zeros(PersonMotion, _PERSON_MOTION_OUT, _person_motion_out_shapes(B, N), device)
+    return _zeros_of(PersonMotion, device, B=B, N=N)
 
 
 def person_motion_state(B, N, device="cuda"):
     """The persistent state of ``person_motion`` for B sensors of N points: no previous scan (allocate once, before a
     graph capture).  -> ``PersonMotionState``."""
-    return _zeros(PersonMotionState, _PERSON_MOTION_STATE, _person_motion_state_shapes(B, N), device)
+    return _zeros_of(PersonMotionState, device, B=B, N=N)
 
 
 def person_motion_reset(state):
@@ -1518,31 +1485,13 @@ def person_motion(ranges, tab, instance_mask, num_det, det_xy, det_cls, rot, tra
     position only), det_centre [B,N,2] f64, det_count [B,N] i32, det_prev [B,N] i32 = the partner's row in the previous
     scan or -1.  Rows >= num_det[b] are zeros (det_prev -1).  The same bits in every run.  ``out``: a ``PersonMotion``
     of preallocated tensors (``person_motion_buffers``)."""
-    ranges = _dev(ranges, torch.float32, "ranges")
-    if ranges.dim() != 2:
-        raise ValueError("ranges must be [B,N]")
-    B, N = ranges.shape
-    dev = ranges.device
-    tab = _dev(tab, torch.float64, "tab")
-    instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
-    num_det = _dev(num_det, torch.int32, "num_det")
-    det_xy = _dev(det_xy, torch.float64, "det_xy")
-    det_cls = _dev(det_cls, torch.float64, "det_cls")
-    if tab.numel() != 3 * N:
-        raise ValueError("ranges must be [B,N] matching the angle table")
-    if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,) or tuple(det_xy.shape) != (B, N, 2) or \
-            tuple(det_cls.shape) != (B, N):
-        raise ValueError("instance_mask and det_cls must be [B,N], num_det [B] and det_xy [B,N,2]")
+    ranges, tab, B, N, dev = _scan_input(ranges, tab)
+    instance_mask, num_det, det_xy, det_cls = _nms_results(instance_mask, num_det, det_xy, det_cls, B, N)
     if rot is None or trans is None:
         raise TypeError("rot and trans must be tensors on the HIP device (no CPU path)")
     _check_pose_terms(B, rot, trans, None)
-    state = PersonMotionState(*state)
-    _check_fields(state, _PERSON_MOTION_STATE, _person_motion_state_shapes(B, N), "state")
-    if out is None:
-        out = person_motion_buffers(B, N, dev)
-    else:
-        out = PersonMotion(*out)
-        _check_fields(out, _PERSON_MOTION_OUT, _person_motion_out_shapes(B, N), "out")
+    state = _checked(PersonMotionState, state, "state", B=B, N=N)
+    out = _out_of(PersonMotion, out, dev, B=B, N=N)
     if B == 0:
         return out
     with torch.cuda.device(dev):
@@ -1552,23 +1501,21 @@ def person_motion(ranges, tab, instance_mask, num_det, det_xy, det_cls, rot, tra
     return out
 
 
-GridMapState = collections.namedtuple("GridMapState", ("grid", "origin"))
-GridMapOut = collections.namedtuple("GridMapOut", ("point_cell", "point_mark", "point_prior", "det_points", "det_free"))
-_GRID_MAP_STATE = (("grid", torch.int16), ("origin", torch.float64))
-_GRID_MAP_OUT = (("point_cell", torch.int32), ("point_mark", torch.uint8), ("point_prior", torch.int16),
-                 ("det_points", torch.int32), ("det_free", torch.int32))
+GridMapState = _record("GridMapState", grid=(_I16, "B", "H", "W"), origin=(_F64, "B", 2))
+GridMapOut = _record("GridMapOut", point_cell=(_I32, "B", "N"), point_mark=(_U8, "B", "N"), point_prior=(_I16, "B", "N"),
+                     det_points=(_I32, "B", "N"), det_free=(_I32, "B", "N"))
 
 
 def grid_map_buffers(B, N, device="cuda"):
     """The five outputs of ``grid_map_update`` for B scans of N points, zero-filled, as its ``out=`` (allocate once,
     before a graph capture)."""
-    return _zeros(GridMapOut, _GRID_MAP_OUT, ((B, N),) * 5, device)
+    return _zeros_of(GridMapOut, device, B=B, N=N)
 
 
 def grid_map_state(B, H, W, device="cuda"):
     """The persistent state of ``grid_map_update`` for B sensors: a grid of H x W cells, all unknown, with its lower
     corner at the world origin (allocate once, before a graph capture).  -> ``GridMapState``."""
-    return _zeros(GridMapState, _GRID_MAP_STATE, ((B, H, W), (B, 2)), device)
+    return _zeros_of(GridMapState, device, B=B, H=H, W=W)
 
 
 def grid_map_reset(state, origin=None):
@@ -1603,32 +1550,21 @@ def grid_map_update(ranges, tab, rot, trans, state, *, res, instance_mask=None, 
     -32768 without one), det_points / det_free [B,N] i32 (per detection row the endpoints inside the grid and how many
     of them lie on cells that held <= -``free_thresh``; zeros without the NMS results).  The same bits in every run.
     ``out``: a ``GridMapOut`` of preallocated tensors (``grid_map_buffers``)."""
-    ranges = _dev(ranges, torch.float32, "ranges")
-    if ranges.dim() != 2:
-        raise ValueError("ranges must be [B,N]")
-    B, N = ranges.shape
-    dev = ranges.device
-    tab = _dev(tab, torch.float64, "tab")
-    if tab.numel() != 3 * N:
-        raise ValueError("ranges must be [B,N] matching the angle table")
+    ranges, tab, B, N, dev = _scan_input(ranges, tab)
     if rot is None or trans is None:
         raise TypeError("rot and trans must be tensors on the HIP device (no CPU path)")
     _check_pose_terms(B, rot, trans, None)
-    gate = (instance_mask, num_det, det_cls)
-    if any(t is not None for t in gate):
-        if any(t is None for t in gate):
-            raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
-        gate = _nms_gate(*gate, B, N)
+    # stricter than _nms_gate, which lets num_det and det_cls pass (unused) without an instance_mask: this stage also
+    # reports per detection, so the three come together or not at all
+    if instance_mask is None and (num_det is not None or det_cls is not None):
+        raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
+    gate = _nms_gate(instance_mask, num_det, det_cls, B, N)
     state = GridMapState(*state)
     if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
         raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
     H, W = state.grid.shape[1:]
-    _check_fields(state, _GRID_MAP_STATE, ((B, H, W), (B, 2)), "state")
-    if out is None:
-        out = grid_map_buffers(B, N, dev)
-    else:
-        out = GridMapOut(*out)
-        _check_fields(out, _GRID_MAP_OUT, ((B, N),) * 5, "out")
+    state = _checked(GridMapState, state, "state", B=B, H=H, W=W)
+    out = _out_of(GridMapOut, out, dev, B=B, N=N)
     if B == 0:
         return out
     with torch.cuda.device(dev):

@@ -106,7 +106,7 @@ class Trainer:
             self._logger.flush()
         return 0
 
-    def _graph_shapes(self, batch):
+    def _batch_shape_key(self, batch):
         return tuple((k, tuple(batch[k].shape)) for k in ("input", "target"))
 
     def _train_batch_graphed(self, model, batch, ratio):
@@ -117,7 +117,7 @@ class Trainer:
             optim = self._optim.make_capturable()
             self._graphed = GraphedTrainStep(model, optim, batch, grad_norm_clip=self._grad_norm_clip,
                                              reducer=self._reducer)
-            self._graphed_shapes = self._graph_shapes(batch)
+            self._graphed_shapes = self._batch_shape_key(batch)
         self._optim.set_lr(self._epoch + ratio)
         loss = self._graphed.step(batch).item()
         self._logger.add_scalar("TRAIN_lr", self._optim.get_lr(), self._step)
@@ -131,7 +131,7 @@ class Trainer:
         # with a reducer the step is captured only where the collective can be a node of the graph (RCCL)
         graphable = self._reducer is None or pdist.backend() == "nccl"
         if self._graph_step and graphable and next(model.parameters()).is_cuda \
-                and (self._graphed is None or self._graph_shapes(batch) == self._graphed_shapes):
+                and (self._graphed is None or self._batch_shape_key(batch) == self._graphed_shapes):
             return self._train_batch_graphed(model, batch, ratio)
         # once a step is captured its graph owns the addresses of the gradient buffers: keep them allocated
         # (and so does a gradient bucket: the gradients are views into it)

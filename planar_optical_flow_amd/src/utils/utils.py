@@ -42,6 +42,30 @@ def _to_dev(x, dtype):
     return torch.from_numpy(arr).to(_device())
 
 
+def _host(t):
+    """Row 0 of a device tensor -- the one scan of a per-scan call -- as NumPy."""
+    return t[0].cpu().numpy()
+
+
+def _nms(ranges, tab, pred_cls, pred_reg, min_dist):
+    """The centre NMS of one scan from host-side predictions: ranges [1,N] on the device, pred_cls [N,1] (scores),
+    pred_reg [N,2] -> (det_xy, det_cls, num_det, instance_mask) as ``ops.nms_predicted_center`` returns them, and the
+    dtype of the scores, which the reference's det_cls keeps."""
+    pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
+    assert pc.ndim == 2 and pc.shape[1] == 1
+    return (*ops.nms_predicted_center(ranges, tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
+                                      _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), min_dist), pc.dtype)
+
+
+def _stage_kw(wrapper, name, kw, *elsewhere):
+    """kw, the settings a class passes on to the ``ops`` wrapper of its stage: a key that is not one of the wrapper's
+    settings (``ops.stage_settings``; ``elsewhere``: those the class takes by another way) raises."""
+    unknown = set(kw) - (set(ops.stage_settings(wrapper)) - set(elsewhere))
+    if unknown:
+        raise ValueError("unknown %s settings: %s" % (name, sorted(unknown)))
+    return kw
+
+
 def _grid_of(scan_phi):
     """(angle_inc, N) of a uniformly spaced angle grid given as array/tensor."""
     phi = scan_phi.detach().cpu().numpy() if _is_t(scan_phi) else np.asarray(scan_phi)
@@ -240,16 +264,12 @@ def ego_motion(scan, scan_phi, pred_flow, pred_cls=None, pred_reg=None, min_dist
     ranges = _to_dev(scan, torch.float32).reshape(1, -1)
     gate = {}
     if pred_cls is not None and pred_reg is not None:
-        pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
-        assert pc.ndim == 2 and pc.shape[1] == 1
-        _, dc, num, inst = ops.nms_predicted_center(ranges, tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
-                                                    _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), min_dist)
+        _, dc, num, inst, _ = _nms(ranges, tab, pred_cls, pred_reg, min_dist)
         gate = dict(instance_mask=inst, num_det=num, det_cls=dc, cls_thresh=cls_thresh)
     res = ops.ego_motion(ranges, tab, _to_dev(pred_flow, torch.float32).reshape(1, -1, 2), max_range=max_range,
                          huber_delta=huber_delta, iters=iters, **gate)
-    host = lambda t: t[0].cpu().numpy()
-    return {"motion": host(res.motion), "ok": bool(res.ok[0].item()), "count": int(res.count[0].item()),
-            "rms": float(res.rms[0].item()), "flow_residual": host(res.flow_residual)}
+    return {"motion": _host(res.motion), "ok": bool(res.ok[0].item()), "count": int(res.count[0].item()),
+            "rms": float(res.rms[0].item()), "flow_residual": _host(res.flow_residual)}
 
 
 def scan_match(scan_prev, scan_cur, scan_phi, pred_cls=None, pred_reg=None, **kw):
@@ -268,16 +288,12 @@ def scan_match(scan_prev, scan_cur, scan_phi, pred_cls=None, pred_reg=None, **kw
     if kw.get("init") is not None:
         kw["init"] = _to_dev(kw["init"], torch.float64).reshape(1, 3)
     if pred_cls is not None and pred_reg is not None:
-        pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
-        assert pc.ndim == 2 and pc.shape[1] == 1
-        _, dc, num, inst = ops.nms_predicted_center(cur, tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
-                                                    _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), min_dist)
+        _, dc, num, inst, _ = _nms(cur, tab, pred_cls, pred_reg, min_dist)
         kw.update(instance_mask=inst, num_det=num, det_cls=dc)
     res = ops.scan_match(prev, cur, tab, **kw)
-    host = lambda t: t[0].cpu().numpy()
-    return {"motion": host(res.motion), "ok": bool(res.ok[0].item()), "count": int(res.count[0].item()),
+    return {"motion": _host(res.motion), "ok": bool(res.ok[0].item()), "count": int(res.count[0].item()),
             "rms": float(res.rms[0].item()), "iters_used": int(res.iters_used[0].item()),
-            "obs": float(res.obs[0].item()), "corr": host(res.corr), "flow_residual": host(res.flow_residual)}
+            "obs": float(res.obs[0].item()), "corr": _host(res.corr), "flow_residual": _host(res.flow_residual)}
 
 
 # ------------------------------------------------------------------ A6
@@ -355,13 +371,10 @@ def scans_to_cutout_torch(scans, scan_phi, stride=1, centered=True, fixed=False,
 # ------------------------------------------------------------------ A11
 def nms_predicted_center(scan_grid, phi_grid, pred_cls, pred_reg, min_dist=0.5):
     """:535-571 -> (det_xys [M,2], det_cls [M,1], instance_mask [N] int32)."""
-    pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
-    assert pc.ndim == 2 and pc.shape[1] == 1
-    xy, dc, num, inst = ops.nms_predicted_center(
-        _to_dev(scan_grid, torch.float32).reshape(1, -1), _table_for(phi_grid),
-        _to_dev(pc[:, 0], torch.float64).reshape(1, -1), _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), min_dist)
+    xy, dc, num, inst, dtype = _nms(_to_dev(scan_grid, torch.float32).reshape(1, -1), _table_for(phi_grid), pred_cls,
+                                    pred_reg, min_dist)
     m = int(num[0].item())
-    return xy[0, :m].cpu().numpy(), dc[0, :m].cpu().numpy().reshape(-1, 1).astype(pc.dtype), inst[0].cpu().numpy()
+    return xy[0, :m].cpu().numpy(), dc[0, :m].cpu().numpy().reshape(-1, 1).astype(dtype), _host(inst)
 
 
 def flow_to_hsv(flow):
@@ -394,23 +407,18 @@ def person_flow(scan, scan_phi, pred_cls, pred_reg, pred_flow, odom1=None, odom0
     -> dict: dets_xy_world [M,2], dets_cls [M,1], person_flow [M,2], person_rgb [M,3], count [M], valid [M] (bool:
     ``dets_cls >= cls_thresh``, the detections the reference draws with an arrow), instance_mask [N], flow_world
     [N,2], rgb [N,3].  A detection whose points all went to later detections has count 0 and NaN means."""
-    pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
-    assert pc.ndim == 2 and pc.shape[1] == 1
     tab = _table_for(scan_phi)
-    xy, dc, num, inst = ops.nms_predicted_center(
-        _to_dev(scan, torch.float32).reshape(1, -1), tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
-        _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), min_dist)
+    xy, dc, num, inst, dtype = _nms(_to_dev(scan, torch.float32).reshape(1, -1), tab, pred_cls, pred_reg, min_dist)
     rot, trans, flow_trans = _pose_terms(None if odom1 is None else np.asarray(odom1, dtype=np.float64)[None],
                                          None if odom0 is None else np.asarray(odom0, dtype=np.float64)[None])
     out = ops.person_flow(_to_dev(pred_flow, torch.float32).reshape(1, -1, 2), tab, inst, num, xy, dc,
                           _to_dev(rot, torch.float32), _to_dev(trans, torch.float64),
                           _to_dev(flow_trans, torch.float64), cls_thresh)
     m = int(num[0].item())
-    host = lambda t: t[0].cpu().numpy()
-    return {"dets_xy_world": host(out.det_xy_world)[:m], "dets_cls": host(dc)[:m].reshape(-1, 1).astype(pc.dtype),
-            "person_flow": host(out.det_flow)[:m], "person_rgb": host(out.det_rgb)[:m],
-            "count": host(out.det_count)[:m], "valid": host(out.det_valid)[:m].astype(bool),
-            "instance_mask": host(inst), "flow_world": host(out.flow_world), "rgb": host(out.rgb)}
+    return {"dets_xy_world": _host(out.det_xy_world)[:m], "dets_cls": _host(dc)[:m].reshape(-1, 1).astype(dtype),
+            "person_flow": _host(out.det_flow)[:m], "person_rgb": _host(out.det_rgb)[:m],
+            "count": _host(out.det_count)[:m], "valid": _host(out.det_valid)[:m].astype(bool),
+            "instance_mask": _host(inst), "flow_world": _host(out.flow_world), "rgb": _host(out.rgb)}
 
 
 class PersonTracker:
@@ -425,10 +433,7 @@ class PersonTracker:
     instance_mask also point_track [N], the track id of every scan point."""
 
     def __init__(self, max_tracks=64, **settings):
-        unknown = set(settings) - {"gate", "q", "r_pos", "r_vel", "v0_var", "max_misses", "min_hits"}
-        if unknown:
-            raise ValueError("unknown tracks settings: %s" % sorted(unknown))
-        self.max_tracks, self.settings = int(max_tracks), settings
+        self.max_tracks, self.settings = int(max_tracks), _stage_kw(ops.track_update, "tracks", settings)
         self._persistent = None
 
     def reset(self):
@@ -449,7 +454,7 @@ class PersonTracker:
                          pad(result["valid"], np.uint8), torch.full((1,), m, dtype=torch.int32, device=dev),
                          torch.zeros((1, n), dtype=torch.int32, device=dev) if inst is None else
                          _to_dev(inst, torch.int32).reshape(1, n), state, **self.settings)
-        self._persistent = {k: getattr(state, k) for k in ops._TRACK_PERSISTENT}
+        self._persistent = {k: getattr(state, k) for k in ops.TrackState.persistent}
         h = {k: getattr(state, k)[0].cpu().numpy() for k in state._fields}
         live = np.flatnonzero(h["track_id"])
         tracks = {"id": h["track_id"][live], "xy": h["track_state"][live, :2], "velocity": h["track_state"][live, 2:],
@@ -478,30 +483,23 @@ class PersonMotion:
         self._tab = _table_for(scan_phi)
         self._n = self._tab.numel() // 3
         self._min_dist = kw.pop("min_dist", 0.5)
-        unknown = set(kw) - {"cls_thresh", "max_range", "reach", "min_points"}
-        if unknown:
-            raise ValueError("unknown person_motion settings: %s" % sorted(unknown))
-        self._kw = kw
+        self._kw = _stage_kw(ops.person_motion, "person_motion", kw)
         self._state = ops.person_motion_state(1, self._n, self._tab.device)
 
     def reset(self):
         ops.person_motion_reset(self._state)
 
     def update(self, scan, pred_cls, pred_reg, odom=None):
-        pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
-        assert pc.ndim == 2 and pc.shape[1] == 1
         cur = _to_dev(scan, torch.float32).reshape(1, -1)
-        xy, dc, num, inst = ops.nms_predicted_center(cur, self._tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
-                                                     _to_dev(pred_reg, torch.float64).reshape(1, -1, 2), self._min_dist)
+        xy, dc, num, inst, dtype = _nms(cur, self._tab, pred_cls, pred_reg, self._min_dist)
         rot, trans, _ = _pose_terms(None if odom is None else np.asarray(odom, dtype=np.float64)[None])
         out = ops.person_motion(cur, self._tab, inst, num, xy, dc, _to_dev(rot, torch.float32),
                                 _to_dev(trans, torch.float64), self._state, **self._kw)
         m = int(num[0].item())
-        host = lambda t: t[0].cpu().numpy()
-        return {"dets_xy_world": host(out.det_xy_world)[:m], "dets_cls": host(dc)[:m].reshape(-1, 1).astype(pc.dtype),
-                "person_flow": host(out.det_flow)[:m], "count": host(out.det_count)[:m],
-                "valid": host(out.det_valid)[:m].astype(bool), "centre": host(out.det_centre)[:m],
-                "prev": host(out.det_prev)[:m], "instance_mask": host(inst)}
+        return {"dets_xy_world": _host(out.det_xy_world)[:m], "dets_cls": _host(dc)[:m].reshape(-1, 1).astype(dtype),
+                "person_flow": _host(out.det_flow)[:m], "count": _host(out.det_count)[:m],
+                "valid": _host(out.det_valid)[:m].astype(bool), "centre": _host(out.det_centre)[:m],
+                "prev": _host(out.det_prev)[:m], "instance_mask": _host(inst)}
 
 
 class KeyframeOdometry:
@@ -525,12 +523,7 @@ class KeyframeOdometry:
         self._tab = _table_for(scan_phi)
         self._n = self._tab.numel() // 3
         self._min_dist = kw.pop("min_dist", 0.5)
-        known = {"cls_thresh", "max_range", "window", "gate", "max_gap", "huber_delta", "iters", "eps_theta", "eps_u",
-                 "min_pivot", "key_dist", "key_rot", "min_share", "max_misses"}
-        unknown = set(kw) - known
-        if unknown:
-            raise ValueError("unknown keyframe settings: %s" % sorted(unknown))
-        self._kw = kw
+        self._kw = _stage_kw(ops.keyframe_match, "keyframe", kw)
 
     _reset, _match = staticmethod(ops.keyframe_reset), staticmethod(ops.keyframe_match)
 
@@ -545,21 +538,16 @@ class KeyframeOdometry:
         cur = _to_dev(scan, torch.float32).reshape(1, -1)
         gate = {}
         if pred_cls is not None and pred_reg is not None:
-            pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
-            assert pc.ndim == 2 and pc.shape[1] == 1
-            _, dc, num, inst = ops.nms_predicted_center(cur, self._tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
-                                                        _to_dev(pred_reg, torch.float64).reshape(1, -1, 2),
-                                                        self._min_dist)
+            _, dc, num, inst, _ = _nms(cur, self._tab, pred_cls, pred_reg, self._min_dist)
             gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
         res = self._match(cur, self._tab, self._state, **gate, **self._kw)
-        host = lambda t: t[0].cpu().numpy()
         s = self._state
-        return res, {"pose": host(s.pose), "motion": host(res.motion), "ok": bool(res.ok[0].item()),
+        return res, {"pose": _host(s.pose), "motion": _host(res.motion), "ok": bool(res.ok[0].item()),
                      "count": int(res.count[0].item()), "rms": float(res.rms[0].item()),
                      "iters_used": int(res.iters_used[0].item()), "obs": float(res.obs[0].item()),
                      "key_replaced": bool(res.key_replaced[0].item()), "key_age": int(s.key_age[0].item()),
-                     "key_misses": int(s.key_misses[0].item()), "key_pose": host(s.key_pose), "corr": host(res.corr),
-                     "flow_residual": host(res.flow_residual)}
+                     "key_misses": int(s.key_misses[0].item()), "key_pose": _host(s.key_pose), "corr": _host(res.corr),
+                     "flow_residual": _host(res.flow_residual)}
 
 
 class KeyframeMapOdometry(KeyframeOdometry):
@@ -608,9 +596,7 @@ class OccupancyGrid:
     def __init__(self, scan_phi, res=0.1, size=512, **kw):
         # the settings first: a wrong one raises before anything touches the device
         self._min_dist = kw.pop("min_dist", 0.5)
-        unknown = set(kw) - {"cls_thresh", "max_range", "tol", "hit", "miss", "lo", "hi", "free_thresh"}
-        if unknown:
-            raise ValueError("unknown grid_map settings: %s" % sorted(unknown))
+        _stage_kw(ops.grid_map_update, "grid_map", kw, "res")
         H, W = (size, size) if np.ndim(size) == 0 else size
         self.res, self.shape = float(res), (int(H), int(W))
         if not self.res > 0.0:
@@ -631,11 +617,7 @@ class OccupancyGrid:
         cur = _to_dev(scan, torch.float32).reshape(1, -1)
         gate, dc = {}, None
         if pred_cls is not None and pred_reg is not None:
-            pc = pred_cls.detach().cpu().numpy() if _is_t(pred_cls) else np.asarray(pred_cls)
-            assert pc.ndim == 2 and pc.shape[1] == 1
-            _, dc, num, inst = ops.nms_predicted_center(cur, self._tab, _to_dev(pc[:, 0], torch.float64).reshape(1, -1),
-                                                        _to_dev(pred_reg, torch.float64).reshape(1, -1, 2),
-                                                        self._min_dist)
+            _, dc, num, inst, dtype = _nms(cur, self._tab, pred_cls, pred_reg, self._min_dist)
             gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
         rot, trans, _ = _pose_terms(None if odom is None else np.asarray(odom, dtype=np.float64)[None])
         if self._centre:                                       # the first pose of a sequence in the middle of the grid
@@ -643,22 +625,21 @@ class OccupancyGrid:
             self._centre = False
         out = ops.grid_map_update(cur, self._tab, _to_dev(rot, torch.float32), _to_dev(trans, torch.float64),
                                   self._state, res=self.res, **gate, **self._kw)
-        host = lambda t: t[0].cpu().numpy()
-        result = {"point_cell": host(out.point_cell), "point_mark": host(out.point_mark).astype(bool),
-                  "point_prior": host(out.point_prior)}
+        result = {"point_cell": _host(out.point_cell), "point_mark": _host(out.point_mark).astype(bool),
+                  "point_prior": _host(out.point_prior)}
         if dc is not None:
             m = int(num[0].item())
-            result.update(det_points=host(out.det_points)[:m], det_free=host(out.det_free)[:m],
-                          dets_cls=host(dc)[:m].reshape(-1, 1).astype(pc.dtype), instance_mask=host(inst))
+            result.update(det_points=_host(out.det_points)[:m], det_free=_host(out.det_free)[:m],
+                          dets_cls=_host(dc)[:m].reshape(-1, 1).astype(dtype), instance_mask=_host(inst))
         return result
 
     @property
     def origin(self):
-        return self._state.origin[0].cpu().numpy()
+        return _host(self._state.origin)
 
     @property
     def logodds(self):
-        return self._state.grid[0].cpu().numpy()
+        return _host(self._state.grid)
 
     def probability(self, unit=0.05):
         return 1.0 / (1.0 + np.exp(-float(unit) * self.logodds.astype(np.float64)))

@@ -50,11 +50,38 @@ _DEFAULT_CUTOUT = dict(fixed=True, centered=True, window_width=1.0, window_depth
                        padding_val=29.99, area_mode=True)
 
 
-def _settings(name, given, **defaults):
-    """The defaults of the argument ``name``, overridden by the dict it was given; a key without a default raises."""
+_MATCHERS = {"scan_match": ops.scan_match, "keyframe": ops.keyframe_match, "keyframe_map": ops.keyframe_map_match}
+
+
+def stage_defaults(arg, cls_thresh=0.5, method="flow"):
+    """What the dict given as the constructor argument ``arg`` ("ego_motion" with its ``method``, "tracks",
+    "person_motion", "grid_map") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
+    signature has them (``ops.stage_settings``), and -- stated here and nowhere else -- what the detector overrides or
+    adds.  ``cls_thresh``: the detector's."""
+    if arg == "ego_motion" and method == "flow":
+        # the displacement of a canonical flow under the rigid model, robustly: of ops.ego_motion's settings the dict
+        # holds these three, and the fit is re-weighted by default
+        kw = ops.stage_settings(ops.ego_motion)
+        return dict({k: kw[k] for k in ("huber_delta", "iters", "max_range")}, huber_delta=0.02, iters=4,
+                    cls_thresh=cls_thresh)
+    if arg == "ego_motion":
+        # keys: the ring's size, which ops.keyframe_map_buffers takes
+        return dict(ops.stage_settings(_MATCHERS[method]), cls_thresh=cls_thresh,
+                    **(dict(keys=16) if method == "keyframe_map" else {}))
+    if arg == "tracks":
+        return dict(ops.stage_settings(ops.track_update), max_tracks=64)
+    # person_motion and grid_map always take the detector's cls_thresh: it is not a key of their dicts
+    kw = ops.stage_settings({"person_motion": ops.person_motion, "grid_map": ops.grid_map_update}[arg])
+    del kw["cls_thresh"]
+    return dict(kw, res=0.1, size=512) if arg == "grid_map" else kw
+
+
+def stage_settings(arg, given, cls_thresh=0.5, method="flow"):
+    """``stage_defaults`` overridden by the dict the argument ``arg`` was given; a key that is not among them raises."""
+    defaults = stage_defaults(arg, cls_thresh, method)
     unknown = set(given) - set(defaults)
     if unknown:
-        raise ValueError("unknown %s settings: %s" % (name, sorted(unknown)))
+        raise ValueError("unknown %s settings: %s" % (arg, sorted(unknown)))
     return dict(defaults, **given)
 
 
@@ -181,8 +208,6 @@ class StreamingDetector:
         if flow_model is not None and self._nms is None:
             raise ValueError("flow_model needs nms_min_dist: the per-person flow is aggregated over the NMS masks")
         ego = {k: v for k, v in (ego_motion or {}).items() if k != "method"}
-        match = dict(window=16, gate=0.5, max_gap=0.3, huber_delta=0.05, iters=16, eps_theta=1e-7, eps_u=1e-7,
-                     min_pivot=1e-6, max_range=20.0, cls_thresh=self._cls_thresh)     # of the three scan matchers
         self._key_map = method == "keyframe_map"
 
         # Everything a stage touches is allocated here, before any capture, and the stages are listed in the order a
@@ -196,8 +221,7 @@ class StreamingDetector:
             self._prev_scan = torch.zeros((self.B, self.N, 1), dtype=torch.float32, device=dev)
         Stage, stages = self._Stage, []
         if method == "keyframe" or self._key_map:
-            kw = _settings("ego_motion", ego, **match, key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2,
-                           **(dict(keys=16, revisit=0.5) if self._key_map else {}))
+            kw = stage_settings("ego_motion", ego, self._cls_thresh, method)
             # the keyframe (or the ring of them), its bookkeeping and the pose live on the device
             if self._key_map:
                 self._key_state = ops.keyframe_map_buffers(self.B, self.N, kw.pop("keys"), dev)
@@ -215,7 +239,7 @@ class StreamingDetector:
             stages.append(Stage(self._keyframe_stage, tuple(self._key_state),
                                 lambda: self._key_reset(self._key_state)))        # the next scan becomes the keyframe
         if method == "scan_match":
-            self._match_kw = _settings("ego_motion", ego, **match)
+            self._match_kw = stage_settings("ego_motion", ego, self._cls_thresh, method)
             self._match_out = ops.scan_match_buffers(self.B, self.N, dev)     # its motion is also the next step's init
             self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
             from_first = person_motion is not None or grid_map is not None
@@ -229,14 +253,13 @@ class StreamingDetector:
             self._flow_model = flow_model.to(dev).eval()
             self._pf_out = ops.person_flow_buffers(self.B, self.N, dev)
             if ego_motion is not None and method == "flow":
-                self._ego_kw = _settings("ego_motion", ego, huber_delta=0.02, iters=4, max_range=20.0,
-                                         cls_thresh=self._cls_thresh)
+                self._ego_kw = stage_settings("ego_motion", ego, self._cls_thresh, method)
                 self._ego_out = ops.ego_motion_buffers(self.B, self.N, dev)
                 self._pose_state = torch.zeros((self.B, 3), dtype=torch.float64, device=dev)
             stages.append(Stage(self._flow_stage, () if self._ego_kw is None else (self._pose_state,),
                                 from_first=False))
         if person_motion is not None:
-            kw = _settings("person_motion", person_motion, reach=0.5, min_points=3, max_range=20.0)
+            kw = stage_settings("person_motion", person_motion)
             if not float(kw["reach"]) >= 0.0 or int(kw["min_points"]) < 1:
                 raise ValueError("reach must be >= 0 and min_points >= 1")
             self._pm_kw = dict(kw, cls_thresh=self._cls_thresh)
@@ -245,15 +268,13 @@ class StreamingDetector:
             stages.append(Stage(self._motion_stage, tuple(self._pm_state),
                                 lambda: ops.person_motion_reset(self._pm_state)))  # the next scan seeds the centroids
         if tracks is not None:
-            kw = _settings("tracks", tracks, max_tracks=64, gate=0.5, q=1e-4, r_pos=2.5e-3, r_vel=2.5e-3, v0_var=0.25,
-                           max_misses=3, min_hits=3)
+            kw = stage_settings("tracks", tracks)
             self._track_state = ops.track_buffers(self.B, kw.pop("max_tracks"), self.N, dev)
             self._filter_kw = kw
             stages.append(Stage(self._track_stage, tuple(self._track_state),
                                 lambda: ops.track_reset(self._track_state), from_first=person_motion is not None))
         if grid_map is not None:
-            kw = _settings("grid_map", grid_map, res=0.1, size=512, max_range=20.0, tol=None, hit=17, miss=8, lo=-40,
-                           hi=70, free_thresh=16)
+            kw = stage_settings("grid_map", grid_map)
             size = kw.pop("size")
             shape = tuple(int(s) for s in ((size, size) if np.ndim(size) == 0 else size))
             if len(shape) != 2 or any(s % 64 or not 64 <= s <= 2048 for s in shape):

@@ -561,5 +561,10 @@ def test_utils_and_streaming_signatures():
     assert list(inspect.signature(u.KeyframeOdometry.update).parameters) == ["self", "scan", "pred_cls", "pred_reg"]
     assert list(inspect.signature(u.KeyframeOdometry.reset).parameters) == ["self", "pose"]
     src = inspect.getsource(StreamingDetector)
-    for word in ('"keyframe"', "keyframe_match", "_key_state", "key_dist=0.3", "key_rot=0.3", "min_share=0.5", "max_misses=2"):
+    for word in ('"keyframe"', "keyframe_match", "_key_state"):
         assert word in src, word
+    # the detector's defaults are no literals in its source any more: they are what it hands the stage
+    from planar_optical_flow_amd.streaming import stage_settings
+    kw = stage_settings("ego_motion", {}, 0.5, "keyframe")
+    assert {k: kw[k] for k in ("key_dist", "key_rot", "min_share", "max_misses")} == \
+        dict(key_dist=0.3, key_rot=0.3, min_share=0.5, max_misses=2)

@@ -743,6 +743,10 @@ def test_utils_and_streaming_signatures():
     assert list(inspect.signature(u.KeyframeMapOdometry.update).parameters) == ["self", "scan", "pred_cls", "pred_reg"]
     assert list(inspect.signature(u.KeyframeMapOdometry.reset).parameters) == ["self", "pose"]
     src = inspect.getsource(StreamingDetector)
-    for word in ('"keyframe_map"', "keyframe_map_match", "keyframe_map_buffers", "keyframe_map_reset", "keys=16",
-                 "revisit=0.5", "key_switched", "key_slot"):
+    for word in ('"keyframe_map"', "keyframe_map_match", "keyframe_map_buffers", "keyframe_map_reset", "key_switched",
+                 "key_slot"):
         assert word in src, word
+    # the detector's defaults are no literals in its source any more: they are what it hands the stage
+    from planar_optical_flow_amd.streaming import stage_settings
+    kw = stage_settings("ego_motion", {}, 0.5, "keyframe_map")
+    assert (kw["keys"], kw["revisit"]) == (16, 0.5)

@@ -17,7 +17,9 @@ next to the keyframe matcher's, so one process gives the bare step, scan_match, 
 process): two more steps next to those, the chosen method's with person_motion=dict() as its tail and that one with
 tracks=dict() behind it, so one process gives the step without and with the person motion.
 --grid (alone or with --nms): the replayed step with ego_motion=dict(method="keyframe") without and with
-grid_map=dict() (512 x 512 cells of 0.1 m per sensor) as its last stage, alternating repeats in one process."""
+grid_map=dict() (512 x 512 cells of 0.1 m per sensor) as its last stage, alternating repeats in one process.
+--eager (with --ego, --tracks or --grid): those steps launched eagerly (graph=False) instead of replayed -- the host
+time of the stage wrappers, which a replay does not run."""
 import faulthandler, os, sys, time
 faulthandler.dump_traceback_later(90, exit=True)       # a stuck step reports where it is instead of hanging the box
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,7 +41,8 @@ KEYFRAME_MAP = dict(method="keyframe_map")
 KEYED = ("keyframe", "keyframe_map")
 TRACKS = "--tracks" in sys.argv
 GRID = "--grid" in sys.argv
-sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--person-motion", "--grid"))]
+EAGER = "--eager" in sys.argv
+sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--person-motion", "--grid", "--eager"))]
 
 
 class DiffFlow(torch.nn.Module):
@@ -61,7 +64,7 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
     scans = torch.from_numpy(synth.make_batch(seed=9, B=B, T=40).scans).cuda()     # [B, 40, 450]
     if EGO or TRACKS or GRID:
         poses = np.cumsum(np.random.default_rng(4).normal(0, 0.05, (40, B, 3)), axis=0)
-        mk = lambda **kw: StreamingDetector(model, batch=B, nms_min_dist=NMS, flow_model=flow_model, **kw)
+        mk = lambda **kw: StreamingDetector(model, batch=B, nms_min_dist=NMS, flow_model=flow_model, graph=not EAGER, **kw)
         if GRID:
             keyed_only, gridded = mk(ego_motion=KEYFRAME), mk(ego_motion=KEYFRAME, grid_map=dict())
             steps = {"keyframe": lambda t: keyed_only(scans[:, t]), "keyframe + grid_map": lambda t: gridded(scans[:, t])}
@@ -137,8 +140,8 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
         if TRACKS and not GRID:
             live, _, state = tracked.tracks()
             print("   tracks after 40 scans: %s live, next_id %s" % ([len(l) for l in live], state.next_id.tolist()))
-        print("streaming step B=%d [flow %s%s], hipGraph replay per scan, 4 alternating repeats of 32 steps: %s"
-              % (B, FLOW, ", ego" if EGO and TRACKS else "", ", ".join("%s %s ms" % (k, " ".join("%.3f" % v for v in vs)) for k, vs in ms.items())), flush=True)
+        print("streaming step B=%d [flow %s%s], %s per scan, 4 alternating repeats of 32 steps: %s"
+              % (B, FLOW, ", ego" if EGO and TRACKS else "", "eager launches" if EAGER else "hipGraph replay", ", ".join("%s %s ms" % (k, " ".join("%.3f" % v for v in vs)) for k, vs in ms.items())), flush=True)
         continue
     res = {}
     for graph in (False, True):
