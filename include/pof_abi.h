@@ -629,6 +629,55 @@ int pof_grid_map_update(const float *ranges, const double *tab, const float *rot
                         int32_t *det_free, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N13 scan-to-grid matching: the pose of a sensor corrected against its own occupancy grid (N12).  An exhaustive
+ * (correlative) search over whole-cell translations and a small table of rotations around the incoming pose, scored
+ * with integers only: it finds a pose that is off by a cell or more (a lost scan pair) to within about a cell and
+ * stays silent while the pose is good.  The reference has nothing of the kind; the specification is this comment
+ * (restated in NumPy by tests/test_grid_match.py).  One sensor per batch entry, two launches on the stream (the scores,
+ * then the pick).
+ * Settings: R = reach (0..16), K = rotations (odd, 1..33), T = 2 R + 1; min_points, min_score, min_gain >= 0 (integers;
+ *   the last two are grid counts per voting point).
+ * Inputs: ranges [B][N] float32, the current scan; tab the angle table; optionally the NMS results instance_mask
+ *   [B][N], num_det [B] (clamped to [0, N]) and det_cls [B][N], all three or none (NULL); grid [B][H][W] int16 and
+ *   origin [B][2] float64 of N12, both read only; res; rot_tab [K][3] float64 = (theta_k, cos theta_k, sin theta_k),
+ *   formed by the host with theta_k = (k - (K - 1) / 2) rot_step, whose middle row is exactly (0, 1, 0) -- the launch
+ *   calls no transcendental while it scores.
+ * In/out: pose [B][3] float64 = (x, y, phi), and the pose terms as pof_pose_advance writes them, rot [B][4] float32
+ *   row-major and trans [B][2] float64.
+ * A point i VOTES when r = (double)ranges[i] is finite, 0 < r < max_range, and it is no person's point (N12's rule:
+ *   1 <= id <= num_det and det_cls[id - 1] >= cls_thresh).  V = the number of voting points.
+ * The cell of a voting point under rotation k, float64, plain multiplies and adds (no FMA), (c, s) = rot_tab[k][1..2]:
+ *   p = (r cos_i, r sin_i),  p' = (c p_x - s p_y, s p_x + c p_y),
+ *   w_x = ((double)R00 p'_x + (double)R01 p'_y) + t_x,  w_y = ((double)R10 p'_x + (double)R11 p'_y) + t_y with the
+ *   INCOMING rot and trans,  g_x = floor((w_x - o_x) / res),  g_y = floor((w_y - o_y) / res) with a true division.
+ *   For the middle row p' = p exactly, so g is N12's point_cell arithmetic.
+ * scores [B][K][T][T] int32:  scores[b][k][a][e] = the sum over the voting points of grid[g_y + (a - R)][g_x + (e - R)].
+ *   A shifted cell outside the grid adds 0 (tested in integers once g is known to be finite); a point whose g_x or g_y
+ *   is not finite adds nothing for that k.
+ * The pick: best = the largest score; ties go to the smaller dx dx + dy dy (dy = a - R, dx = e - R), then the smaller
+ *   |kappa| (kappa = k - (K - 1) / 2), then the smaller flat index (k T + a) T + e.  zero = scores[b][(K - 1) / 2][R][R].
+ *   ok    = V >= min_points  and  best >= min_score V
+ *   moved = ok  and  the best candidate is not the zero candidate  and  best - zero >= min_gain V
+ *   with the products and the difference formed in int64.
+ * With moved:  x += (double)dx res,  y += (double)dy res,  phi += theta_k;  pose is written and rot, trans are written
+ *   from it as pof_pose_advance writes them.  Without moved pose, rot and trans keep their bits: nothing is stored.
+ * Outputs: scores (required: it also carries the sums from the first launch to the second); best [B][3] int32 =
+ *   (kappa, dy, dx) of the best candidate, written always; score [B][2] int32 = (best, zero); votes [B] int32 = V;
+ *   ok [B], moved [B] uint8; correction [B][3] float64 = ((double)dx res, (double)dy res, theta_k), zeros without moved.
+ * Integer sums, no global atomics: the same bits in every run, at every batch position and in a graph replay.
+ * POF_E_BADARG (checked first; nothing written): a NULL pointer other than the three NMS results, NMS pointers given
+ *   in part, res not > 0, max_range not > 0, reach outside [0, 16], rotations outside [1, 33] or even, min_points,
+ *   min_score or min_gain < 0, B < 0, N < 1.  POF_E_SHAPE (nothing written): N > 4096, H or W not a multiple of 64 or
+ *   outside [64, 2048].  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_grid_match(const float *ranges, const double *tab, const int32_t *instance_mask, const int32_t *num_det,
+                   const double *det_cls, double cls_thresh, double max_range, const int16_t *grid,
+                   const double *origin, double res, const double *rot_tab, int reach, int rotations, int min_points,
+                   int min_score, int min_gain, int B, int N, int H, int W, double *pose, float *rot, double *trans,
+                   int32_t *scores, int32_t *best, int32_t *score, int32_t *votes, uint8_t *ok, uint8_t *moved,
+                   double *correction, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

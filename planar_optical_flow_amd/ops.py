@@ -920,12 +920,13 @@ def nms_predicted_center(ranges, tab, pred_cls, pred_reg, min_dist=0.5):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The per-scan stages N5-N12.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
+# The per-scan stages N5-N13.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
 # a dtype and a symbolic shape per field.  ``_zeros_of`` allocates a record, ``_checked`` takes a caller's and
 # ``_out_of`` does whichever an ``out=`` needs; ``stage_settings`` reads a wrapper's tunable scalars off its signature.
 def _record(name, persistent=None, **fields):
     """The namedtuple class ``name`` with one field per keyword, in their order: field=(dtype, *dims), a dim being a
-    number or the name of a size ("B" sensors, "N" points, "K" keys, "M" track slots, "H" x "W" cells).  The fields of
+    number or the name of a size ("B" sensors, "N" points, "K" keys or rotations, "M" track slots, "H" x "W" cells, "T"
+    translations per axis).  The fields of
     the dict ``persistent`` come first and are the ones that carry over from scan to scan (``cls.persistent``, their
     names); ``cls.spec`` is the (dtype, dims) of every field."""
     fields = dict(persistent or {}, **fields)
@@ -965,7 +966,7 @@ def _out_of(cls, out, device, **sizes):
 
 
 _STAGE_TENSORS = frozenset(("init", "xy", "weight", "instance_mask", "num_det", "det_cls", "out", "rot", "trans",
-                            "flow_trans"))
+                            "flow_trans", "table"))
 REQUIRED = inspect.Parameter.empty
 
 
@@ -1572,6 +1573,83 @@ def grid_map_update(ranges, tab, rot, trans, state, *, res, instance_mask=None, 
                   float(res), float(res if tol is None else tol), float(max_range), float(cls_thresh), int(hit),
                   int(miss), int(lo), int(hi), int(free_thresh), B, N, H, W, *[_ptr(t) for t in state],
                   *[_ptr(t) for t in out], _stream())
+    return out
+
+
+GridMatch = _record("GridMatch", scores=(_I32, "B", "K", "T", "T"), best=(_I32, "B", 3), score=(_I32, "B", 2),
+                    votes=(_I32, "B"), ok=(_U8, "B"), moved=(_U8, "B"), correction=(_F64, "B", 3))
+
+
+def _check_search(reach, rotations):
+    if not 0 <= int(reach) <= 16:
+        raise ValueError("reach must be in [0, 16]")
+    if not 1 <= int(rotations) <= 33 or int(rotations) % 2 == 0:
+        raise ValueError("rotations must be odd and in [1, 33]")
+
+
+def grid_match_buffers(B, reach=4, rotations=9, device="cuda"):
+    """The seven outputs of ``grid_match`` for B sensors and a search of ``rotations`` x (2 ``reach`` + 1)^2 candidates,
+    zero-filled, as its ``out=`` (allocate once, before a graph capture)."""
+    _check_search(reach, rotations)
+    return _zeros_of(GridMatch, device, B=B, K=int(rotations), T=2 * int(reach) + 1)
+
+
+def grid_match_table(rot_step=0.01, rotations=9, device="cuda"):
+    """The rotation table of ``grid_match`` -> [rotations, 3] f64 = (theta, cos theta, sin theta) with theta_k =
+    (k - (rotations - 1) / 2) ``rot_step``, cosines and sines by NumPy; the middle row is exactly (0, 1, 0)."""
+    _check_search(0, rotations)
+    theta = (np.arange(int(rotations), dtype=np.float64) - (int(rotations) - 1) // 2) * float(rot_step)
+    return torch.from_numpy(np.stack([theta, np.cos(theta), np.sin(theta)], axis=1)).to(device)
+
+
+def grid_match(ranges, tab, rot, trans, pose, state, *, res, table=None, instance_mask=None, num_det=None,
+               det_cls=None, cls_thresh=0.5, max_range=20.0, reach=4, rotations=9, rot_step=0.01, min_points=50,
+               min_score=20, min_gain=8, out=None):
+    """N13: the pose of every sensor corrected against its occupancy grid, two launches per batch (include/pof_abi.h
+    states the rules in full).
+
+    ranges [B,N] f32, the current scan; tab the angle table; rot [B,2,2] (or [B,4]) f32, trans [B,2] f64 and pose [B,3]
+    f64 = (x, y, phi), the sensor's pose at this scan as ``pose_advance`` leaves it, all three UPDATED IN PLACE when a
+    sensor is moved.  ``state``: the ``GridMapState`` of ``grid_map_update``, read only; ``res``: its metres per cell.
+    Every point that votes (finite, 0 < r < ``max_range``, no point of a detection of score >= ``cls_thresh`` when the
+    NMS results instance_mask [B,N] i32, num_det [B] i32, det_cls [B,N] f64 are given, all three or none) is entered at
+    ``rotations`` rotations, ``rot_step`` radians apart around the pose, and (2 ``reach`` + 1)^2 whole-cell
+    translations, and the grid values under it are summed, in integers.  The best candidate (ties: the shorter
+    translation, the smaller rotation, the lower index) is ``ok`` with at least ``min_points`` voting points and a score
+    of at least ``min_score`` per voting point; the sensor is ``moved`` there when it is not the incoming pose and gains
+    at least ``min_gain`` per voting point over it.  ``table``: ``grid_match_table(rot_step, rotations)``; None builds
+    it, which allocates -- a graph capture passes its own (``rot_step`` is then not read).
+    -> ``GridMatch``: scores [B,rotations,T,T] i32, best [B,3] i32 = (rotation, dy, dx) of the best candidate in steps
+    and cells, score [B,2] i32 = (the best, the incoming pose's), votes [B] i32, ok [B], moved [B] u8, correction [B,3]
+    f64 = (dx res, dy res, theta), zeros without ``moved``.  The same bits in every run.  ``out``: a ``GridMatch`` of
+    preallocated tensors (``grid_match_buffers``)."""
+    ranges, tab, B, N, dev = _scan_input(ranges, tab)
+    if rot is None or trans is None or pose is None:
+        raise TypeError("rot, trans and pose must be tensors on the HIP device (no CPU path)")
+    _check_pose_terms(B, rot, trans, None)
+    if tuple(_dev(pose, torch.float64, "pose").shape) != (B, 3):
+        raise ValueError("pose must be [B,3]")
+    if instance_mask is None and (num_det is not None or det_cls is not None):
+        raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
+    gate = _nms_gate(instance_mask, num_det, det_cls, B, N)
+    state = GridMapState(*state)
+    if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
+        raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
+    H, W = state.grid.shape[1:]
+    state = _checked(GridMapState, state, "state", B=B, H=H, W=W)
+    _check_search(reach, rotations)
+    if table is None:
+        table = grid_match_table(rot_step, rotations, dev)
+    if tuple(_dev(table, torch.float64, "table").shape) != (int(rotations), 3):
+        raise ValueError("table must be [rotations,3] (grid_match_table)")
+    out = _out_of(GridMatch, out, dev, B=B, K=int(rotations), T=2 * int(reach) + 1)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_grid_match", _ptr(ranges), _ptr(tab), *[_ptr(t) for t in gate], float(cls_thresh),
+                  float(max_range), _ptr(state.grid), _ptr(state.origin), float(res), _ptr(table), int(reach),
+                  int(rotations), int(min_points), int(min_score), int(min_gain), B, N, H, W, _ptr(pose), _ptr(rot),
+                  _ptr(trans), *[_ptr(t) for t in out], _stream())
     return out
 
 

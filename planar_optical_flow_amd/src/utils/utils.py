@@ -591,7 +591,8 @@ class OccupancyGrid:
     point_prior [N], and with predictions det_points [M], det_free [M], dets_cls [M,1] and instance_mask [N].
     ``reset(origin)``: every cell unknown; origin [2] = the world position of the grid's lower corner -- by default the
     next update puts its pose in the middle of the grid.  ``logodds`` is the grid [H,W] int16 on the host,
-    ``probability(unit)`` the occupancy probability of a count worth ``unit`` nat."""
+    ``probability(unit)`` the occupancy probability of a count worth ``unit`` nat.  ``localize(scan, odom, ...)``
+    corrects a pose against the grid as it stands (``ops.grid_match``) without updating it."""
 
     def __init__(self, scan_phi, res=0.1, size=512, **kw):
         # the settings first: a wrong one raises before anything touches the device
@@ -632,6 +633,28 @@ class OccupancyGrid:
             result.update(det_points=_host(out.det_points)[:m], det_free=_host(out.det_free)[:m],
                           dets_cls=_host(dc)[:m].reshape(-1, 1).astype(dtype), instance_mask=_host(inst))
         return result
+
+    def localize(self, scan, odom, pred_cls=None, pred_reg=None, **settings):
+        """The pose ``odom`` = (x, y, phi) corrected against the grid as it stands (``ops.grid_match``, two launches;
+        ``settings``: its ``reach``, ``rotations``, ``rot_step``, ``min_points``, ``min_score``, ``min_gain``).  The
+        grid is not updated.  With predictions the centre NMS runs first and people's points do not vote.
+        -> (the corrected (x, y, phi) [3], dict of best [3] = (rotation steps, dy, dx in cells), score [2] = (the best
+        candidate's, the given pose's), votes, ok, moved (bool) and correction [3])."""
+        _stage_kw(ops.grid_match, "grid_match", settings, "res", "cls_thresh", "max_range")
+        cur = _to_dev(scan, torch.float32).reshape(1, -1)
+        gate = {}
+        if pred_cls is not None and pred_reg is not None:
+            _, dc, num, inst, _ = _nms(cur, self._tab, pred_cls, pred_reg, self._min_dist)
+            gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
+        pose = np.asarray(odom, dtype=np.float64).reshape(1, 3)
+        rot, trans, _ = _pose_terms(pose)
+        pose = _to_dev(pose, torch.float64)
+        shared = {k: self._kw[k] for k in ("cls_thresh", "max_range") if k in self._kw}
+        out = ops.grid_match(cur, self._tab, _to_dev(rot, torch.float32), _to_dev(trans, torch.float64), pose,
+                             self._state, res=self.res, **gate, **shared, **settings)
+        return _host(pose), {"best": _host(out.best), "score": _host(out.score), "votes": int(out.votes[0].item()),
+                             "ok": bool(out.ok[0].item()), "moved": bool(out.moved[0].item()),
+                             "correction": _host(out.correction)}
 
     @property
     def origin(self):

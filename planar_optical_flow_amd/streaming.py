@@ -12,9 +12,9 @@ A model fused with ``embed="hip"`` has its gate embedding as one HIP node for th
 float16 storage (float16 cutout and template).
 
 Behind the trunk (cutout, model, NMS) a scan runs the stages its detector was built with, always in this order and on
-one stream, so a capture stays one linear chain: the keyframe launch; the scan matcher and its pose launch; the flow
-net; the flow fit and its pose launch; the per-person flow; the person motion; the track update; the grid map; the
-copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
+one stream, so a capture stays one linear chain: the keyframe launch; the scan matcher and its pose launch; the
+scan-to-grid match; the flow net; the flow fit and its pose launch; the per-person flow; the person motion; the track
+update; the grid map; the copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
 capture's warm-up and the captured region are each a loop over it, the warm-up puts back exactly the state the table names, and
 ``reset()`` clears exactly that ("The stage table").  The paragraphs below say what each stage is.
 With a ``flow_model`` the step ends in the per-person flow (``ops.person_flow``): a flow net on the previous
@@ -38,6 +38,10 @@ world-frame centroid of its own scan points, paired with the previous scan's cen
 stands in for the per-person flow, and with ``tracks`` it feeds ``ops.track_update`` in the same chain.
 With ``grid_map`` the chain also holds ``ops.grid_map_update``: every scan is entered at the step's
 pose into an occupancy grid per sensor that stays on the device, and every scan point learns what its cell held before.
+With ``grid_match`` (and ``method="scan_match"`` plus ``grid_map``) ``ops.grid_match`` stands directly behind the scan
+matcher's pose launch: the scan is scored against the grid at whole-cell shifts and a few rotations
+around the pose, in integers, and a pose that has lost a scan pair is put back before any later stage reads it and
+before the scan is entered into the map.
 """
 from collections import namedtuple
 
@@ -55,7 +59,7 @@ _MATCHERS = {"scan_match": ops.scan_match, "keyframe": ops.keyframe_match, "keyf
 
 def stage_defaults(arg, cls_thresh=0.5, method="flow"):
     """What the dict given as the constructor argument ``arg`` ("ego_motion" with its ``method``, "tracks",
-    "person_motion", "grid_map") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
+    "person_motion", "grid_map", "grid_match") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
     signature has them (``ops.stage_settings``), and -- stated here and nowhere else -- what the detector overrides or
     adds.  ``cls_thresh``: the detector's."""
     if arg == "ego_motion" and method == "flow":
@@ -70,9 +74,12 @@ def stage_defaults(arg, cls_thresh=0.5, method="flow"):
                     **(dict(keys=16) if method == "keyframe_map" else {}))
     if arg == "tracks":
         return dict(ops.stage_settings(ops.track_update), max_tracks=64)
-    # person_motion and grid_map always take the detector's cls_thresh: it is not a key of their dicts
-    kw = ops.stage_settings({"person_motion": ops.person_motion, "grid_map": ops.grid_map_update}[arg])
+    # person_motion, grid_map and grid_match always take the detector's cls_thresh: it is not a key of their dicts
+    kw = ops.stage_settings({"person_motion": ops.person_motion, "grid_map": ops.grid_map_update,
+                             "grid_match": ops.grid_match}[arg])
     del kw["cls_thresh"]
+    if arg == "grid_match":
+        del kw["res"]                                          # the grid's: a key of grid_map's dict
     return dict(kw, res=0.1, size=512) if arg == "grid_map" else kw
 
 
@@ -144,7 +151,16 @@ class StreamingDetector:
     scan into an occupancy grid per sensor at the step's pose; with ``nms_min_dist`` the points of this scan's
     confident detections are not burned in and ``det_points`` / ``det_free`` say per detection how many of its points
     lie on cells seen free.  ``grid_map()`` returns the grid and the per-point outputs, and ``reset()`` empties the
-    grid and puts the start pose in its middle."""
+    grid and puts the start pose in its middle.
+
+    ``grid_match`` (needs ``grid_map`` and ``ego_motion=dict(method="scan_match")``; with ``"keyframe"``,
+    ``"keyframe_map"``, a pose per call or a ``flow_model`` it is refused, not built): None, or a dict of ``reach`` (4
+    cells), ``rotations`` (9), ``rot_step`` (0.01 rad), ``min_points`` (50), ``min_score`` (20), ``min_gain`` (8) and
+    ``max_range`` of ``ops.grid_match``.  Every step, the first of a sequence included, then scores the scan against
+    the sensor's grid around the dead-reckoned pose, directly behind the pose launch, and moves the pose and its terms
+    when a shifted or turned candidate is clearly better: what a failed scan pair lost is put back before the person
+    stages and the grid update read the pose.  ``grid_match()`` returns what was found; ``reset()`` needs nothing new
+    (an empty grid scores 0 and moves nothing)."""
 
     # One stage of a scan behind the trunk.  launch(first) enqueues it on the current stream (first: the first scan of a
     # sequence) and writes only fixed buffers; state: the tensors it advances, which a capture's warm-up puts back;
@@ -154,7 +170,7 @@ class StreamingDetector:
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
                  nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None,
-                 grid_map=None):
+                 grid_map=None, grid_match=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -187,7 +203,7 @@ class StreamingDetector:
         # what a feature was built with, None without it; _filter_kw: the settings of ops.track_update (a detector
         # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
-        self._gm_kw = None
+        self._gm_kw = self._sg_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
@@ -202,6 +218,12 @@ class StreamingDetector:
         if grid_map is not None and ego_motion is not None and method == "flow":
             raise ValueError("grid_map with ego_motion method='flow' is not built: use 'scan_match', 'keyframe' or "
                              "'keyframe_map', or no ego_motion and det(scan, pose=...)")
+        if grid_match is not None:
+            if grid_map is None or method != "scan_match" or ego_motion is None:
+                raise ValueError("grid_match corrects the pose of ego_motion method='scan_match' against grid_map: with "
+                                 "'keyframe', 'keyframe_map' or det(scan, pose=...) it is not built")
+            if flow_model is not None:
+                raise ValueError("grid_match with a flow_model is not built: flow_trans is not corrected")
         self._cls_thresh = float(cls_thresh)
         if tracks is not None and flow_model is None and person_motion is None:
             raise ValueError("tracks needs flow_model: the tracks are fed by the per-person flow")
@@ -249,6 +271,18 @@ class StreamingDetector:
             stages.append(Stage(self._match_stage, (self._match_out.motion, self._pose_state),
                                 self._match_out.motion.zero_,                    # the first pair starts from rest
                                 from_first=from_first))
+        if grid_match is not None:
+            # directly behind the pose launch: every later stage reads the corrected terms.  The grid is allocated
+            # below, so the stage reads self._gm_state when it runs; it advances nothing but the pose, which is in
+            # the match stage's snapshot, and from an empty grid it is not ok
+            kw = stage_settings("grid_match", grid_match)
+            self._sg_out = ops.grid_match_buffers(self.B, kw["reach"], kw["rotations"], dev)
+            self._sg_table = ops.grid_match_table(kw["rot_step"], kw["rotations"], dev)
+            for k in ("min_points", "min_score", "min_gain"):
+                if int(kw[k]) < 0:
+                    raise ValueError("grid_match %s must be >= 0" % k)
+            self._sg_kw = dict(kw, cls_thresh=self._cls_thresh)
+            stages.append(Stage(self._grid_match_stage))
         if flow_model is not None:
             self._flow_model = flow_model.to(dev).eval()
             self._pf_out = ops.person_flow_buffers(self.B, self.N, dev)
@@ -420,6 +454,13 @@ class StreamingDetector:
         ops.grid_map_update(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._gm_state,
                             out=self._gm_out, **self._match_gate(), **self._gm_kw)
 
+    # Behind the scan matcher's pose launch and in front of everything that reads the pose terms: the pose against the
+    # grid as the scans before this one left it.
+    def _grid_match_stage(self, first):
+        ops.grid_match(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._pose_state, self._gm_state,
+                       res=self._gm_kw["res"], table=self._sg_table, out=self._sg_out, **self._match_gate(),
+                       **self._sg_kw)
+
     def _gm_centre(self, xy):
         """The origin that puts the world positions xy [B,2] in the middle of their grids."""
         H, W = self._gm_state.grid.shape[1:]
@@ -556,6 +597,18 @@ class StreamingDetector:
         if self._gm_kw is None or self._seen < 1:
             raise RuntimeError("construct the detector with grid_map and feed it a scan first")
         return self._gm_state, self._gm_out
+
+    def grid_match(self):
+        """-> (list with one dict per sensor of the last step's scan-to-grid match: best [3] = (rotation steps, dy, dx
+        in cells), score [2] = (the best candidate's, the incoming pose's), votes, ok, moved and correction [3] = what
+        was added to (x, y, phi);  the device-resident ``ops.GridMatch``, valid until the next call).  Needs
+        ``grid_match`` and one scan.  Synchronises."""
+        if self._sg_kw is None or self._seen < 1:
+            raise RuntimeError("construct the detector with grid_match and feed it a scan first")
+        o = self._sg_out
+        h = {k: getattr(o, k).cpu().numpy() for k in ("best", "score", "votes", "ok", "moved", "correction")}
+        return [{"best": h["best"][b], "score": h["score"][b], "votes": int(h["votes"][b]), "ok": bool(h["ok"][b]),
+                 "moved": bool(h["moved"][b]), "correction": h["correction"][b]} for b in range(self.B)], o
 
     def ego_motion(self):
         """-> list (one dict per sensor) of the last step's fit: motion [3] = (theta, u_x, u_y) since the previous

@@ -1,5 +1,5 @@
 """Per-kernel timing on the GPU box (events on torch's current stream, which is the
-stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] ..."""
+stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -219,13 +219,17 @@ if "person" in which:
             "max_tracks %d: %.3f ms, %.0f live tracks per sensor" % (M, ms_t[M], (tracks[M].track_id > 0).sum().item() / B)
             for M in tracks)))
 
-if "grid" in which:
+if "grid" in which or "gridmatch" in which:
     # N12: the occupancy grid map, 450 beams into 512 x 512 cells of 0.1 m per sensor, for 1024, 8 and 1 sensors, next
     # to person_motion on the same scans, NMS results and pose (alternating, three repeats of 50 launches).  The same
     # scan every call, with lo / hi at the int16 limits so that no cell saturates inside the run and every launch
     # stores what a first scan would.  Bytes: 2 * H * W * 2 per sensor is the bound of a launch that loads and stores
     # the whole grid; `changed` counts the 16-byte runs one launch really stored, `near` the share of tiles that are
     # not left at once (nearest point within max_range, or inside the box of the endpoints).
+    # gridmatch: N13 next to it on the same scans, NMS results, pose and grid (the grid as two updates left it, a copy
+    # so that the search reads the same cells every call), defaults: 9 rotations x 81 translations.  The pose starts
+    # off by (0.23, -0.17) m and 0.02 rad; a moved pose stays moved, so from the second launch on the search starts
+    # where the first one ended (the work of a launch does not depend on it).  Gathers: 9 * 81 * votes int16.
     N, H, W, RES = 450, 512, 512, 0.1
     rng = np.random.default_rng(1701)
     tab = ops.phi_table()
@@ -250,7 +254,25 @@ if "grid" in which:
         runs = int((gm_state.grid != before).view(B, H, W // 8, 8).any(dim=3).sum().item())
         touched = (gm_state.grid != 0).view(B, H // 64, 64, W // 64, 64).any(dim=4).any(dim=2).float().mean().item()
         del before
-        for rep in range(3):
+        if "gridmatch" in which:
+            sg_state = ops.GridMapState(gm_state.grid.clone(), gm_state.origin.clone())
+            sg_out, sg_table = ops.grid_match_buffers(B, device=dev), ops.grid_match_table(device=dev)
+            off = torch.tensor([0.23, -0.17, 0.02], dtype=torch.float64, device=dev)
+            pose = torch.cat([trans, torch.from_numpy(ang).to(dev)[:, None]], dim=1) + off
+            sg_rot = torch.stack([pose[:, 2].cos(), -pose[:, 2].sin(), pose[:, 2].sin(), pose[:, 2].cos()], 1).float().contiguous()
+            sg_trans = pose[:, :2].contiguous()
+            match = lambda: ops.grid_match(scans, tab, sg_rot, sg_trans, pose, sg_state, res=RES, table=sg_table,
+                                           instance_mask=inst, num_det=num, det_cls=dc, out=sg_out)
+            match()
+            first = (sg_out.moved.sum().item(), sg_out.ok.sum().item())
+            for rep in range(3):
+                ms_g, ms_m = timeit(grid, iters=50), timeit(match, iters=50)
+                print("gridmatch B=%d N=%d %dx%d at %.2f m: grid_match %.3f ms (%.2f us per sensor) next to grid_map_update "
+                      "%.3f ms; %.0f voting points per scan, %.1f M int16 gathers per launch; first launch ok %d, moved %d "
+                      "of %d" % (B, N, H, W, RES, ms_m, ms_m / B * 1e3, ms_g, sg_out.votes.sum().item() / B,
+                                 9 * 81 * sg_out.votes.sum().item() / 1e6, first[1], first[0], B))
+            del sg_state
+        for rep in range(3 if "grid" in which else 0):
             ms_g, ms_pm = timeit(grid, iters=50), timeit(motion, iters=50)
             bound = B * 2 * H * W * 2
             print("grid B=%d N=%d %dx%d at %.2f m: grid_map_update %.3f ms (%.2f us per sensor) next to person_motion %.3f ms; "
