@@ -678,6 +678,41 @@ int pof_grid_match(const float *ranges, const double *tab, const int32_t *instan
                    double *correction, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N14 scrolling occupancy grid: the grid of N12 follows its sensor.  When the sensor comes within `margin` cells of a
+ * border the grid is shifted by whole tiles of 64 cells so that the sensor's tile is the middle tile again -- the tile
+ * a reset centres it on -- and what scrolls in is unknown.  The reference has nothing of the kind; the specification
+ * is this comment (restated in NumPy by tests/test_grid_scroll.py).  One sensor per batch entry, two launches on the
+ * stream (the shifted grid into scratch, then back).
+ * State per sensor: N12's grid [B][H][W] int16 and origin [B][2] float64, the origin now WRITTEN by this stage;
+ *   persistent base [B][2] float64, the origin as the last reset set it, read only, and offset [B][2] int32, the
+ *   cumulative shift in tiles of 64 cells as (x, y); a workspace scratch [B][H][W] int16 whose content means nothing
+ *   between calls.
+ * Inputs: trans [B][2] float64 (the pose terms' translation), res, margin in cells.
+ * Per axis, shown for x with TW = W / 64, float64, plain operations (no FMA):
+ *   c_x = floor((t_x - o_x) / res): N12's point_cell arithmetic applied to the sensor position, a true division.
+ *   c_x not finite or |c_x| >= 2^30:  s_x = 0.  Otherwise, with the integer c_x and q_x = c_x floor-divided by 64:
+ *   s_x = q_x - floor(TW / 2) when c_x < margin or c_x >= W - margin, else 0.
+ *   A shift that would make |offset_x + s_x| > 2^20 is not made (s_x = 0).
+ *   A triggered scroll puts the sensor's tile back on tile floor(TW / 2), the tile a reset centres it on: the next
+ *   scroll is half a grid of travel away.
+ * With (s_x, s_y) != (0, 0):  grid'[iy][ix] = grid[iy + 64 s_y][ix + 64 s_x] where that cell exists, else 0 (unknown);
+ *   offset += s;  origin = base + (double)(64 offset) res, computed from base and not accumulated: a sensor that scrolls
+ *   away and back gets its origin's old bits back, and its cells line up with the old ones exactly.
+ * Without a shift grid, origin and offset keep their bits: nothing is stored to them.
+ * Outputs: shift [B][2] int32 = (s_x, s_y) and scrolled [B] uint8, both always written.
+ * Whole tiles: every row of a 64 x 64 tile stays one 128-byte line, the copy is 16-byte loads and stores in the thread
+ *   layout of N12's cells launch, and cell indices move by multiples of 64.
+ * No atomics and no sums: the same bits in every run, at every batch position and in a graph replay.
+ * POF_E_BADARG (nothing written): a NULL pointer, res not > 0, margin < 0, B < 0 (these are checked first); with H and
+ *   W inside N12's rule, margin > 64 floor((TW - 1) / 2) or the same for H -- the bound keeps a re-centred sensor outside
+ *   the margin.  POF_E_SHAPE (nothing written): H or W not a multiple of 64 or outside [64, 2048], grid or scratch not
+ *   16-byte aligned, B H W / 4096 >= 2^31.  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_grid_scroll(const double *trans, double res, int margin, int B, int H, int W, int16_t *grid, double *origin,
+                    const double *base, int32_t *offset, int16_t *scratch, int32_t *shift, uint8_t *scrolled,
+                    pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

@@ -31,16 +31,13 @@
 // A tile wholly outside the field of view is not detected (not built).
 #include <cmath>
 
+#include "pof_grid.h"
 #include "pof_sensor.h"
 
 namespace {
 
 using namespace pof_sensor;
-
-constexpr int kTile = 64;                       // cells per tile side: a row of int16 is one 128-byte line
-constexpr int kCellThreads = 256;
-constexpr int kRun = 8;                         // neighbouring cells per thread: 16 bytes
-constexpr int kMinSide = 64, kMaxSide = 2048;
+using namespace pof_grid;                       // the tile form: kTile, kCellThreads, kRun, kMinSide, kMaxSide
 
 struct GridMapArgs {
     const float *ranges;

@@ -920,7 +920,7 @@ def nms_predicted_center(ranges, tab, pred_cls, pred_reg, min_dist=0.5):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The per-scan stages N5-N13.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
+# The per-scan stages N5-N14.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
 # a dtype and a symbolic shape per field.  ``_zeros_of`` allocates a record, ``_checked`` takes a caller's and
 # ``_out_of`` does whichever an ``out=`` needs; ``stage_settings`` reads a wrapper's tunable scalars off its signature.
 def _record(name, persistent=None, **fields):
@@ -1650,6 +1650,79 @@ def grid_match(ranges, tab, rot, trans, pose, state, *, res, table=None, instanc
                   float(max_range), _ptr(state.grid), _ptr(state.origin), float(res), _ptr(table), int(reach),
                   int(rotations), int(min_points), int(min_score), int(min_gain), B, N, H, W, _ptr(pose), _ptr(rot),
                   _ptr(trans), *[_ptr(t) for t in out], _stream())
+    return out
+
+
+GridScrollState = _record("GridScrollState", persistent=dict(base=(_F64, "B", 2), offset=(_I32, "B", 2)),
+                          scratch=(_I16, "B", "H", "W"))
+GridScroll = _record("GridScroll", shift=(_I32, "B", 2), scrolled=(_U8, "B"))
+
+
+def grid_scroll_buffers(B, device="cuda"):
+    """The two outputs of ``grid_scroll`` for B sensors, zero-filled, as its ``out=`` (allocate once, before a graph
+    capture)."""
+    return _zeros_of(GridScroll, device, B=B)
+
+
+def grid_scroll_state(B, H, W, device="cuda"):
+    """What ``grid_scroll`` keeps for B sensors beside the ``GridMapState`` it scrolls: the origin of the last reset,
+    the shift since then in tiles, and a workspace of the grid's size (allocate once, before a graph capture).
+    -> ``GridScrollState``."""
+    return _zeros_of(GridScrollState, device, B=B, H=H, W=W)
+
+
+def grid_scroll_reset(scroll, state):
+    """The grid of ``state`` (a ``GridMapState``) stands where it was reset to: base <- state.origin and offset <- 0, in
+    place, with tensor ops on the current stream (no host sync).  Call it after any ``grid_map_reset``."""
+    scroll = GridScrollState(*scroll)
+    scroll.base.copy_(GridMapState(*state).origin)
+    scroll.offset.zero_()
+    return scroll
+
+
+def grid_scroll_margin(H, W, margin=None):
+    """The ``margin`` of ``grid_scroll`` for a grid of H x W cells.  None: the default, a quarter of the shorter side
+    rounded down to a multiple of 64.  A given one must lie in [0, 64 floor((side / 64 - 1) / 2)] for both sides -- a
+    re-centred sensor then stands outside it -- or this raises: what wraps the stage checks its setting here, before
+    anything is allocated."""
+    if margin is None:
+        return min(int(H), int(W)) // 4 // 64 * 64
+    if not 0 <= int(margin) <= 64 * ((min(int(H), int(W)) // 64 - 1) // 2):
+        raise ValueError("margin must be in [0, 64 floor((side / 64 - 1) / 2)]")
+    return int(margin)
+
+
+def grid_scroll(trans, state, scroll, *, res, margin=None, out=None):
+    """N14: the occupancy grid of every sensor follows it, two launches per batch (include/pof_abi.h states the rule in
+    full).
+
+    trans [B,2] f64, the sensor's position at this scan as ``pose_advance`` and the keyframe matchers write it.
+    ``state``: the ``GridMapState`` of ``grid_map_update``, grid AND origin UPDATED IN PLACE; ``scroll``: a
+    ``GridScrollState`` (``grid_scroll_state``, set by ``grid_scroll_reset``), its offset UPDATED IN PLACE; ``res``: the
+    grid's metres per cell.  A sensor within ``margin`` cells of a border of its grid (None: ``grid_scroll_margin``, a
+    quarter of the shorter side in whole tiles; at most 64 floor((side / 64 - 1) / 2)) has the grid shifted by whole
+    tiles of 64 cells so that it stands on the middle tile again; what scrolls in is unknown (0), the origin moves with
+    it, and a grid that does not scroll keeps every bit.
+    -> ``GridScroll``: shift [B,2] i32 = the shift of this call in tiles (x, y), scrolled [B] u8.  The same bits in every
+    run.  ``out``: a ``GridScroll`` of preallocated tensors (``grid_scroll_buffers``)."""
+    if trans is None:
+        raise TypeError("trans must be a tensor on the HIP device (no CPU path)")
+    trans = _dev(trans, torch.float64, "trans")
+    if trans.dim() != 2 or trans.shape[1] != 2:
+        raise ValueError("trans must be [B,2]")
+    B, dev = trans.shape[0], trans.device
+    state = GridMapState(*state)
+    if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
+        raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
+    H, W = state.grid.shape[1:]
+    state = _checked(GridMapState, state, "state", B=B, H=H, W=W)
+    scroll = _checked(GridScrollState, scroll, "scroll", B=B, H=H, W=W)
+    out = _out_of(GridScroll, out, dev, B=B)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_grid_scroll", _ptr(trans), float(res), int(grid_scroll_margin(H, W) if margin is None else margin),
+                  B, H, W, *[_ptr(t) for t in state], *[_ptr(t) for t in scroll], *[_ptr(t) for t in out], _stream())
     return out
 
 

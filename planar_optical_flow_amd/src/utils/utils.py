@@ -592,11 +592,17 @@ class OccupancyGrid:
     ``reset(origin)``: every cell unknown; origin [2] = the world position of the grid's lower corner -- by default the
     next update puts its pose in the middle of the grid.  ``logodds`` is the grid [H,W] int16 on the host,
     ``probability(unit)`` the occupancy probability of a count worth ``unit`` nat.  ``localize(scan, odom, ...)``
-    corrects a pose against the grid as it stands (``ops.grid_match``) without updating it."""
+    corrects a pose against the grid as it stands (``ops.grid_match``) without updating it.
+    ``scroll=dict(margin=...)`` (None: the grid stays where ``reset`` put it): the grid follows the sensor
+    (``ops.grid_scroll``, two more launches in front of ``update`` and ``localize``): within ``margin`` cells of a border
+    (None: a quarter of the shorter side in whole tiles) it is shifted by whole tiles of 64 cells so that the sensor
+    stands on the middle tile again.  The result dicts then hold ``shift`` [2] = this call's shift in tiles (x, y),
+    ``offset`` is the shift since the last reset [2] and ``origin`` moves with it."""
 
-    def __init__(self, scan_phi, res=0.1, size=512, **kw):
+    def __init__(self, scan_phi, res=0.1, size=512, scroll=None, **kw):
         # the settings first: a wrong one raises before anything touches the device
         self._min_dist = kw.pop("min_dist", 0.5)
+        self._scroll_kw = None if scroll is None else dict(_stage_kw(ops.grid_scroll, "scroll", dict(scroll), "res"))
         _stage_kw(ops.grid_map_update, "grid_map", kw, "res")
         H, W = (size, size) if np.ndim(size) == 0 else size
         self.res, self.shape = float(res), (int(H), int(W))
@@ -604,15 +610,32 @@ class OccupancyGrid:
             raise ValueError("res must be > 0")
         if any(s % 64 or not 64 <= s <= 2048 for s in self.shape):
             raise ValueError("size must be a multiple of 64 in [64, 2048]")
+        if self._scroll_kw is not None:
+            ops.grid_scroll_margin(*self.shape, self._scroll_kw.get("margin"))
         self._kw = kw
         self._tab = _table_for(scan_phi)
         self._n = self._tab.numel() // 3
         self._state = ops.grid_map_state(1, *self.shape, self._tab.device)
         self._centre = True
+        if self._scroll_kw is not None:
+            self._scroll = ops.grid_scroll_state(1, *self.shape, self._tab.device)
+            self._scroll_out = ops.grid_scroll_buffers(1, self._tab.device)
 
     def reset(self, origin=None):
-        ops.grid_map_reset(self._state, origin)
+        self._reset(origin)
         self._centre = origin is None
+
+    def _reset(self, origin):
+        ops.grid_map_reset(self._state, origin)
+        if self._scroll_kw is not None:
+            ops.grid_scroll_reset(self._scroll, self._state)
+
+    def _scrolled(self, trans):
+        """With ``scroll``: the grid follows the sensor at trans [1,2] (device) -> {"shift": [2]}; else {}."""
+        if self._scroll_kw is None:
+            return {}
+        out = ops.grid_scroll(trans, self._state, self._scroll, res=self.res, out=self._scroll_out, **self._scroll_kw)
+        return {"shift": _host(out.shift)}
 
     def update(self, scan, odom=None, pred_cls=None, pred_reg=None):
         cur = _to_dev(scan, torch.float32).reshape(1, -1)
@@ -622,12 +645,14 @@ class OccupancyGrid:
             gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
         rot, trans, _ = _pose_terms(None if odom is None else np.asarray(odom, dtype=np.float64)[None])
         if self._centre:                                       # the first pose of a sequence in the middle of the grid
-            ops.grid_map_reset(self._state, trans[0] - 0.5 * self.res * np.array(self.shape[::-1], dtype=np.float64))
+            self._reset(trans[0] - 0.5 * self.res * np.array(self.shape[::-1], dtype=np.float64))
             self._centre = False
-        out = ops.grid_map_update(cur, self._tab, _to_dev(rot, torch.float32), _to_dev(trans, torch.float64),
-                                  self._state, res=self.res, **gate, **self._kw)
-        result = {"point_cell": _host(out.point_cell), "point_mark": _host(out.point_mark).astype(bool),
-                  "point_prior": _host(out.point_prior)}
+        trans = _to_dev(trans, torch.float64)
+        shift = self._scrolled(trans)
+        out = ops.grid_map_update(cur, self._tab, _to_dev(rot, torch.float32), trans, self._state, res=self.res, **gate,
+                                  **self._kw)
+        result = dict(shift, point_cell=_host(out.point_cell), point_mark=_host(out.point_mark).astype(bool),
+                      point_prior=_host(out.point_prior))
         if dc is not None:
             m = int(num[0].item())
             result.update(det_points=_host(out.det_points)[:m], det_free=_host(out.det_free)[:m],
@@ -648,17 +673,23 @@ class OccupancyGrid:
             gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
         pose = np.asarray(odom, dtype=np.float64).reshape(1, 3)
         rot, trans, _ = _pose_terms(pose)
-        pose = _to_dev(pose, torch.float64)
+        pose, trans = _to_dev(pose, torch.float64), _to_dev(trans, torch.float64)
+        shift = self._scrolled(trans)
         shared = {k: self._kw[k] for k in ("cls_thresh", "max_range") if k in self._kw}
-        out = ops.grid_match(cur, self._tab, _to_dev(rot, torch.float32), _to_dev(trans, torch.float64), pose,
-                             self._state, res=self.res, **gate, **shared, **settings)
-        return _host(pose), {"best": _host(out.best), "score": _host(out.score), "votes": int(out.votes[0].item()),
-                             "ok": bool(out.ok[0].item()), "moved": bool(out.moved[0].item()),
-                             "correction": _host(out.correction)}
+        out = ops.grid_match(cur, self._tab, _to_dev(rot, torch.float32), trans, pose, self._state, res=self.res,
+                             **gate, **shared, **settings)
+        return _host(pose), dict(shift, best=_host(out.best), score=_host(out.score), votes=int(out.votes[0].item()),
+                                 ok=bool(out.ok[0].item()), moved=bool(out.moved[0].item()),
+                                 correction=_host(out.correction))
 
     @property
     def origin(self):
         return _host(self._state.origin)
+
+    @property
+    def offset(self):
+        """The shift since the last reset in tiles of 64 cells [2] = (x, y); zeros without ``scroll``."""
+        return _host(self._scroll.offset) if self._scroll_kw is not None else np.zeros(2, np.int32)
 
     @property
     def logodds(self):

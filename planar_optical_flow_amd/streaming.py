@@ -13,7 +13,7 @@ float16 storage (float16 cutout and template).
 
 Behind the trunk (cutout, model, NMS) a scan runs the stages its detector was built with, always in this order and on
 one stream, so a capture stays one linear chain: the keyframe launch; the scan matcher and its pose launch; the
-scan-to-grid match; the flow net; the flow fit and its pose launch; the per-person flow; the person motion; the track
+grid scroll; the scan-to-grid match; the flow net; the flow fit and its pose launch; the per-person flow; the person motion; the track
 update; the grid map; the copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
 capture's warm-up and the captured region are each a loop over it, the warm-up puts back exactly the state the table names, and
 ``reset()`` clears exactly that ("The stage table").  The paragraphs below say what each stage is.
@@ -42,6 +42,9 @@ With ``grid_match`` (and ``method="scan_match"`` plus ``grid_map``) ``ops.grid_m
 matcher's pose launch: the scan is scored against the grid at whole-cell shifts and a few rotations
 around the pose, in integers, and a pose that has lost a scan pair is put back before any later stage reads it and
 before the scan is entered into the map.
+With ``grid_scroll`` (and ``grid_map``) ``ops.grid_scroll`` stands behind the pose launch and in front of every stage
+that reads cells: a sensor that comes near a border of its grid has the grid shifted by whole tiles so
+that it stands on the middle tile again, origin included, on the device -- the map follows a sensor that travels.
 """
 from collections import namedtuple
 
@@ -59,7 +62,7 @@ _MATCHERS = {"scan_match": ops.scan_match, "keyframe": ops.keyframe_match, "keyf
 
 def stage_defaults(arg, cls_thresh=0.5, method="flow"):
     """What the dict given as the constructor argument ``arg`` ("ego_motion" with its ``method``, "tracks",
-    "person_motion", "grid_map", "grid_match") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
+    "person_motion", "grid_map", "grid_match", "grid_scroll") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
     signature has them (``ops.stage_settings``), and -- stated here and nowhere else -- what the detector overrides or
     adds.  ``cls_thresh``: the detector's."""
     if arg == "ego_motion" and method == "flow":
@@ -74,6 +77,10 @@ def stage_defaults(arg, cls_thresh=0.5, method="flow"):
                     **(dict(keys=16) if method == "keyframe_map" else {}))
     if arg == "tracks":
         return dict(ops.stage_settings(ops.track_update), max_tracks=64)
+    if arg == "grid_scroll":
+        kw = ops.stage_settings(ops.grid_scroll)
+        del kw["res"]                                          # the grid's: a key of grid_map's dict
+        return kw
     # person_motion, grid_map and grid_match always take the detector's cls_thresh: it is not a key of their dicts
     kw = ops.stage_settings({"person_motion": ops.person_motion, "grid_map": ops.grid_map_update,
                              "grid_match": ops.grid_match}[arg])
@@ -160,7 +167,15 @@ class StreamingDetector:
     the sensor's grid around the dead-reckoned pose, directly behind the pose launch, and moves the pose and its terms
     when a shifted or turned candidate is clearly better: what a failed scan pair lost is put back before the person
     stages and the grid update read the pose.  ``grid_match()`` returns what was found; ``reset()`` needs nothing new
-    (an empty grid scores 0 and moves nothing)."""
+    (an empty grid scores 0 and moves nothing).
+
+    ``grid_scroll`` (needs ``grid_map``; works with every way that argument gets its pose, ``det(scan, pose=...)``
+    included): None, or a dict of ``margin`` (None: a quarter of the grid's shorter side in whole tiles of 64 cells) of
+    ``ops.grid_scroll``.  Every step, the first of a sequence included, then looks where the sensor stands in its grid,
+    directly behind the pose launch and in front of ``grid_match`` and every other stage that reads cells: within
+    ``margin`` cells of a border the grid and its origin are shifted by whole tiles so that the sensor's tile is the
+    middle one again, and what scrolls in is unknown.  ``grid_scroll()`` returns the shift; ``reset()`` puts the grid
+    back around the start pose and clears the offset."""
 
     # One stage of a scan behind the trunk.  launch(first) enqueues it on the current stream (first: the first scan of a
     # sequence) and writes only fixed buffers; state: the tensors it advances, which a capture's warm-up puts back;
@@ -170,7 +185,7 @@ class StreamingDetector:
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
                  nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None,
-                 grid_map=None, grid_match=None):
+                 grid_map=None, grid_match=None, grid_scroll=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -203,7 +218,7 @@ class StreamingDetector:
         # what a feature was built with, None without it; _filter_kw: the settings of ops.track_update (a detector
         # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
-        self._gm_kw = self._sg_kw = None
+        self._gm_kw = self._sg_kw = self._gs_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
@@ -224,6 +239,8 @@ class StreamingDetector:
                                  "'keyframe', 'keyframe_map' or det(scan, pose=...) it is not built")
             if flow_model is not None:
                 raise ValueError("grid_match with a flow_model is not built: flow_trans is not corrected")
+        if grid_scroll is not None and grid_map is None:
+            raise ValueError("grid_scroll scrolls the grid of grid_map: give both")
         self._cls_thresh = float(cls_thresh)
         if tracks is not None and flow_model is None and person_motion is None:
             raise ValueError("tracks needs flow_model: the tracks are fed by the per-person flow")
@@ -271,6 +288,17 @@ class StreamingDetector:
             stages.append(Stage(self._match_stage, (self._match_out.motion, self._pose_state),
                                 self._match_out.motion.zero_,                    # the first pair starts from rest
                                 from_first=from_first))
+        if grid_scroll is not None:
+            # behind the pose launch (with a pose per call the terms are copied in before any stage) and in front of
+            # every stage that reads cells: the search window of grid_match must not hang over a border.  The grid is
+            # allocated below, so the stage reads self._gm_state when it runs; the grid and its origin are in the grid
+            # stage's snapshot, base and offset in this one's
+            self._gs_kw = stage_settings("grid_scroll", grid_scroll)
+            shape = self._grid_shape(stage_settings("grid_map", grid_map)["size"])
+            ops.grid_scroll_margin(*shape, self._gs_kw["margin"])
+            self._gs_state = ops.grid_scroll_state(self.B, *shape, dev)
+            self._gs_out = ops.grid_scroll_buffers(self.B, dev)
+            stages.append(Stage(self._grid_scroll_stage, (self._gs_state.base, self._gs_state.offset)))
         if grid_match is not None:
             # directly behind the pose launch: every later stage reads the corrected terms.  The grid is allocated
             # below, so the stage reads self._gm_state when it runs; it advances nothing but the pose, which is in
@@ -309,10 +337,7 @@ class StreamingDetector:
                                 lambda: ops.track_reset(self._track_state), from_first=person_motion is not None))
         if grid_map is not None:
             kw = stage_settings("grid_map", grid_map)
-            size = kw.pop("size")
-            shape = tuple(int(s) for s in ((size, size) if np.ndim(size) == 0 else size))
-            if len(shape) != 2 or any(s % 64 or not 64 <= s <= 2048 for s in shape):
-                raise ValueError("grid_map size must be a multiple of 64 in [64, 2048] (or two of them, (H, W))")
+            shape = self._grid_shape(kw.pop("size"))
             if not float(kw["res"]) > 0.0:
                 raise ValueError("grid_map res must be > 0")
             self._gm_kw = dict(kw, cls_thresh=self._cls_thresh)
@@ -324,6 +349,13 @@ class StreamingDetector:
             # not in a warm-up: the captured step behind it reads the scan before this one
             stages.append(Stage(self._keep_scan, warm_up=False))
         self._stages = tuple(stages)
+
+    @staticmethod
+    def _grid_shape(size):
+        shape = tuple(int(s) for s in ((size, size) if np.ndim(size) == 0 else size))
+        if len(shape) != 2 or any(s % 64 or not 64 <= s <= 2048 for s in shape):
+            raise ValueError("grid_map size must be a multiple of 64 in [64, 2048] (or two of them, (H, W))")
+        return shape
 
     def _alloc_pose_terms(self, dev):
         # trans | flow_trans | rot of every sensor in one buffer: one small copy per scan from a pinned staging
@@ -461,11 +493,19 @@ class StreamingDetector:
                        res=self._gm_kw["res"], table=self._sg_table, out=self._sg_out, **self._match_gate(),
                        **self._sg_kw)
 
+    # Behind the pose launch and in front of every stage that reads cells: the grid follows the sensor.
+    def _grid_scroll_stage(self, first):
+        ops.grid_scroll(self._pose_trans, self._gm_state, self._gs_state, res=self._gm_kw["res"], out=self._gs_out,
+                        **self._gs_kw)
+
     def _gm_centre(self, xy):
-        """The origin that puts the world positions xy [B,2] in the middle of their grids."""
+        """The origin that puts the world positions xy [B,2] in the middle of their grids (with grid_scroll: where the
+        scrolling starts from)."""
         H, W = self._gm_state.grid.shape[1:]
         origin = np.asarray(xy, dtype=np.float64) - 0.5 * float(self._gm_kw["res"]) * np.array([W, H], dtype=np.float64)
         self._gm_state.origin.copy_(torch.from_numpy(origin))
+        if self._gs_kw is not None:
+            ops.grid_scroll_reset(self._gs_state, self._gm_state)
 
     def _keep_scan(self, first):
         self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
@@ -609,6 +649,19 @@ class StreamingDetector:
         h = {k: getattr(o, k).cpu().numpy() for k in ("best", "score", "votes", "ok", "moved", "correction")}
         return [{"best": h["best"][b], "score": h["score"][b], "votes": int(h["votes"][b]), "ok": bool(h["ok"][b]),
                  "moved": bool(h["moved"][b]), "correction": h["correction"][b]} for b in range(self.B)], o
+
+    def grid_scroll(self):
+        """-> (list with one dict per sensor of the last step's scroll: shift [2] = this step's shift in tiles of 64
+        cells (x, y), scrolled, offset [2] = the shift since the reset and origin [2], the grid's lower corner now;  the
+        device-resident ``ops.GridScroll``, valid until the next call).  Needs ``grid_scroll`` and one scan.
+        Synchronises."""
+        if self._gs_kw is None or self._seen < 1:
+            raise RuntimeError("construct the detector with grid_scroll and feed it a scan first")
+        o = self._gs_out
+        h = {"shift": o.shift.cpu().numpy(), "scrolled": o.scrolled.cpu().numpy(),
+             "offset": self._gs_state.offset.cpu().numpy(), "origin": self._gm_state.origin.cpu().numpy()}
+        return [{"shift": h["shift"][b], "scrolled": bool(h["scrolled"][b]), "offset": h["offset"][b],
+                 "origin": h["origin"][b]} for b in range(self.B)], o
 
     def ego_motion(self):
         """-> list (one dict per sensor) of the last step's fit: motion [3] = (theta, u_x, u_y) since the previous

@@ -1,5 +1,5 @@
 """Per-kernel timing on the GPU box (events on torch's current stream, which is the
-stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] ..."""
+stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [gridscroll] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -219,7 +219,7 @@ if "person" in which:
             "max_tracks %d: %.3f ms, %.0f live tracks per sensor" % (M, ms_t[M], (tracks[M].track_id > 0).sum().item() / B)
             for M in tracks)))
 
-if "grid" in which or "gridmatch" in which:
+if "grid" in which or "gridmatch" in which or "gridscroll" in which:
     # N12: the occupancy grid map, 450 beams into 512 x 512 cells of 0.1 m per sensor, for 1024, 8 and 1 sensors, next
     # to person_motion on the same scans, NMS results and pose (alternating, three repeats of 50 launches).  The same
     # scan every call, with lo / hi at the int16 limits so that no cell saturates inside the run and every launch
@@ -230,6 +230,12 @@ if "grid" in which or "gridmatch" in which:
     # so that the search reads the same cells every call), defaults: 9 rotations x 81 translations.  The pose starts
     # off by (0.23, -0.17) m and 0.02 rad; a moved pose stays moved, so from the second launch on the search starts
     # where the first one ended (the work of a launch does not depend on it).  Gathers: 9 * 81 * votes int16.
+    # gridscroll: N14 next to grid_map_update on a copy of the same grid, two cases.  `stays`: the sensor in the middle
+    # of its grid as it stands, what every step pays (two launches that leave at once).  `scrolls`: every sensor scrolls
+    # in every call -- the position alternates between tile 7 of 8 and, seen from the grid so scrolled, tile 1, on both
+    # axes, so the calls shift by +3 and -3 tiles and the offset alternates between 3 and 0.  A scroll writes the
+    # grid twice and reads it once and the (5/8)^2 of it that stay: the bound of 4 * H * W * 2 bytes per sensor is
+    # what a one-tile shift comes near.  Both cases form their position with one small add on the stream.
     N, H, W, RES = 450, 512, 512, 0.1
     rng = np.random.default_rng(1701)
     tab = ops.phi_table()
@@ -272,6 +278,31 @@ if "grid" in which or "gridmatch" in which:
                       "of %d" % (B, N, H, W, RES, ms_m, ms_m / B * 1e3, ms_g, sg_out.votes.sum().item() / B,
                                  9 * 81 * sg_out.votes.sum().item() / 1e6, first[1], first[0], B))
             del sg_state
+        if "gridscroll" in which:
+            gs_state = ops.GridMapState(gm_state.grid.clone(), gm_state.origin.clone())
+            gs_scroll = ops.grid_scroll_reset(ops.grid_scroll_state(B, H, W, dev), gs_state)
+            gs_out = ops.grid_scroll_buffers(B, dev)
+            # positions relative to the origin as it then stands: the middle; tile 7 (-> +3); tile 1 (-> -3)
+            at = lambda cx, cy: torch.tensor([(cx + 0.5) * RES, (cy + 0.5) * RES], dtype=torch.float64, device=dev)
+            middle, up, down = at(W // 2, H // 2), at(W - 64, H - 64), at(64, 64)
+            stays = lambda: ops.grid_scroll(gs_state.origin + middle, gs_state, gs_scroll, res=RES, out=gs_out)
+            flip = [0]
+
+            def scrolls():
+                flip[0] ^= 1
+                ops.grid_scroll(gs_state.origin + (up if flip[0] else down), gs_state, gs_scroll, res=RES, out=gs_out)
+
+            scrolls()
+            assert bool(gs_out.scrolled.all())
+            scrolls()
+            for rep in range(3):
+                ms_g, ms_0, ms_1 = timeit(grid, iters=50), timeit(stays, iters=50), timeit(scrolls, iters=50)
+                assert bool(gs_out.scrolled.all()) and int(gs_scroll.offset.abs().max()) <= 3
+                moved = B * 4 * H * W * 2
+                print("gridscroll B=%d %dx%d at %.2f m: no sensor scrolls %.3f ms, every sensor scrolls %.3f ms (%.2f us per "
+                      "sensor, %.0f GB/s against the bound of 4*H*W*2 bytes per sensor) next to "
+                      "grid_map_update %.3f ms" % (B, H, W, RES, ms_0, ms_1, ms_1 / B * 1e3, moved / ms_1 / 1e6, ms_g))
+            del gs_state, gs_scroll
         for rep in range(3 if "grid" in which else 0):
             ms_g, ms_pm = timeit(grid, iters=50), timeit(motion, iters=50)
             bound = B * 2 * H * W * 2

@@ -1,5 +1,5 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-scroll]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
@@ -21,6 +21,8 @@ grid_map=dict() (512 x 512 cells of 0.1 m per sensor) as its last stage, alterna
 --grid-match (with --grid): two more steps in the same process, ego_motion=dict(method="scan_match") with grid_map=dict()
 and that one with grid_match=dict() behind the scan matcher, so one process gives the map step without and with the
 scan-to-grid match.
+--grid-scroll (with --grid): one more step in the same process, the keyframe step with grid_map=dict() and
+grid_scroll=dict() behind the keyframe launch, so one process gives the map step without and with the scrolling grid.
 --eager (with --ego, --tracks or --grid): those steps launched eagerly (graph=False) instead of replayed -- the host
 time of the stage wrappers, which a replay does not run."""
 import faulthandler, os, sys, time
@@ -45,6 +47,7 @@ KEYED = ("keyframe", "keyframe_map")
 TRACKS = "--tracks" in sys.argv
 GRID = "--grid" in sys.argv
 GRID_MATCH = "--grid-match" in sys.argv
+GRID_SCROLL = "--grid-scroll" in sys.argv
 EAGER = "--eager" in sys.argv
 sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--person-motion", "--grid", "--eager"))]
 
@@ -72,6 +75,9 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
         if GRID:
             keyed_only, gridded = mk(ego_motion=KEYFRAME), mk(ego_motion=KEYFRAME, grid_map=dict())
             steps = {"keyframe": lambda t: keyed_only(scans[:, t]), "keyframe + grid_map": lambda t: gridded(scans[:, t])}
+            if GRID_SCROLL:
+                scrolling = mk(ego_motion=KEYFRAME, grid_map=dict(), grid_scroll=dict())
+                steps["keyframe + grid_map + grid_scroll"] = lambda t: scrolling(scans[:, t])
             if GRID_MATCH:
                 reckoned, corrected = mk(ego_motion=MATCH, grid_map=dict()), mk(ego_motion=MATCH, grid_map=dict(), grid_match=dict())
                 steps["scan_match + grid_map"] = lambda t: reckoned(scans[:, t])
@@ -145,6 +151,10 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             print("   grid_map after 40 scans: occupied cells %s, free cells %s, marked points of the last scan %s"
                   % ((state.grid > 0).sum(dim=(1, 2)).tolist(), (state.grid < 0).sum(dim=(1, 2)).tolist(),
                      out.point_mark.sum(dim=1).tolist()))
+        if GRID and GRID_SCROLL:
+            moved_by, _ = scrolling.grid_scroll()
+            print("   grid_scroll at the last scan: shift %s, offset %s" % ([m["shift"].tolist() for m in moved_by],
+                                                                             [m["offset"].tolist() for m in moved_by]))
         if GRID and GRID_MATCH:
             found, _ = corrected.grid_match()
             print("   grid_match at the last scan: votes %s, score per voting point %s, ok %s, moved %s"
