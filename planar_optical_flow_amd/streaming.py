@@ -46,6 +46,7 @@ With ``grid_scroll`` (and ``grid_map``) ``ops.grid_scroll`` stands behind the po
 that reads cells: a sensor that comes near a border of its grid has the grid shifted by whole tiles so
 that it stands on the middle tile again, origin included, on the device -- the map follows a sensor that travels.
 """
+import gc
 from collections import namedtuple
 
 import numpy as np
@@ -555,11 +556,22 @@ class StreamingDetector:
                 t.copy_(was)
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            cls, reg, tmpl, fused = self._step(False)
-            self.template.copy_(tmpl)                 # feed the fused template back in place
-            for stage in self._stages:
-                stage.launch(False)
+        # A detector that was dropped is held by cycles (its stages are bound methods) until Python's collector runs,
+        # and with it its captured graph and the graph's memory pool.  A collection that starts inside the capture
+        # would destroy them there, which a capture in progress does not survive: collect now and keep the collector
+        # off until the capture has ended.
+        gc.collect()
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g):
+                cls, reg, tmpl, fused = self._step(False)
+                self.template.copy_(tmpl)             # feed the fused template back in place
+                for stage in self._stages:
+                    stage.launch(False)
+        finally:
+            if collecting:
+                gc.enable()
         self._graph, self._out, self._graph_dets = g, (cls, reg, fused), self._dets
 
     def __call__(self, scan, pose=None):

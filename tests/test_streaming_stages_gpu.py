@@ -2,7 +2,13 @@
 public surface only: after every scan the eager and the replayed detector hold the same bits in every output and in
 every accessor that is available, each accessor raises exactly until its scans-seen requirement is met (and always when
 its feature is off), and after ``reset()`` the same sequence gives the same bits again -- ids from 1, pose from zero.
-The refused combinations raise ``ValueError``."""
+The refused combinations raise ``ValueError``.
+
+GRID_CASES are 20 more rows run by the same test body, with the grid stages on (a 128 x 192 grid): ``grid_map`` alone
+and with ``grid_scroll`` under the four pose sources that it accepts, ``grid_map`` + ``grid_match`` with and without
+``grid_scroll`` under ``scan_match`` (the one source it accepts), each with the ``motion`` tail and tracks and once
+without a tail.  After ``reset()`` the grid is empty and its origin and the scroll's offset are back where the
+constructor put them."""
 import numpy as np
 import pytest
 import torch
@@ -19,6 +25,24 @@ DEAD_RECKONS = ("flow", "scan_match") + KEYED
 CASES = [(src, None, False, nms) for src in ("none", "scan_match") + KEYED for nms in (False, True)] \
     + [(src, "flow", tr, True) for src in ("given", "flow", "scan_match") + KEYED for tr in (False, True)] \
     + [(src, "motion", tr, True) for src in ("given", "scan_match") + KEYED for tr in (False, True)]
+
+
+# (pose source, tail, tracks, nms, grid stages): the grid stages with every pose source the constructor accepts for them
+GRID_STAGES = ("grid_map", "grid_scroll", "grid_match")
+GRID_CASES = [(src, tail, tail is not None, True, grid)
+              for sources, grids in ((("given", "scan_match") + KEYED, (("grid_map",), ("grid_map", "grid_scroll"))),
+                                     (("scan_match",), (("grid_map", "grid_match"), ("grid_map", "grid_scroll", "grid_match"))))
+              for grid in grids for src in sources for tail in ("motion", None)]
+GRID_SIZE = (128, 192)
+
+
+def _grid_of(case):
+    return case[4] if len(case) > 4 else ()
+
+
+def _case_id(c):
+    base = "%s-%s-%s-%s" % (c[0], c[1] or "notail", "tracks" if c[2] else "notracks", "nms" if c[3] else "nonms")
+    return base + "".join("-" + g for g in _grid_of(c))
 
 
 class DiffFlow(torch.nn.Module):
@@ -57,7 +81,7 @@ def gate_score(model, sequence):
 
 
 def _settings(case, gate_score):
-    src, tail, tracks, nms = case
+    src, tail, tracks, nms = case[:4]
     kw = dict(batch=B, num_pts=N, cls_thresh=0.0, nms_min_dist=0.5 if nms else None)
     if src in DEAD_RECKONS:
         kw["ego_motion"] = dict(cls_thresh=gate_score) if src == "flow" else dict(method=src, cls_thresh=gate_score)
@@ -67,16 +91,22 @@ def _settings(case, gate_score):
         kw["person_motion"] = dict()
     if tracks:
         kw["tracks"] = dict()
+    for stage in _grid_of(case):
+        kw[stage] = dict(size=GRID_SIZE) if stage == "grid_map" else dict()
+    if _grid_of(case):
+        kw["cls_thresh"] = gate_score                          # at 0.0 every point is a person's: none would enter the map
     return kw
 
 
 def _available(case, seen):
     """Which accessors answer after `seen` scans of a sequence."""
-    src, tail, tracks, _ = case
-    return {"person_flow": tail == "flow" and seen >= 2,
-            "person_motion": tail == "motion" and seen >= 1,
-            "ego_motion": src in DEAD_RECKONS and seen >= (1 if src in KEYED else 2),
-            "tracks": tracks and seen >= 2}
+    src, tail, tracks, _ = case[:4]
+    there = {"person_flow": tail == "flow" and seen >= 2,
+             "person_motion": tail == "motion" and seen >= 1,
+             "ego_motion": src in DEAD_RECKONS and seen >= (1 if src in KEYED else 2),
+             "tracks": tracks and seen >= 2}
+    there.update({stage: stage in _grid_of(case) and seen >= 1 for stage in GRID_STAGES})
+    return there
 
 
 def _leaves(obj, path=""):
@@ -106,14 +136,22 @@ def _same(a, b, where):
         assert same_bits(x, y), (where, p)
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "%s-%s-%s-%s" % (c[0], c[1] or "notail", "tracks" if c[2] else "notracks",
-                                                                      "nms" if c[3] else "nonms"))
+def _grid_state(det, case):
+    """Where the grid stands between two sequences: (grid, origin) and with grid_scroll (base, offset), on the host."""
+    state = [t.cpu().numpy().copy() for t in det._gm_state]
+    if "grid_scroll" in _grid_of(case):
+        state += [det._gs_state.base.cpu().numpy().copy(), det._gs_state.offset.cpu().numpy().copy()]
+    return state
+
+
+@pytest.mark.parametrize("case", CASES + GRID_CASES, ids=_case_id)
 def test_eager_graph_availability_and_reset(case, model, sequence, gate_score):
     from planar_optical_flow_amd.streaming import StreamingDetector
-    src, tail, tracks, nms = case
+    src, tail, tracks, nms = case[:4]
     scans, poses = sequence
     eager = StreamingDetector(model, graph=False, **_settings(case, gate_score))
     graphed = StreamingDetector(model, graph=True, **_settings(case, gate_score))
+    built = [_grid_state(det, case) for det in (eager, graphed)] if _grid_of(case) else None
 
     def one_pass():
         snaps, pairs, live, ok, first_ids = [], 0, 0, 0, None
@@ -145,6 +183,15 @@ def test_eager_graph_availability_and_reset(case, model, sequence, gate_score):
     first = one_pass()
     for det in (eager, graphed):
         det.reset()
+    if _grid_of(case):
+        # the grid is zeroed, its origin and the scroll's base and offset are back where the constructor put them
+        for det, was in zip((eager, graphed), built):
+            now = _grid_state(det, case)
+            assert not now[0].any() and all(same_bits(a, b) for a, b in zip(now, was))
+            if "grid_scroll" in _grid_of(case):
+                assert not now[3].any()
+        known = [leaf for path, _, leaf in first[0][-1] if path.startswith(".grid_map[0][0]")]
+        assert len(known) == 1 and known[0].shape == (B,) + GRID_SIZE and (known[0] > 0).any() and (known[0] < 0).any()
     again = one_pass()
     for t, (a, b) in enumerate(zip(first[0], again[0])):
         _same(a, b, (t, "first pass against the pass after reset()"))
@@ -157,6 +204,28 @@ def test_eager_graph_availability_and_reset(case, model, sequence, gate_score):
         assert live > 0 and min(first_ids) == 1
     if src in DEAD_RECKONS:
         assert ok > 0
+
+
+def test_the_collector_stays_out_of_the_capture(model, sequence):
+    """A collection inside the capture could free a dropped detector with its captured graph: ``_capture`` collects first
+    and holds the collector off until the capture has ended.  Nothing is provoked here: a stage only notes, each time it
+    is launched, whether the stream is capturing and whether the collector is enabled."""
+    import gc
+    from planar_optical_flow_amd.streaming import StreamingDetector
+    scans, poses = sequence
+    det = StreamingDetector(model, batch=B, num_pts=N, nms_min_dist=0.5, person_motion=dict())
+    noted, launch = [], det._stages[0].launch
+
+    def noting(first):
+        noted.append((torch.cuda.is_current_stream_capturing(), gc.isenabled()))
+        launch(first)
+
+    det._stages = (det._stages[0]._replace(launch=noting),) + det._stages[1:]
+    assert gc.isenabled()
+    for t in range(3):
+        det(scans[:, t], pose=poses[t])
+    assert det._graph is not None and gc.isenabled()
+    assert (True, False) in noted and (True, True) not in noted and (False, False) not in noted, noted
 
 
 def test_refused_combinations(model, sequence):
@@ -180,3 +249,18 @@ def test_refused_combinations(model, sequence):
     for kw in (dict(), dict(nms_min_dist=0.5, flow_model=DiffFlow()), dict(nms_min_dist=0.5, person_motion=dict())):
         with pytest.raises(ValueError):
             mk(**kw).reset(pose=poses[0])
+    # the grid stages
+    grid, match = dict(size=GRID_SIZE), dict(method="scan_match")
+    for kw in (dict(grid_match=dict(), grid_map=grid, ego_motion=dict(method="keyframe"), nms_min_dist=0.5),
+               dict(grid_match=dict(), grid_map=grid, ego_motion=dict(method="keyframe_map"), nms_min_dist=0.5),
+               dict(grid_match=dict(), grid_map=grid, nms_min_dist=0.5),           # a pose per call is not corrected
+               dict(grid_match=dict(), grid_map=grid, ego_motion=match, nms_min_dist=0.5, flow_model=DiffFlow()),
+               dict(grid_match=dict(), grid_map=grid, ego_motion=dict(), nms_min_dist=0.5, flow_model=DiffFlow()),
+               dict(grid_match=dict(), ego_motion=match),                          # no grid to match against
+               dict(grid_scroll=dict(), ego_motion=match),                         # no grid to scroll
+               dict(grid_scroll=dict(), nms_min_dist=0.5, person_motion=dict()),
+               dict(grid_map=grid, ego_motion=dict(), nms_min_dist=0.5, flow_model=DiffFlow())):      # method "flow"
+        with pytest.raises(ValueError):
+            mk(**kw)
+    with pytest.raises(ValueError):                            # a dead-reckoning detector with a grid takes no pose
+        mk(grid_map=grid, grid_scroll=dict(), ego_motion=match)(scans[:, 0], pose=poses[0])
