@@ -713,6 +713,57 @@ int pof_grid_scroll(const double *trans, double res, int margin, int B, int H, i
                     pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N15 map-checked tracks: per-track evidence from the occupancy grid.  The detection row of the NMS is a rank that
+ * changes with every scan and only a track (N7) carries identity over time; this stage joins what the grid (N12) says
+ * about the row a track was matched with to the track's slot, sums it there, and derives a class per track: a walker's
+ * points land on cells seen free and the track travels, an intermittent false positive on a static object lands on
+ * cells the map already holds as occupied.  The reference has nothing of the kind; the specification is this comment
+ * (restated in NumPy by tests/test_track_map.py).  One sensor per batch entry, one launch, M = max_tracks.
+ * Inputs, read only, as this step's NMS, pof_grid_map_update and pof_track_update left them: instance_mask [B][N],
+ *   num_det [B] (clamped to [0, N]), point_cell [B][N] int32, point_prior [B][N] int16, det_points [B][N],
+ *   det_free [B][N] int32, track_id [B][M] int32 (0 = free), track_state [B][M][4] float64 = (x, y, vx, vy),
+ *   track_det [B][M] int32.
+ * State, in place, every field persistent, all zeros after a reset: ev_id [B][M] int32 = the track id the evidence
+ *   belongs to; ev_points, ev_free, ev_occ, ev_scans [B][M] int32; ev_start [B][M][2] float64 = where the track stood
+ *   when its evidence started; ev_moved [B][M] uint8.
+ * One step:
+ *   0. per detection row k < num_det:  det_occ[k] = the number of beams i with instance_mask[i] = k + 1,
+ *      point_cell[i] >= 0 and point_prior[i] >= occ_thresh (the -32768 of a beam without a cell counts nowhere);
+ *      rows >= num_det are 0
+ *   1. per slot s, id = track_id[s]:  id = 0: every state field of the slot becomes 0.  Else id != ev_id[s] (the slot
+ *      was reused): the fields become 0, ev_id = id and ev_start = (x, y) of track_state[s]
+ *   2. per live slot, k = track_det[s]:  if 0 <= k < num_det and n = det_points[k] > 0:  ev_points += n,
+ *      ev_free += det_free[k], ev_occ += det_occ[k], ev_scans += 1 (saturating at 2^30); then, if ev_points > cap, the
+ *      three sums are each shifted right by one, once: with cap >= N they stay bounded by cap, old evidence fades and
+ *      the ratios survive
+ *   3. per live slot, float64, plain multiplies and adds (no FMA):  dx = x - ev_start_x, dy = y - ev_start_y,
+ *      d2 = dx dx + dy dy;  d2 >= travel travel sets ev_moved = 1, which stays set; a NaN compares false
+ *   4. the class of a slot, a pure function of its state, the products in int64:
+ *        0 undecided      not live, or ev_scans < min_scans, or ev_points < min_points
+ *        3 background     else 100 ev_occ >= occ_pct ev_points  (tested first: a false positive that slides along a
+ *                         wall as the sensor moves does travel)
+ *        1 free-standing  else ev_moved, or 100 ev_free >= free_pct ev_points
+ *        2 unsupported    everything else
+ * Outputs, overwritten every step: det_occ [B][N] int32; track_class [B][M] uint8; det_class [B][N] uint8 = the class of
+ *   the live slot whose track_det is that row (inside [0, num_det)), else 0 -- should two slots name one row, the
+ *   lower slot stands; point_class [B][N] uint8 = det_class[instance_mask - 1] for ids in [1, num_det], else 0;
+ *   class_count [B][4] int32 = the live slots per class.
+ * Integer sums in LDS, no global and no floating-point atomics: the same bits in every run, at every batch position
+ * and in a graph replay.  A grid that scrolls (N14) changes nothing here: the state holds world coordinates and
+ * counts, no cells.
+ * POF_E_BADARG (checked first; nothing written): a NULL pointer, B < 0, N < 1, max_tracks < 1, occ_thresh < 0, free_pct
+ *   or occ_pct outside [0, 100], min_points or min_scans < 0, cap < N or > 2^20, travel not >= 0.  POF_E_SHAPE (nothing
+ *   written): N > 4096, max_tracks > 256.  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_track_map(const int32_t *instance_mask, const int32_t *num_det, const int32_t *point_cell,
+                  const int16_t *point_prior, const int32_t *det_points, const int32_t *det_free,
+                  const int32_t *track_id, const double *track_state, const int32_t *track_det, int B, int N,
+                  int max_tracks, int32_t *ev_id, int32_t *ev_points, int32_t *ev_free, int32_t *ev_occ,
+                  int32_t *ev_scans, double *ev_start, uint8_t *ev_moved, int32_t *det_occ, uint8_t *track_class,
+                  uint8_t *det_class, uint8_t *point_class, int32_t *class_count, int occ_thresh, int free_pct,
+                  int occ_pct, int min_points, int min_scans, double travel, int cap, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

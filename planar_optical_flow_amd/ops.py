@@ -920,7 +920,7 @@ def nms_predicted_center(ranges, tab, pred_cls, pred_reg, min_dist=0.5):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The per-scan stages N5-N14.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
+# The per-scan stages N5-N15.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
 # a dtype and a symbolic shape per field.  ``_zeros_of`` allocates a record, ``_checked`` takes a caller's and
 # ``_out_of`` does whichever an ``out=`` needs; ``stage_settings`` reads a wrapper's tunable scalars off its signature.
 def _record(name, persistent=None, **fields):
@@ -1723,6 +1723,79 @@ def grid_scroll(trans, state, scroll, *, res, margin=None, out=None):
     with torch.cuda.device(dev):
         _lib.call("pof_grid_scroll", _ptr(trans), float(res), int(grid_scroll_margin(H, W) if margin is None else margin),
                   B, H, W, *[_ptr(t) for t in state], *[_ptr(t) for t in scroll], *[_ptr(t) for t in out], _stream())
+    return out
+
+
+# the evidence of a track slot carries over from scan to scan; the classes describe one step
+TrackMapState = _record("TrackMapState",
+                        persistent=dict(ev_id=(_I32, "B", "M"), ev_points=(_I32, "B", "M"), ev_free=(_I32, "B", "M"),
+                                        ev_occ=(_I32, "B", "M"), ev_scans=(_I32, "B", "M"), ev_start=(_F64, "B", "M", 2),
+                                        ev_moved=(_U8, "B", "M")))
+TrackMap = _record("TrackMap", det_occ=(_I32, "B", "N"), track_class=(_U8, "B", "M"), det_class=(_U8, "B", "N"),
+                   point_class=(_U8, "B", "N"), class_count=(_I32, "B", 4))
+TRACK_CLASSES = ("undecided", "free-standing", "unsupported", "background")     # the values of a class, 0..3
+
+
+def track_map_state(B, max_tracks, device="cuda"):
+    """The persistent state of ``track_map`` for B sensors of ``max_tracks`` slots: no evidence (allocate once, before
+    a graph capture).  -> ``TrackMapState``."""
+    return _zeros_of(TrackMapState, device, B=B, M=int(max_tracks))
+
+
+def track_map_buffers(B, max_tracks, N, device="cuda"):
+    """The five outputs of ``track_map`` for B sensors, ``max_tracks`` slots and N points, zero-filled, as its ``out=``
+    (allocate once, before a graph capture)."""
+    return _zeros_of(TrackMap, device, B=B, M=int(max_tracks), N=N)
+
+
+def track_map_reset(state):
+    """Forget the evidence of every slot, in place, with tensor ops on the current stream (no host sync)."""
+    state = TrackMapState(*state)
+    for t in state:
+        t.zero_()
+    return state
+
+
+def track_map(tracks, grid_out, instance_mask, num_det, state, *, occ_thresh=17, free_pct=50, occ_pct=50,
+              min_points=20, min_scans=3, travel=0.5, cap=4096, out=None):
+    """N15: what the occupancy grid says about every track, one launch per batch (include/pof_abi.h states the rules
+    in full).
+
+    ``tracks``: the ``TrackState`` of this step's ``track_update``; ``grid_out``: the ``GridMapOut`` of this step's
+    ``grid_map_update`` (with the NMS results); instance_mask [B,N] i32 and num_det [B] i32 as the NMS returns them; all
+    read only.  ``state``: a ``TrackMapState`` (``track_map_state``), UPDATED IN PLACE: per track slot the points of
+    the detections the track was matched with, how many of them lay on cells seen free (``det_free``) and on cells that
+    held >= ``occ_thresh`` before the scan, the scans that added some, where the track stood when its evidence started
+    and whether it has been ``travel`` metres from there since.  Beyond ``cap`` points (N <= cap <= 2^20) the three
+    sums are halved.  A slot that is freed or reused starts again.  From ``min_scans`` scans and ``min_points`` points a
+    track has a class: 3 background (at least ``occ_pct`` per cent of its points on occupied cells), else 1
+    free-standing (it moved, or at least ``free_pct`` per cent on free cells), else 2 unsupported; 0 is undecided.
+    -> ``TrackMap``: det_occ [B,N] i32, track_class [B,M] u8, det_class [B,N] u8 (the class of the track matched with
+    each detection row), point_class [B,N] u8 (of the track every scan point belongs to), class_count [B,4] i32 (live
+    tracks per class).  max_tracks <= 256, N <= 4096.  The same bits in every run.  ``out``: a ``TrackMap`` of
+    preallocated tensors (``track_map_buffers``)."""
+    tracks, grid_out = TrackState(*tracks), GridMapOut(*grid_out)
+    if not isinstance(tracks.track_id, torch.Tensor) or tracks.track_id.dim() != 2 or \
+            not isinstance(grid_out.point_cell, torch.Tensor) or grid_out.point_cell.dim() != 2:
+        raise TypeError("tracks.track_id must be a [B,max_tracks] and grid_out.point_cell a [B,N] tensor on the HIP "
+                        "device (no CPU path)")
+    (B, M), N, dev = tracks.track_id.shape, grid_out.point_cell.shape[1], tracks.track_id.device
+    tracks = _checked(TrackState, tracks, "tracks", B=B, M=M, N=N)
+    grid_out = _checked(GridMapOut, grid_out, "grid_out", B=B, N=N)
+    instance_mask = _dev(instance_mask, torch.int32, "instance_mask")
+    num_det = _dev(num_det, torch.int32, "num_det")
+    if tuple(instance_mask.shape) != (B, N) or tuple(num_det.shape) != (B,):
+        raise ValueError("instance_mask must be [B,N] and num_det [B]")
+    state = _checked(TrackMapState, state, "state", B=B, M=M)
+    out = _out_of(TrackMap, out, dev, B=B, M=M, N=N)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_track_map", _ptr(instance_mask), _ptr(num_det), _ptr(grid_out.point_cell),
+                  _ptr(grid_out.point_prior), _ptr(grid_out.det_points), _ptr(grid_out.det_free), _ptr(tracks.track_id),
+                  _ptr(tracks.track_state), _ptr(tracks.track_det), B, N, M, *[_ptr(t) for t in state],
+                  *[_ptr(t) for t in out], int(occ_thresh), int(free_pct), int(occ_pct), int(min_points),
+                  int(min_scans), float(travel), int(cap), _stream())
     return out
 
 

@@ -434,10 +434,10 @@ class PersonTracker:
 
     def __init__(self, max_tracks=64, **settings):
         self.max_tracks, self.settings = int(max_tracks), _stage_kw(ops.track_update, "tracks", settings)
-        self._persistent = None
+        self._persistent = self._last = None
 
     def reset(self):
-        self._persistent = None
+        self._persistent = self._last = None
 
     def update(self, result):
         xy = np.asarray(result["dets_xy_world"], dtype=np.float64).reshape(-1, 2)
@@ -455,6 +455,7 @@ class PersonTracker:
                          torch.zeros((1, n), dtype=torch.int32, device=dev) if inst is None else
                          _to_dev(inst, torch.int32).reshape(1, n), state, **self.settings)
         self._persistent = {k: getattr(state, k) for k in ops.TrackState.persistent}
+        self._last = state                                     # on the device, for ``TrackMap.update``
         h = {k: getattr(state, k)[0].cpu().numpy() for k in state._fields}
         live = np.flatnonzero(h["track_id"])
         tracks = {"id": h["track_id"][live], "xy": h["track_state"][live, :2], "velocity": h["track_state"][live, 2:],
@@ -617,6 +618,7 @@ class OccupancyGrid:
         self._n = self._tab.numel() // 3
         self._state = ops.grid_map_state(1, *self.shape, self._tab.device)
         self._centre = True
+        self._last = None                                      # (outputs, instance_mask, num_det) of the last update
         if self._scroll_kw is not None:
             self._scroll = ops.grid_scroll_state(1, *self.shape, self._tab.device)
             self._scroll_out = ops.grid_scroll_buffers(1, self._tab.device)
@@ -653,6 +655,7 @@ class OccupancyGrid:
                                   **self._kw)
         result = dict(shift, point_cell=_host(out.point_cell), point_mark=_host(out.point_mark).astype(bool),
                       point_prior=_host(out.point_prior))
+        self._last = None if dc is None else (out, inst, num)  # on the device, for ``TrackMap.update``
         if dc is not None:
             m = int(num[0].item())
             result.update(det_points=_host(out.det_points)[:m], det_free=_host(out.det_free)[:m],
@@ -697,6 +700,46 @@ class OccupancyGrid:
 
     def probability(self, unit=0.05):
         return 1.0 / (1.0 + np.exp(-float(unit) * self.logodds.astype(np.float64)))
+
+
+class TrackMap:
+    """What the occupancy grid says about every track, scan after scan (``ops.track_map``, one launch per scan; the
+    reference has nothing of the kind).  ``tm = TrackMap(max_tracks=64, occ_thresh=17, ...)`` with the settings of
+    ``ops.track_map``; ``res = tm.update(tracker, grid)`` per scan, ``tm.reset()`` between sequences.
+
+    ``update(tracker, grid)``: a ``PersonTracker`` (of the same ``max_tracks``) and an ``OccupancyGrid`` after their own
+    ``update`` of this scan -- the tracker's with a result that holds the scan's instance_mask (``PersonMotion.update``
+    and ``person_flow`` give one), the grid's with the same predictions, so that both speak of the same detection rows.
+    NumPy out.  -> dict: the live tracks in slot order as arrays id, cls (0 undecided, 1 free-standing, 2 unsupported,
+    3 background), points, free, occ (the three sums), scans, moved (bool), start [T,2]; det_class [M] per detection,
+    point_class [N] per scan point and class_count [4]."""
+
+    def __init__(self, max_tracks=64, **settings):
+        self.max_tracks, self.settings = int(max_tracks), _stage_kw(ops.track_map, "track_map", settings)
+        self._state = None
+
+    def reset(self):
+        self._state = None
+
+    def update(self, tracker, grid):
+        tracks, seen = getattr(tracker, "_last", None), getattr(grid, "_last", None)
+        if tracks is None or seen is None:
+            raise ValueError("update the tracker and the grid (with predictions) for this scan first")
+        out, inst, num = seen
+        if tracks.track_id.shape[1] != self.max_tracks or tracks.det_track.shape[1] != inst.shape[1]:
+            raise ValueError("the tracker must have max_tracks = %d and be updated with the scan's instance_mask"
+                             % self.max_tracks)
+        if self._state is None:
+            self._state = ops.track_map_state(1, self.max_tracks, inst.device)
+        res = ops.track_map(tracks, out, inst, num, self._state, **self.settings)
+        ids, m = _host(tracks.track_id), int(num[0].item())
+        live = np.flatnonzero(ids)
+        h = {k: _host(t) for k, t in zip(self._state._fields, self._state)}
+        return {"id": ids[live], "cls": _host(res.track_class)[live], "points": h["ev_points"][live],
+                "free": h["ev_free"][live], "occ": h["ev_occ"][live], "scans": h["ev_scans"][live],
+                "moved": h["ev_moved"][live].astype(bool), "start": h["ev_start"][live],
+                "det_class": _host(res.det_class)[:m], "point_class": _host(res.point_class),
+                "class_count": _host(res.class_count)}
 
 
 def _pose_terms(odom1, odom0=None, batch=1):

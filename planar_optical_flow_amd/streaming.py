@@ -14,7 +14,7 @@ float16 storage (float16 cutout and template).
 Behind the trunk (cutout, model, NMS) a scan runs the stages its detector was built with, always in this order and on
 one stream, so a capture stays one linear chain: the keyframe launch; the scan matcher and its pose launch; the
 grid scroll; the scan-to-grid match; the flow net; the flow fit and its pose launch; the per-person flow; the person motion; the track
-update; the grid map; the copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
+update; the grid map; the map check of the tracks; the copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
 capture's warm-up and the captured region are each a loop over it, the warm-up puts back exactly the state the table names, and
 ``reset()`` clears exactly that ("The stage table").  The paragraphs below say what each stage is.
 With a ``flow_model`` the step ends in the per-person flow (``ops.person_flow``): a flow net on the previous
@@ -45,6 +45,9 @@ before the scan is entered into the map.
 With ``grid_scroll`` (and ``grid_map``) ``ops.grid_scroll`` stands behind the pose launch and in front of every stage
 that reads cells: a sensor that comes near a border of its grid has the grid shifted by whole tiles so
 that it stands on the middle tile again, origin included, on the device -- the map follows a sensor that travels.
+With ``track_map`` (and ``tracks`` plus ``grid_map``) ``ops.track_map`` stands behind the grid map: what
+the grid says about the detection a track was matched with is summed per track slot on the device, and every track has
+a class -- free-standing, unsupported, background -- that an intermittent false positive on a static object cannot shed.
 """
 import gc
 from collections import namedtuple
@@ -63,7 +66,7 @@ _MATCHERS = {"scan_match": ops.scan_match, "keyframe": ops.keyframe_match, "keyf
 
 def stage_defaults(arg, cls_thresh=0.5, method="flow"):
     """What the dict given as the constructor argument ``arg`` ("ego_motion" with its ``method``, "tracks",
-    "person_motion", "grid_map", "grid_match", "grid_scroll") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
+    "person_motion", "grid_map", "grid_match", "grid_scroll", "track_map") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
     signature has them (``ops.stage_settings``), and -- stated here and nowhere else -- what the detector overrides or
     adds.  ``cls_thresh``: the detector's."""
     if arg == "ego_motion" and method == "flow":
@@ -78,6 +81,8 @@ def stage_defaults(arg, cls_thresh=0.5, method="flow"):
                     **(dict(keys=16) if method == "keyframe_map" else {}))
     if arg == "tracks":
         return dict(ops.stage_settings(ops.track_update), max_tracks=64)
+    if arg == "track_map":
+        return ops.stage_settings(ops.track_map)
     if arg == "grid_scroll":
         kw = ops.stage_settings(ops.grid_scroll)
         del kw["res"]                                          # the grid's: a key of grid_map's dict
@@ -176,7 +181,16 @@ class StreamingDetector:
     directly behind the pose launch and in front of ``grid_match`` and every other stage that reads cells: within
     ``margin`` cells of a border the grid and its origin are shifted by whole tiles so that the sensor's tile is the
     middle one again, and what scrolls in is unknown.  ``grid_scroll()`` returns the shift; ``reset()`` puts the grid
-    back around the start pose and clears the offset."""
+    back around the start pose and clears the offset.
+
+    ``track_map`` (needs ``tracks`` and ``grid_map``; works with ``person_motion`` and every ``method`` that argument
+    accepts, and with ``flow_model`` plus ``det(scan, pose=...)``): None, or a dict of ``occ_thresh`` (17), ``free_pct``
+    (50), ``occ_pct`` (50), ``min_points`` (20), ``min_scans`` (3), ``travel`` (0.5 m) and ``cap`` (4096) of
+    ``ops.track_map``.  Every step on which the track update runs then ends, behind the grid map, in one launch that adds
+    what the grid said about each track's detection -- its points, those on cells seen free, those on cells already
+    occupied -- to the track's slot and classes the track: 3 background, 1 free-standing, 2 unsupported, 0 undecided.
+    ``track_map()`` returns the classes and the evidence; ``reset()`` forgets the evidence.  A scroll of the grid needs
+    nothing here: the evidence is world coordinates and counts, not cells."""
 
     # One stage of a scan behind the trunk.  launch(first) enqueues it on the current stream (first: the first scan of a
     # sequence) and writes only fixed buffers; state: the tensors it advances, which a capture's warm-up puts back;
@@ -186,7 +200,7 @@ class StreamingDetector:
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
                  nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None,
-                 grid_map=None, grid_match=None, grid_scroll=None):
+                 grid_map=None, grid_match=None, grid_scroll=None, track_map=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -219,7 +233,7 @@ class StreamingDetector:
         # what a feature was built with, None without it; _filter_kw: the settings of ops.track_update (a detector
         # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
-        self._gm_kw = self._sg_kw = self._gs_kw = None
+        self._gm_kw = self._sg_kw = self._gs_kw = self._tm_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
@@ -242,6 +256,8 @@ class StreamingDetector:
                 raise ValueError("grid_match with a flow_model is not built: flow_trans is not corrected")
         if grid_scroll is not None and grid_map is None:
             raise ValueError("grid_scroll scrolls the grid of grid_map: give both")
+        if track_map is not None and (tracks is None or grid_map is None):
+            raise ValueError("track_map joins the tracks of tracks with the grid of grid_map: give both")
         self._cls_thresh = float(cls_thresh)
         if tracks is not None and flow_model is None and person_motion is None:
             raise ValueError("tracks needs flow_model: the tracks are fed by the per-person flow")
@@ -346,6 +362,20 @@ class StreamingDetector:
             self._gm_out = ops.grid_map_buffers(self.B, self.N, dev)
             self._gm_centre(np.zeros((self.B, 2)))
             stages.append(Stage(self._grid_stage, tuple(self._gm_state), self._gm_state.grid.zero_))
+        if track_map is not None:
+            # behind the track update and the grid map, whose outputs of this step it joins; it runs when the track
+            # stage runs
+            kw = stage_settings("track_map", track_map)
+            if not self.N <= int(kw["cap"]) <= 1 << 20 or not float(kw["travel"]) >= 0.0 or \
+                    any(not 0 <= int(kw[k]) <= 100 for k in ("free_pct", "occ_pct")) or \
+                    any(int(kw[k]) < 0 for k in ("occ_thresh", "min_points", "min_scans")):
+                raise ValueError("track_map: cap must be in [num_pts, 2^20], free_pct and occ_pct in [0, 100], travel, "
+                                 "occ_thresh, min_points and min_scans >= 0")
+            self._tm_kw = kw
+            self._tm_state = ops.track_map_state(self.B, self._track_state.track_id.shape[1], dev)
+            self._tm_out = ops.track_map_buffers(self.B, self._track_state.track_id.shape[1], self.N, dev)
+            stages.append(Stage(self._track_map_stage, tuple(self._tm_state),
+                                lambda: ops.track_map_reset(self._tm_state), from_first=person_motion is not None))
         if keeps_scan:
             # not in a warm-up: the captured step behind it reads the scan before this one
             stages.append(Stage(self._keep_scan, warm_up=False))
@@ -486,6 +516,11 @@ class StreamingDetector:
     def _grid_stage(self, first):
         ops.grid_map_update(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._gm_state,
                             out=self._gm_out, **self._match_gate(), **self._gm_kw)
+
+    # Behind the track update and the grid map of this step: the grid's word on every track's detection, per slot.
+    def _track_map_stage(self, first):
+        _, _, num, inst = self._dets
+        ops.track_map(self._track_state, self._gm_out, inst, num, self._tm_state, out=self._tm_out, **self._tm_kw)
 
     # Behind the scan matcher's pose launch and in front of everything that reads the pose terms: the pose against the
     # grid as the scans before this one left it.
@@ -674,6 +709,24 @@ class StreamingDetector:
              "offset": self._gs_state.offset.cpu().numpy(), "origin": self._gm_state.origin.cpu().numpy()}
         return [{"shift": h["shift"][b], "scrolled": bool(h["scrolled"][b]), "offset": h["offset"][b],
                  "origin": h["origin"][b]} for b in range(self.B)], o
+
+    def track_map(self):
+        """-> (list with one list per sensor of the live tracks, in slot order as ``tracks()`` has them: dicts of id,
+        cls (0 undecided, 1 free-standing, 2 unsupported, 3 background), points, free, occ (the three sums), scans,
+        moved and start [2];  det_class, one array per sensor with the class of every row of ``detections()``;  the
+        device-resident ``ops.TrackMapState`` and ``ops.TrackMap``, valid until the next call).  Needs ``track_map``
+        and two scans of a sequence.  Reads the state back, i.e. synchronises."""
+        if self._tm_kw is None or self._seen < 2:
+            raise RuntimeError("construct the detector with track_map and feed it two scans of a sequence first")
+        s, o = self._tm_state, self._tm_out
+        h = {k: getattr(s, k).cpu().numpy() for k in s._fields}
+        ids, cls = self._track_state.track_id.cpu().numpy(), o.track_class.cpu().numpy()
+        det_class, counts = o.det_class.cpu().numpy(), self._dets[2].cpu().numpy()
+        live = [[{"id": int(ids[b, t]), "cls": int(cls[b, t]), "points": int(h["ev_points"][b, t]),
+                  "free": int(h["ev_free"][b, t]), "occ": int(h["ev_occ"][b, t]), "scans": int(h["ev_scans"][b, t]),
+                  "moved": bool(h["ev_moved"][b, t]), "start": h["ev_start"][b, t].copy()}
+                 for t in np.flatnonzero(ids[b])] for b in range(self.B)]
+        return live, [det_class[b, :m].copy() for b, m in enumerate(counts)], s, o
 
     def ego_motion(self):
         """-> list (one dict per sensor) of the last step's fit: motion [3] = (theta, u_x, u_y) since the previous

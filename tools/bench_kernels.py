@@ -184,6 +184,16 @@ if "person" in which:
     ops.person_flow(flow, tab, inst, num, xy, dc, rot, trans, ftr, 0.5, out=out)
     tracks = {M: ops.track_buffers(B, M, N, dev) for M in (64, 256)}
     track = lambda M: ops.track_update(out.det_xy_world, out.det_flow, out.det_valid, num, inst, tracks[M])
+    # N15: the map check of those tracks, next to the track update on the same state.  The grid's outputs are those of
+    # the second of two updates of a 128 x 128 grid of 0.25 m with the same scan (every burned-in point finds its own
+    # hit), so the same rows add to the same slots every call and the sums halve whenever they pass the cap: the steady
+    # state of a long sequence
+    tm_grid = ops.grid_map_reset(ops.grid_map_state(B, 128, 128, dev), trans - 16.0)
+    for _ in range(2):
+        tm_seen = ops.grid_map_update(scans, tab, rot, trans, tm_grid, res=0.25, instance_mask=inst, num_det=num, det_cls=dc)
+    tm_state = {M: ops.track_map_state(B, M, dev) for M in tracks}
+    tm_out = {M: ops.track_map_buffers(B, M, N, dev) for M in tracks}
+    tmap = lambda M: ops.track_map(tracks[M], tm_seen, inst, num, tm_state[M], out=tm_out[M])
     # N11: person motion on the same scans, NMS results and pose.  The same scan every call: after the first one every
     # candidate finds its own centroid of the call before -- the steady state, both pairwise searches run in full
     pm_state, pm_out = ops.person_motion_state(B, N, dev), ops.person_motion_buffers(B, N, dev)
@@ -218,6 +228,11 @@ if "person" in which:
         print("   track_update (%.0f candidates per scan): %s" % (out.det_valid.sum().item() / B, ", ".join(
             "max_tracks %d: %.3f ms, %.0f live tracks per sensor" % (M, ms_t[M], (tracks[M].track_id > 0).sum().item() / B)
             for M in tracks)))
+        ms_tm = {M: timeit(lambda: tmap(M), iters=50) for M in tracks}
+        print("   track_map next to it: %s" % ", ".join(
+            "max_tracks %d: %.3f ms (track_update %.3f ms), %.0f slots with evidence per sensor, classes %s"
+            % (M, ms_tm[M], ms_t[M], (tm_state[M].ev_scans > 0).sum().item() / B,
+               tm_out[M].class_count.sum(dim=0).tolist()) for M in tracks))
 
 if "grid" in which or "gridmatch" in which or "gridscroll" in which:
     # N12: the occupancy grid map, 450 beams into 512 x 512 cells of 0.1 m per sensor, for 1024, 8 and 1 sensors, next

@@ -1,5 +1,5 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-scroll]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-scroll] [--track-map]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
@@ -23,6 +23,9 @@ and that one with grid_match=dict() behind the scan matcher, so one process give
 scan-to-grid match.
 --grid-scroll (with --grid): one more step in the same process, the keyframe step with grid_map=dict() and
 grid_scroll=dict() behind the keyframe launch, so one process gives the map step without and with the scrolling grid.
+--track-map (with --person-motion --tracks --grid, without --flow; --ego=scan_match|keyframe|keyframe_map chooses the
+pose, keyframe by default): the replayed step with person_motion=dict(), tracks=dict() and grid_map=dict() without and
+with track_map=dict() behind the grid map, alternating repeats in one process.
 --eager (with --ego, --tracks or --grid): those steps launched eagerly (graph=False) instead of replayed -- the host
 time of the stage wrappers, which a replay does not run."""
 import faulthandler, os, sys, time
@@ -48,8 +51,11 @@ TRACKS = "--tracks" in sys.argv
 GRID = "--grid" in sys.argv
 GRID_MATCH = "--grid-match" in sys.argv
 GRID_SCROLL = "--grid-scroll" in sys.argv
+TRACK_MAP = "--track-map" in sys.argv
+if TRACK_MAP and not (PERSON_MOTION and TRACKS and GRID and FLOW is None):
+    sys.exit("--track-map needs --person-motion --tracks --grid and no --flow")
 EAGER = "--eager" in sys.argv
-sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--person-motion", "--grid", "--eager"))]
+sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--track-map", "--person-motion", "--grid", "--eager"))]
 
 
 class DiffFlow(torch.nn.Module):
@@ -72,7 +78,13 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
     if EGO or TRACKS or GRID:
         poses = np.cumsum(np.random.default_rng(4).normal(0, 0.05, (40, B, 3)), axis=0)
         mk = lambda **kw: StreamingDetector(model, batch=B, nms_min_dist=NMS, flow_model=flow_model, graph=not EAGER, **kw)
-        if GRID:
+        if TRACK_MAP:
+            chain = dict(ego_motion={"scan_match": MATCH, "keyframe_map": KEYFRAME_MAP}.get(EGO_METHOD, KEYFRAME),
+                         person_motion=dict(), tracks=dict(), grid_map=dict())
+            unchecked, checked = mk(**chain), mk(track_map=dict(), **chain)
+            steps = {"person_motion + tracks + grid_map": lambda t: unchecked(scans[:, t]),
+                     "person_motion + tracks + grid_map + track_map": lambda t: checked(scans[:, t])}
+        elif GRID:
             keyed_only, gridded = mk(ego_motion=KEYFRAME), mk(ego_motion=KEYFRAME, grid_map=dict())
             steps = {"keyframe": lambda t: keyed_only(scans[:, t]), "keyframe + grid_map": lambda t: gridded(scans[:, t])}
             if GRID_SCROLL:
@@ -126,6 +138,14 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
                     step(t)
                 torch.cuda.synchronize()
                 ms[name].append((time.perf_counter() - t0) / 32 * 1e3)
+        if TRACK_MAP:
+            live, _, state, out = checked.track_map()
+            print("   track_map after 40 scans: live tracks %s, with evidence %s, classes (0-3) %s"
+                  % ([len(l) for l in live], (state.ev_scans > 0).sum(dim=1).tolist(), out.class_count.tolist()))
+            print("streaming step B=%d, %s per scan, 4 alternating repeats of 32 steps: %s"
+                  % (B, "eager launches" if EAGER else "hipGraph replay",
+                     ", ".join("%s %s ms" % (k, " ".join("%.3f" % v for v in vs)) for k, vs in ms.items())), flush=True)
+            continue
         if EGO_METHOD == "keyframe_map" and not TRACKS:
             fits, _ = mapped.ego_motion()
             print("   keyframe_map at the last scan: iterations %s, matched %s, ok %s, key age %s, slot %s"
