@@ -764,6 +764,70 @@ int pof_track_map(const int32_t *instance_mask, const int32_t *num_det, const in
                   int occ_pct, int min_points, int min_scans, double travel, int cap, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N16 map-predicted scan: a ray cast of the occupancy grid (N12) from the sensor pose, per beam.  N12-N15 read the map
+ * only at a beam's endpoint; this stage walks it along the beam and says where the map expects the beam to end, whether
+ * the point stands in front of that surface in space the map knows to be empty, whether the beam went through something
+ * the map holds as solid, and whether it passed cells the map knows nothing about.  The reference has nothing of the
+ * kind; the specification is this comment (restated in NumPy by tests/test_grid_cast.py).  One sensor per batch entry,
+ * two launches on the stream (the walk, then the counts).  No state: the grid and the origin are read only, and the
+ * grid is read as it stands, so in a step this stage runs in front of pof_grid_map_update, as point_prior is taken.
+ * Inputs: ranges [B][N] float32, the current scan; tab the angle table; the pose terms rot [B][4] float32 row-major and
+ *   trans [B][2] float64; grid [B][H][W] int16 and origin [B][2] float64 of N12; optionally the NMS results
+ *   instance_mask [B][N], num_det [B] (clamped to [0, N]) and det_cls [B][N], all three or none (NULL): only the
+ *   detection rows are used, no score gates anything here (det_cls is not read).
+ * The walk of beam i, float64 with plain multiplies, adds and true divisions (no FMA, no transcendental):
+ *   u_x = (t_x - o_x) / res, u_y likewise; c_x = floor(u_x), c_y = floor(u_y): N14's arithmetic for the sensor's cell.
+ *   The sensor is INSIDE when 0 <= c_x < W and 0 <= c_y < H, compared in double (a NaN is outside).  Otherwise every
+ *   beam of the sensor has state OUTSIDE and walks nothing.
+ *   d_x = (double)R00 cos_i + (double)R01 sin_i,  d_y = (double)R10 cos_i + (double)R11 sin_i.
+ *   Crossings of the cell borders on the x axis:  d_x > 0:  a_x = ((c_x + 1.0) - u_x) / d_x, q_x = 1.0 / d_x, step +1;
+ *   d_x < 0:  a_x = (u_x - c_x) / (-d_x), q_x = 1.0 / (-d_x), step -1;  otherwise (zero or NaN) the axis has no crossing.
+ *   The k-th crossing is at X_k = a_x + (double)k q_x (closed form, no running sum), +inf for an axis without one; the
+ *   y axis likewise.  The walk starts in cell (c_x, c_y) with k_x = k_y = 0.
+ *   A step:  X = X_kx, Y = Y_ky.  Both +inf: the beam stops (state NONE outside a run).  Else X <= Y:  t = X, the cell
+ *   moves by the x step, k_x += 1;  else t = Y, the cell moves by the y step, k_y += 1: through a corner x goes first.
+ *   rho = t res: the parameter in cells times res.  (d_x, d_y) is a float32 rotation of a unit vector, so rho is the
+ *   metric range along the beam to about 1e-7 relative.  The sensor's own cell is not tested.
+ *   For the cell a step enters, in this order:
+ *     (a) rho >= max_range: stop; the state is OPEN, or inside an occupied run exp_far = rho and the state stays WALL;
+ *     (b) the cell is outside the grid (tested in integers): stop; EDGE, or inside a run exp_far = rho, WALL;
+ *     (c) v = grid[iy][ix].  Outside a run and v >= occ_thresh: the run starts, exp_range = rho, exp_cell = iy W + ix,
+ *         state WALL, and the walk goes on.  Inside a run and v < occ_thresh: exp_far = rho, stop.  (Walking a run to
+ *         its far side keeps a wall seen at a grazing angle, whose cells the beam enters early, from reading as
+ *         "gone through".)
+ *     (d) the first entered cell with v > -free_thresh, cells of a run included: free_range = rho.
+ *   exp_steps = the steps taken, the one that stops the walk included (0 for NONE and OUTSIDE).  A walk ends within
+ *   H + W steps: every step moves the cell away from the start by one on one axis, so step H + W at the latest leaves
+ *   the grid; no step beyond that is taken and no other bound is relied on.
+ * Outputs per beam, [B][N]: exp_range float64 = the range at which the beam enters the first occupied cell, exp_far
+ *   float64 = the range at which it leaves that occupied run, both +inf unless the state is WALL; free_range float64 =
+ *   the range of the first entered cell not known free, +inf when there was none; exp_cell int32, -1 unless WALL;
+ *   exp_state uint8: 0 NONE, 1 OPEN, 2 EDGE, 3 WALL, 4 OUTSIDE; exp_steps int32.
+ * The class of point i, r = (double)ranges[i], a HIT by N12's rule (r finite, 0 < r < max_range), tested in this order,
+ *   point_class [B][N] uint8:
+ *     0 NONE     not a hit, or the state is NONE or OUTSIDE
+ *     1 MAP      state WALL and r >= exp_range - tol and r <= exp_far + tol
+ *     3 THROUGH  state WALL and r > exp_far + tol
+ *     2 NOVEL    r + tol < exp_range and r < free_range: the point stands in front of the map's surface (exp_range is
+ *                +inf without one) and every cell the beam passed on the way to it is known free
+ *     4 UNKNOWN  everything else
+ * Per detection row k < num_det (NMS results given): det_novel, det_map, det_through [B][N] int32 = the points with
+ *   instance_mask = k + 1 of class NOVEL, MAP, THROUGH.  Rows >= num_det, and every row without NMS results, are zeros.
+ *   class_count [B][5] int32 = the points of the scan per class.
+ * Integer sums in LDS, no global and no floating-point atomics: the same bits in every run, at every batch position
+ * and in a graph replay.
+ * POF_E_BADARG (checked first; nothing written): a NULL required pointer, NMS pointers given in part, res or max_range
+ *   not > 0, tol not >= 0, occ_thresh < 1, free_thresh < 0, B < 0, N < 1.  POF_E_SHAPE (nothing written): N > 4096, H or
+ *   W not a multiple of 64 or outside [64, 2048], B ceil(N / 64) >= 2^31.  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_grid_cast(const float *ranges, const double *tab, const float *rot, const double *trans,
+                  const int32_t *instance_mask, const int32_t *num_det, const double *det_cls, const int16_t *grid,
+                  const double *origin, double res, double max_range, double tol, int occ_thresh, int free_thresh,
+                  int B, int N, int H, int W, double *exp_range, double *exp_far, double *free_range,
+                  int32_t *exp_cell, uint8_t *exp_state, int32_t *exp_steps, uint8_t *point_class, int32_t *det_novel,
+                  int32_t *det_map, int32_t *det_through, int32_t *class_count, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

@@ -920,7 +920,7 @@ def nms_predicted_center(ranges, tab, pred_cls, pred_reg, min_dist=0.5):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The per-scan stages N5-N15.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
+# The per-scan stages N5-N16.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
 # a dtype and a symbolic shape per field.  ``_zeros_of`` allocates a record, ``_checked`` takes a caller's and
 # ``_out_of`` does whichever an ``out=`` needs; ``stage_settings`` reads a wrapper's tunable scalars off its signature.
 def _record(name, persistent=None, **fields):
@@ -1796,6 +1796,64 @@ def track_map(tracks, grid_out, instance_mask, num_det, state, *, occ_thresh=17,
                   _ptr(tracks.track_state), _ptr(tracks.track_det), B, N, M, *[_ptr(t) for t in state],
                   *[_ptr(t) for t in out], int(occ_thresh), int(free_pct), int(occ_pct), int(min_points),
                   int(min_scans), float(travel), int(cap), _stream())
+    return out
+
+
+GridCast = _record("GridCast", exp_range=(_F64, "B", "N"), exp_far=(_F64, "B", "N"), free_range=(_F64, "B", "N"),
+                   exp_cell=(_I32, "B", "N"), exp_state=(_U8, "B", "N"), exp_steps=(_I32, "B", "N"),
+                   point_class=(_U8, "B", "N"), det_novel=(_I32, "B", "N"), det_map=(_I32, "B", "N"),
+                   det_through=(_I32, "B", "N"), class_count=(_I32, "B", 5))
+CAST_STATES = ("none", "open", "edge", "wall", "outside")           # the values of exp_state, 0..4
+CAST_CLASSES = ("none", "map", "novel", "through", "unknown")       # the values of point_class, 0..4
+
+
+def grid_cast_buffers(B, N, device="cuda"):
+    """The eleven outputs of ``grid_cast`` for B scans of N points, zero-filled, as its ``out=`` (allocate once, before
+    a graph capture)."""
+    return _zeros_of(GridCast, device, B=B, N=N)
+
+
+def grid_cast(ranges, tab, rot, trans, state, *, res, instance_mask=None, num_det=None, det_cls=None, max_range=20.0,
+              tol=None, occ_thresh=17, free_thresh=16, out=None):
+    """N16: the scan the occupancy grid predicts, one ray cast per beam, two launches per batch (include/pof_abi.h
+    states the rules in full).
+
+    ranges [B,N] f32, the current scan; tab the angle table; rot [B,2,2] (or [B,4]) f32 and trans [B,2] f64, the
+    sensor's pose at this scan.  ``state``: the ``GridMapState`` of ``grid_map_update``, read only, and read as it
+    stands: call this in front of the scan's ``grid_map_update``, as ``point_prior`` is taken; ``res``: its metres per
+    cell.  Every beam is walked from the sensor's cell through the grid, cell by cell, up to ``max_range``: the first
+    cell that holds >= ``occ_thresh`` starts an occupied run, the first cell behind it that does not ends it, and the
+    first cell that holds more than -``free_thresh`` is where known free space ends.  A point (finite, 0 < r <
+    ``max_range``) is MAP when it lies within ``tol`` (None: ``res``) of the run, THROUGH when it lies behind it, NOVEL
+    when it lies in front of the run -- or where the map has none -- with only known-free cells on the way, else
+    UNKNOWN.  With the NMS results instance_mask [B,N] i32, num_det [B] i32, det_cls [B,N] f64 (all three or none) the
+    classes are also counted per detection row; no score gates anything.
+    -> ``GridCast``: exp_range, exp_far [B,N] f64 (where the beam enters and leaves the run, +inf without one),
+    free_range [B,N] f64 (+inf when every cell was known free), exp_cell [B,N] i32 (iy W + ix of the run's first cell
+    or -1), exp_state [B,N] u8 (``CAST_STATES``: 0 none, 1 open, 2 edge, 3 wall, 4 outside), exp_steps [B,N] i32,
+    point_class [B,N] u8 (``CAST_CLASSES``: 0 none, 1 map, 2 novel, 3 through, 4 unknown), det_novel, det_map,
+    det_through [B,N] i32 per detection row (zeros without the NMS results), class_count [B,5] i32.  N <= 4096.  The
+    same bits in every run.  ``out``: a ``GridCast`` of preallocated tensors (``grid_cast_buffers``)."""
+    ranges, tab, B, N, dev = _scan_input(ranges, tab)
+    if rot is None or trans is None:
+        raise TypeError("rot and trans must be tensors on the HIP device (no CPU path)")
+    _check_pose_terms(B, rot, trans, None)
+    # as grid_map_update: the stage reports per detection, so the three come together or not at all
+    if instance_mask is None and (num_det is not None or det_cls is not None):
+        raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
+    gate = _nms_gate(instance_mask, num_det, det_cls, B, N)
+    state = GridMapState(*state)
+    if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
+        raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
+    H, W = state.grid.shape[1:]
+    state = _checked(GridMapState, state, "state", B=B, H=H, W=W)
+    out = _out_of(GridCast, out, dev, B=B, N=N)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_grid_cast", _ptr(ranges), _ptr(tab), _ptr(rot), _ptr(trans), *[_ptr(t) for t in gate],
+                  _ptr(state.grid), _ptr(state.origin), float(res), float(max_range), float(res if tol is None else tol),
+                  int(occ_thresh), int(free_thresh), B, N, H, W, *[_ptr(t) for t in out], _stream())
     return out
 
 

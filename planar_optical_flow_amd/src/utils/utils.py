@@ -593,7 +593,8 @@ class OccupancyGrid:
     ``reset(origin)``: every cell unknown; origin [2] = the world position of the grid's lower corner -- by default the
     next update puts its pose in the middle of the grid.  ``logodds`` is the grid [H,W] int16 on the host,
     ``probability(unit)`` the occupancy probability of a count worth ``unit`` nat.  ``localize(scan, odom, ...)``
-    corrects a pose against the grid as it stands (``ops.grid_match``) without updating it.
+    corrects a pose against the grid as it stands (``ops.grid_match``) without updating it; ``cast(scan, odom, ...)``
+    ray-casts the grid as it stands along every beam (``ops.grid_cast``), to be called before the scan's ``update``.
     ``scroll=dict(margin=...)`` (None: the grid stays where ``reset`` put it): the grid follows the sensor
     (``ops.grid_scroll``, two more launches in front of ``update`` and ``localize``): within ``margin`` cells of a border
     (None: a quarter of the shorter side in whole tiles) it is shifted by whole tiles of 64 cells so that the sensor
@@ -684,6 +685,38 @@ class OccupancyGrid:
         return _host(pose), dict(shift, best=_host(out.best), score=_host(out.score), votes=int(out.votes[0].item()),
                                  ok=bool(out.ok[0].item()), moved=bool(out.moved[0].item()),
                                  correction=_host(out.correction))
+
+    def cast(self, scan, odom=None, pred_cls=None, pred_reg=None, **settings):
+        """The scan the grid predicts at the pose ``odom`` = (x, y, phi), and what it says about every point of ``scan``
+        (``ops.grid_cast``, two launches; ``settings``: its ``tol``, ``occ_thresh``, ``free_thresh``; ``max_range`` is
+        the grid's).  The grid is not updated and is read as it stands: call this BEFORE the ``update`` of the same
+        scan, which then enters the scan at the same pose (a first pose is put in the middle of the grid here as it
+        would be there, and with ``scroll`` the grid scrolls here first).  With predictions the centre NMS runs first
+        and the classes are also counted per detection.
+        -> dict: exp_range, exp_far, free_range [N] (+inf without), exp_cell, exp_state (0 none, 1 open, 2 edge, 3
+        wall, 4 outside), exp_steps [N], point_class [N] (0 none, 1 map, 2 novel, 3 through, 4 unknown), class_count
+        [5], and with predictions det_novel, det_map, det_through [M], dets_cls [M,1] and instance_mask [N]."""
+        _stage_kw(ops.grid_cast, "grid_cast", settings, "res", "max_range")
+        cur = _to_dev(scan, torch.float32).reshape(1, -1)
+        gate, dc = {}, None
+        if pred_cls is not None and pred_reg is not None:
+            _, dc, num, inst, dtype = _nms(cur, self._tab, pred_cls, pred_reg, self._min_dist)
+            gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
+        rot, trans, _ = _pose_terms(None if odom is None else np.asarray(odom, dtype=np.float64)[None])
+        if self._centre:                                       # as ``update``: the first pose in the middle of the grid
+            self._reset(trans[0] - 0.5 * self.res * np.array(self.shape[::-1], dtype=np.float64))
+            self._centre = False
+        trans = _to_dev(trans, torch.float64)
+        shift = self._scrolled(trans)
+        shared = {k: self._kw[k] for k in ("max_range",) if k in self._kw}
+        out = ops.grid_cast(cur, self._tab, _to_dev(rot, torch.float32), trans, self._state, res=self.res, **gate,
+                            **shared, **settings)
+        result = dict(shift, **{k: _host(getattr(out, k)) for k in out._fields if not k.startswith("det_")})
+        if dc is not None:
+            m = int(num[0].item())
+            result.update({k: _host(getattr(out, k))[:m] for k in ("det_novel", "det_map", "det_through")},
+                          dets_cls=_host(dc)[:m].reshape(-1, 1).astype(dtype), instance_mask=_host(inst))
+        return result
 
     @property
     def origin(self):

@@ -14,7 +14,7 @@ float16 storage (float16 cutout and template).
 Behind the trunk (cutout, model, NMS) a scan runs the stages its detector was built with, always in this order and on
 one stream, so a capture stays one linear chain: the keyframe launch; the scan matcher and its pose launch; the
 grid scroll; the scan-to-grid match; the flow net; the flow fit and its pose launch; the per-person flow; the person motion; the track
-update; the grid map; the map check of the tracks; the copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
+update; the grid cast; the grid map; the map check of the tracks; the copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
 capture's warm-up and the captured region are each a loop over it, the warm-up puts back exactly the state the table names, and
 ``reset()`` clears exactly that ("The stage table").  The paragraphs below say what each stage is.
 With a ``flow_model`` the step ends in the per-person flow (``ops.person_flow``): a flow net on the previous
@@ -48,6 +48,9 @@ that it stands on the middle tile again, origin included, on the device -- the m
 With ``track_map`` (and ``tracks`` plus ``grid_map``) ``ops.track_map`` stands behind the grid map: what
 the grid says about the detection a track was matched with is summed per track slot on the device, and every track has
 a class -- free-standing, unsupported, background -- that an intermittent false positive on a static object cannot shed.
+With ``grid_cast`` (and ``grid_map``) ``ops.grid_cast`` stands directly in front of the grid map: every
+beam is walked through the grid as the scans before this one left it, and every point learns whether it lies on the
+surface the map predicts, in front of it in space known to be empty, behind it, or where the map knows nothing.
 """
 import gc
 from collections import namedtuple
@@ -66,7 +69,7 @@ _MATCHERS = {"scan_match": ops.scan_match, "keyframe": ops.keyframe_match, "keyf
 
 def stage_defaults(arg, cls_thresh=0.5, method="flow"):
     """What the dict given as the constructor argument ``arg`` ("ego_motion" with its ``method``, "tracks",
-    "person_motion", "grid_map", "grid_match", "grid_scroll", "track_map") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
+    "person_motion", "grid_map", "grid_match", "grid_scroll", "track_map", "grid_cast") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
     signature has them (``ops.stage_settings``), and -- stated here and nowhere else -- what the detector overrides or
     adds.  ``cls_thresh``: the detector's."""
     if arg == "ego_motion" and method == "flow":
@@ -83,8 +86,8 @@ def stage_defaults(arg, cls_thresh=0.5, method="flow"):
         return dict(ops.stage_settings(ops.track_update), max_tracks=64)
     if arg == "track_map":
         return ops.stage_settings(ops.track_map)
-    if arg == "grid_scroll":
-        kw = ops.stage_settings(ops.grid_scroll)
+    if arg in ("grid_scroll", "grid_cast"):
+        kw = ops.stage_settings({"grid_scroll": ops.grid_scroll, "grid_cast": ops.grid_cast}[arg])
         del kw["res"]                                          # the grid's: a key of grid_map's dict
         return kw
     # person_motion, grid_map and grid_match always take the detector's cls_thresh: it is not a key of their dicts
@@ -190,7 +193,16 @@ class StreamingDetector:
     what the grid said about each track's detection -- its points, those on cells seen free, those on cells already
     occupied -- to the track's slot and classes the track: 3 background, 1 free-standing, 2 unsupported, 0 undecided.
     ``track_map()`` returns the classes and the evidence; ``reset()`` forgets the evidence.  A scroll of the grid needs
-    nothing here: the evidence is world coordinates and counts, not cells."""
+    nothing here: the evidence is world coordinates and counts, not cells.
+
+    ``grid_cast`` (needs ``grid_map``; works with every source of a pose ``grid_map`` accepts, with ``grid_scroll`` and
+    ``grid_match``, with and without ``nms_min_dist``): None, or a dict of ``max_range`` (20.0), ``tol`` (None: the
+    grid's ``res``), ``occ_thresh`` (17) and ``free_thresh`` (16) of ``ops.grid_cast``.  Every scan, the first of a
+    sequence included, then runs ``ops.grid_cast`` directly in front of the grid map, behind the scroll and the
+    scan-to-grid match: each beam is walked through the grid as the scans before this one left it, and each point is
+    MAP, NOVEL, THROUGH or UNKNOWN (on an empty map every beam runs to the grid's edge and every point is UNKNOWN).
+    ``grid_cast()`` returns the predicted scan and the classes.  The stage keeps nothing: ``reset()`` has nothing of
+    its own to forget."""
 
     # One stage of a scan behind the trunk.  launch(first) enqueues it on the current stream (first: the first scan of a
     # sequence) and writes only fixed buffers; state: the tensors it advances, which a capture's warm-up puts back;
@@ -200,7 +212,7 @@ class StreamingDetector:
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
                  nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None,
-                 grid_map=None, grid_match=None, grid_scroll=None, track_map=None):
+                 grid_map=None, grid_match=None, grid_scroll=None, track_map=None, grid_cast=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -233,7 +245,7 @@ class StreamingDetector:
         # what a feature was built with, None without it; _filter_kw: the settings of ops.track_update (a detector
         # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
-        self._gm_kw = self._sg_kw = self._gs_kw = self._tm_kw = None
+        self._gm_kw = self._sg_kw = self._gs_kw = self._tm_kw = self._gc_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
@@ -256,6 +268,8 @@ class StreamingDetector:
                 raise ValueError("grid_match with a flow_model is not built: flow_trans is not corrected")
         if grid_scroll is not None and grid_map is None:
             raise ValueError("grid_scroll scrolls the grid of grid_map: give both")
+        if grid_cast is not None and grid_map is None:
+            raise ValueError("grid_cast walks the grid of grid_map: give both")
         if track_map is not None and (tracks is None or grid_map is None):
             raise ValueError("track_map joins the tracks of tracks with the grid of grid_map: give both")
         self._cls_thresh = float(cls_thresh)
@@ -361,6 +375,17 @@ class StreamingDetector:
             self._gm_state = ops.grid_map_state(self.B, *shape, dev)
             self._gm_out = ops.grid_map_buffers(self.B, self.N, dev)
             self._gm_centre(np.zeros((self.B, 2)))
+            if grid_cast is not None:
+                # directly in front of the grid map, which it reads as the scans before this one left it, and behind the
+                # scroll and the scan-to-grid match; it advances nothing
+                kw = stage_settings("grid_cast", grid_cast)
+                if not float(kw["max_range"]) > 0.0 or (kw["tol"] is not None and not float(kw["tol"]) >= 0.0) or \
+                        int(kw["occ_thresh"]) < 1 or int(kw["free_thresh"]) < 0:
+                    raise ValueError("grid_cast: max_range must be > 0, tol >= 0 (or None), occ_thresh >= 1 and "
+                                     "free_thresh >= 0")
+                self._gc_kw = kw
+                self._gc_out = ops.grid_cast_buffers(self.B, self.N, dev)
+                stages.append(Stage(self._grid_cast_stage))
             stages.append(Stage(self._grid_stage, tuple(self._gm_state), self._gm_state.grid.zero_))
         if track_map is not None:
             # behind the track update and the grid map, whose outputs of this step it joins; it runs when the track
@@ -516,6 +541,11 @@ class StreamingDetector:
     def _grid_stage(self, first):
         ops.grid_map_update(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._gm_state,
                             out=self._gm_out, **self._match_gate(), **self._gm_kw)
+
+    # Directly in front of the grid map, on every scan of a sequence: the scan the grid predicts, before this scan enters it.
+    def _grid_cast_stage(self, first):
+        ops.grid_cast(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._gm_state,
+                      res=self._gm_kw["res"], out=self._gc_out, **self._match_gate(), **self._gc_kw)
 
     # Behind the track update and the grid map of this step: the grid's word on every track's detection, per slot.
     def _track_map_stage(self, first):
@@ -709,6 +739,16 @@ class StreamingDetector:
              "offset": self._gs_state.offset.cpu().numpy(), "origin": self._gm_state.origin.cpu().numpy()}
         return [{"shift": h["shift"][b], "scrolled": bool(h["scrolled"][b]), "offset": h["offset"][b],
                  "origin": h["origin"][b]} for b in range(self.B)], o
+
+    def grid_cast(self):
+        """-> the last step's ``ops.GridCast``, device-resident and valid until the next call: per beam exp_range,
+        exp_far, free_range, exp_cell, exp_state and exp_steps [B,N], per point point_class [B,N] (0 none, 1 map, 2
+        novel, 3 through, 4 unknown), det_novel, det_map and det_through [B,N] in the row order of ``detections()`` and
+        class_count [B,5].  The grid it was cast through is the one the scans before this one left.  Needs ``grid_cast``
+        and one scan.  No synchronisation: the tensors stay on the device."""
+        if self._gc_kw is None or self._seen < 1:
+            raise RuntimeError("construct the detector with grid_cast and feed it a scan first")
+        return self._gc_out
 
     def track_map(self):
         """-> (list with one list per sensor of the live tracks, in slot order as ``tracks()`` has them: dicts of id,

@@ -1,5 +1,5 @@
 """Per-kernel timing on the GPU box (events on torch's current stream, which is the
-stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [gridscroll] ..."""
+stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [gridscroll] [cast] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -234,7 +234,7 @@ if "person" in which:
             % (M, ms_tm[M], ms_t[M], (tm_state[M].ev_scans > 0).sum().item() / B,
                tm_out[M].class_count.sum(dim=0).tolist()) for M in tracks))
 
-if "grid" in which or "gridmatch" in which or "gridscroll" in which:
+if "grid" in which or "gridmatch" in which or "gridscroll" in which or "cast" in which:
     # N12: the occupancy grid map, 450 beams into 512 x 512 cells of 0.1 m per sensor, for 1024, 8 and 1 sensors, next
     # to person_motion on the same scans, NMS results and pose (alternating, three repeats of 50 launches).  The same
     # scan every call, with lo / hi at the int16 limits so that no cell saturates inside the run and every launch
@@ -251,6 +251,9 @@ if "grid" in which or "gridmatch" in which or "gridscroll" in which:
     # axes, so the calls shift by +3 and -3 tiles and the offset alternates between 3 and 0.  A scroll writes the
     # grid twice and reads it once and the (5/8)^2 of it that stay: the bound of 4 * H * W * 2 bytes per sensor is
     # what a one-tile shift comes near.  Both cases form their position with one small add on the stream.
+    # cast: N16 next to grid_map_update, alternating, on a copy of the grid as two updates left it (every endpoint that
+    # is nobody's burned in twice, every cell in front of it freed twice: a map that knows the scene), the same scans,
+    # NMS results and pose.  Cell reads: the sum of exp_steps, int16 gathers of one lane each.
     N, H, W, RES = 450, 512, 512, 0.1
     rng = np.random.default_rng(1701)
     tab = ops.phi_table()
@@ -318,6 +321,23 @@ if "grid" in which or "gridmatch" in which or "gridscroll" in which:
                       "sensor, %.0f GB/s against the bound of 4*H*W*2 bytes per sensor) next to "
                       "grid_map_update %.3f ms" % (B, H, W, RES, ms_0, ms_1, ms_1 / B * 1e3, moved / ms_1 / 1e6, ms_g))
             del gs_state, gs_scroll
+        if "cast" in which:
+            gc_state = ops.GridMapState(gm_state.grid.clone(), gm_state.origin.clone())
+            gc_out = ops.grid_cast_buffers(B, N, dev)
+            cast = lambda: ops.grid_cast(scans, tab, rot, trans, gc_state, res=RES, instance_mask=inst, num_det=num,
+                                         det_cls=dc, out=gc_out)
+            cast()
+            steps = gc_out.exp_steps.sum().item()
+            for rep in range(3):
+                ms_g, ms_c = timeit(grid, iters=50), timeit(cast, iters=50)
+                print("cast B=%d N=%d %dx%d at %.2f m: grid_cast %.3f ms (%.2f us per sensor) next to grid_map_update %.3f ms; "
+                      "%.1f M cell reads per launch (%.0f per beam, the longest walk %d), %.1f G cells/s; beams per state "
+                      "%s, points per class %s"
+                      % (B, N, H, W, RES, ms_c, ms_c / B * 1e3, ms_g, steps / 1e6, steps / (B * N),
+                         gc_out.exp_steps.max().item(), steps / ms_c / 1e6,
+                         torch.bincount(gc_out.exp_state.flatten().long(), minlength=5).tolist(),
+                         gc_out.class_count.sum(dim=0).tolist()))
+            del gc_state
         for rep in range(3 if "grid" in which else 0):
             ms_g, ms_pm = timeit(grid, iters=50), timeit(motion, iters=50)
             bound = B * 2 * H * W * 2
