@@ -282,6 +282,14 @@ __device__ __forceinline__ void params_sincos(double x, double *sn, double *cs)
 // so the minimum alone decides a point unless it lies in one of the error bands; those points, every point
 // beyond 100 m, and all points of a sample with a "far" detection (centre beyond 100 m or sd > 400) take the
 // exact float64 loop.
+// The candidate pass (one packed pass for both points of a lane, entered by a wave that has a point with
+// min <= thr_assoc) recomputes dd_j with the operands and the operation order of the minimum pass -- the same value
+// bit for bit -- and compares it with w_j - m_assoc and w_j + m_assoc, w_j = fl32(sa_j - sd_j) from the record and
+// m_assoc from launch_flat: the two float32 sums it has always been compared with.  It adds and moves no rounding, so
+// the margin stands as derived: m_assoc >= max_c (1e-3 + 1e-4 max(sd_c, sa_c)) covers E(s2) at s2 = sa_j, the
+// rounding of w_j and of w_j +- m_assoc (2.4e-7 of the span, the factor 1.001); dd_j <= w_j - m_assoc => s2_j <= sa_j
+// (surely a candidate), dd_j > w_j + m_assoc => s2_j > sa_j (surely not).  A different rounding of a screen
+// comparison could change only which path decides a point, never the answer, as long as "sure" stays sure.
 __device__ __forceinline__ bool det_is_far(double cx, double cy, double sd)
 {
     return !(fabs(cx) + fabs(cy) < 100.0) || !(sd <= 400.0);
@@ -1037,43 +1045,67 @@ __device__ __forceinline__ void flat_run(const FlatArgs &L, const FlatBatch &bt,
             }
             bidx[k] = j1;
         };
+        bool exk[2], need_dyn[2], need_assoc[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const bool exk = samp_far || !(fabsf(pxf[k]) + fabsf(pyf[k]) < 100.0f);   // NaN -> exact
-            bool need_dyn = false;
-            if (!exk && mind[k] <= -L.m_dyn) dmask[k] = 0.0f;
-            else need_dyn = want_dyn && (exk || mind[k] <= L.m_dyn);
-            bool need_assoc = want_assoc && (exk || mind[k] <= L.thr_assoc);
-            if (need_assoc && !exk) {
-                // a point near an association disc (a few lanes of most waves): which detection?  The same float32
-                // d_j as above against the detection's own sa_j - sd_j (entry.w): d_j <= w - m surely a candidate,
-                // d_j > w + m surely not.  One sure candidate and nothing in the error band decides the point without
-                // any float64 arithmetic; anything else (overlapping discs, a band) takes the exact loop below.
-                int ncand = 0, jc = 0;
-                bool unsure = false;
-                for (int j = 0; j < n_in; ++j) {
-                    const float4 e = *reinterpret_cast<const float4 *>(ent + 16 * j);
-                    const float exf = pxf[k] - e.x, eyf = pyf[k] - e.y;
-                    const float d = fmaf(exf, exf, fmaf(eyf, eyf, e.z));
-                    if (d <= e.w + L.m_assoc) {
-                        if (d <= e.w - L.m_assoc) { ++ncand; jc = j; }
-                        else unsure = true;
-                    }
+            exk[k] = samp_far || !(fabsf(pxf[k]) + fabsf(pyf[k]) < 100.0f);   // NaN -> exact
+            need_dyn[k] = false;
+            if (!exk[k] && mind[k] <= -L.m_dyn) dmask[k] = 0.0f;
+            else need_dyn[k] = want_dyn && (exk[k] || mind[k] <= L.m_dyn);
+            need_assoc[k] = want_assoc && (exk[k] || mind[k] <= L.thr_assoc);
+        }
+        // Points near an association disc (a few lanes of four waves in ten): which detection?  ONE pass over the
+        // wave's n_loop screen entries for both points of the lane, entered by the whole wave when any lane has such
+        // a point: the same packed d_j as above (same operands, same order, hence the same value) against the
+        // detection's own sa_j - sd_j (entry.w): d_j <= w - m surely a candidate, d_j > w + m surely not, between
+        // them the error band.  Per point three values are kept by compare-and-add / select, with no branch per
+        // point or per detection: how many d_j lay at or below w + m, how many of those were sure, and the slot of
+        // the last sure one.  One sure candidate and nothing in a band (both counts 1) decides the point without any
+        // float64 arithmetic, both counts 0 decides it as unassociated; anything else (overlapping discs, a band)
+        // takes the exact loop below.  Slots beyond the lane's own sample count hold the null entry (d_j = +inf: in
+        // neither count), so a wave that straddles two samples runs the larger count for all its lanes.  The entries
+        // are read two at a time, ahead of the arithmetic (slot 7 is the last one an odd count reads: inside the image).
+        const bool scr[2] = {need_assoc[0] && !exk[0], need_assoc[1] && !exk[1]};
+        if (__builtin_amdgcn_ballot_w64(scr[0] || scr[1]) != 0) {
+            int nin[2] = {0, 0}, nsure[2] = {0, 0}, jc[2] = {0, 0};
+            auto screen = [&](const float4 e, const int j) {
+                const F2V cx2 = {e.x, e.x}, cy2 = {e.y, e.y}, ns2 = {e.z, e.z};
+                const F2V ex = pxf - cx2, ey = pyf - cy2;
+                F2V d = __builtin_elementwise_fma(ey, ey, ns2);
+                d = __builtin_elementwise_fma(ex, ex, d);
+                const float hi = e.w + L.m_assoc, lo = e.w - L.m_assoc;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const bool sure = d[k] <= lo;
+                    nin[k] += d[k] <= hi ? 1 : 0;
+                    nsure[k] += sure ? 1 : 0;
+                    jc[k] = sure ? j : jc[k];
                 }
-                if (!unsure && ncand <= 1) {
-                    if (ncand == 1) bidx[k] = jc + 1;
-                    need_assoc = false;
-                }
+            };
+            for (int j = 0; j < n_loop; j += 2) {
+                const float4 e0 = *reinterpret_cast<const float4 *>(ent + 16 * j);
+                const float4 e1 = *reinterpret_cast<const float4 *>(ent + 16 * j + 16);
+                screen(e0, j);
+                screen(e1, j + 1);
             }
-            if (need_dyn || need_assoc) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const bool decided = scr[k] && nin[k] == nsure[k] && nsure[k] <= 1;
+                bidx[k] = decided && nsure[k] == 1 ? jc[k] + 1 : 0;
+                need_assoc[k] = need_assoc[k] && !decided;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (need_dyn[k] || need_assoc[k]) {
                 const double pxd = p64x(k), pyd = p64y(k);
                 for (int j = 0; j < n_in; ++j) {
                     const D2V c = *reinterpret_cast<const D2V *>(hdr + kImgCtr + 16 * j);
                     const int cl = cls_of(j);
                     const double exd = pxd - c.x, eyd = pyd - c.y;
                     const double s2 = exd * exd + eyd * eyd;   // cdist: (dx*dx) + (dy*dy), no fusion
-                    if (need_dyn && s2 <= sel3(L.sd, cl)) dmask[k] = 0.0f;                 // dist <= dyn radius
-                    if (need_assoc && s2 <= sel3(L.sa, cl)) candidate(k, j + 1, s2, sel3(L.ra, cl));   // dist < assoc radius
+                    if (need_dyn[k] && s2 <= sel3(L.sd, cl)) dmask[k] = 0.0f;                 // dist <= dyn radius
+                    if (need_assoc[k] && s2 <= sel3(L.sa, cl)) candidate(k, j + 1, s2, sel3(L.ra, cl));   // dist < assoc radius
                 }
             }
         }
@@ -1094,30 +1126,50 @@ __device__ __forceinline__ void flat_run(const FlatArgs &L, const FlatBatch &bt,
             }
         }
         if (ok && want_assoc) {
-            long long cls[2];
-            float gx[2], gy[2];
+            long long cls[2] = {0, 0};
+            float gx[2] = {0.0f, 0.0f}, gy[2] = {0.0f, 0.0f};
+            if (bidx[0] > 0 || bidx[1] > 0) {
+                // ONE block for the lane's two points: the float64 (cos, sin) of its two beams are 32 contiguous
+                // bytes of the table -- both loads go out together and are waited for once -- and a point without a
+                // winner computes along on inline slot 7 and selects zero at the end.
+                const D2V t0 = *reinterpret_cast<const D2V *>(tab_cs + 2u * (unsigned)i0);
+                const D2V t1 = *reinterpret_cast<const D2V *>(tab_cs + 2u * (unsigned)i0 + 2);
+                const double c64[2] = {t0.x, t1.x}, s64[2] = {t0.y, t1.y};
+                double wx[2], wy[2];
+                long long lab[2];
 #pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                cls[k] = 0;
-                gx[k] = gy[k] = 0.0f;
-                if (bidx[k] > 0) {
-                    // winner's centre and label.  global_to_canonical via the angle-difference identity:
-                    // sin(dp-phi)*dr = cy*cos(phi) - cx*sin(phi)
-                    double wx, wy;
-                    if (bidx[k] <= kInline) {
-                        const D2V c = *reinterpret_cast<const D2V *>(hdr + kImgCtr + 16 * (bidx[k] - 1));
-                        wx = c.x; wy = c.y;
-                        const int cl = cls_of(bidx[k] - 1);
-                        cls[k] = cl == 0 ? L.lb[0] : (cl == 1 ? L.lb[1] : L.lb[2]);
-                    } else {
-                        const GLOBAL_AS double *w = (const GLOBAL_AS double *)bt.ws_det + (long long)(dfirst + bidx[k] - 1) * kDetStride;
-                        wx = w[0];
-                        wy = w[1];
-                        cls[k] = (long long)w[4];
+                for (int k = 0; k < 2; ++k) {
+                    // winner's centre and label from the staged image, the label by selects
+                    const int slot = (bidx[k] - 1) & (kInline - 1);
+                    const D2V c = *reinterpret_cast<const D2V *>(hdr + kImgCtr + 16 * slot);
+                    wx[k] = c.x; wy[k] = c.y;
+                    // class 0, 1 or 2 -> label, as integer multiply-adds (a ternary on the scalar labels comes
+                    // back from the compiler as nested exec branches)
+                    const unsigned cl = (unsigned)cls_of(slot);
+                    const unsigned lb0 = (unsigned)L.lb[0];
+                    lab[k] = (int)(lb0 + (cl & 1u) * ((unsigned)L.lb[1] - lb0) + (cl >> 1) * ((unsigned)L.lb[2] - lb0));
+                }
+                if (nd > kInline) {
+                    // crowded sample, winner beyond the inline slots (rare): centre and label from the CSR table
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        if (bidx[k] > kInline) {
+                            const GLOBAL_AS double *w = (const GLOBAL_AS double *)bt.ws_det + (long long)(dfirst + bidx[k] - 1) * kDetStride;
+                            wx[k] = w[0];
+                            wy[k] = w[1];
+                            lab[k] = (long long)w[4];
+                        }
                     }
-                    const double c = cs64(k), sn_ = sn64(k);
-                    gx[k] = (float)(wy * c - wx * sn_);
-                    gy[k] = (float)((wx * c + wy * sn_) - (double)r[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    // global_to_canonical via the angle-difference identity: sin(dp-phi)*dr = cy*cos(phi) - cx*sin(phi)
+                    const bool won = bidx[k] > 0;
+                    const float tx = (float)(wy[k] * c64[k] - wx[k] * s64[k]);
+                    const float ty = (float)((wx[k] * c64[k] + wy[k] * s64[k]) - (double)r[k]);
+                    cls[k] = won ? lab[k] : 0;
+                    gx[k] = won ? tx : 0.0f;
+                    gy[k] = won ? ty : 0.0f;
                 }
             }
             if (cfg.has(kOutClosest)) stream_ll2(reinterpret_cast<long long *>(bt.closest) + 2 * pair0, (unsigned)lane, bidx[0], bidx[1]);
