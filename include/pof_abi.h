@@ -828,6 +828,61 @@ int pof_grid_cast(const float *ranges, const double *tab, const float *rot, cons
                   int32_t *det_map, int32_t *det_through, int32_t *class_count, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N17 novelty segments: the NOVEL points of a scan grouped into detections.  N16 says per point whether it stands in
+ * front of the map's surface in space the map knows to be empty; this stage turns the runs of such points into
+ * detections in the layout every stage behind the detector takes -- instance_mask, num_det, det_xy, det_cls, the results
+ * of pof_nms_predicted_center in the argument order of pof_person_motion -- so a mover the net does not report is a
+ * detection row all the same, and the chain needs no net at all.  The reference has nothing of the kind; the
+ * specification is this comment (restated in NumPy by tests/test_novel_segments.py).  One sensor per batch entry, one
+ * launch, the per-sensor workgroup of pof_sensor.h: one wave up to N = 512, 512 threads up to N = 4096, chosen by the
+ * launcher from N alone.  No state.
+ * Inputs: ranges [B][N] float32, the scan; tab the angle table; point_class [B][N] uint8 as pof_grid_cast writes it (any
+ *   byte is legal, only the value 2 means anything); optionally the NMS results nms_instance_mask [B][N], nms_num_det
+ *   [B] (clamped to [0, N]) and nms_det_cls [B][N], all three or none (NULL), with cls_thresh: they only feed det_known.
+ *   Settings: jump (0.3 m), the largest distance between consecutive members of one segment; max_skip (2), the beams
+ *   that may lie between two consecutive members; min_points (3), the fewest members of a kept segment; max_width
+ *   (1.0 m), the largest distance between a kept segment's first and last member.
+ * Everything is float64 with plain multiplies and adds: no FMA, no libm call, no square root.
+ *   MEMBERS.  Beam i is a member when point_class[i] == 2 and r = (double)ranges[i] is finite and r > 0.  Its point is
+ *     p_i = (r cos_i, r sin_i), one rounding per product, in the sensor frame.
+ *   SEGMENTS.  The members are walked in ascending beam index.  Member i continues the open segment when the previous
+ *     member l is at most max_skip beams back, i - l <= max_skip + 1, AND d2 = dx dx + dy dy <= jump jump with dx =
+ *     p_i.x - p_l.x, dy = p_i.y - p_l.y and jump jump formed once.  Otherwise i closes the open segment and opens a new
+ *     one.  Beams that are no members belong to no segment and do not break one within the skip.  There is no
+ *     wrap-around from beam N - 1 to beam 0.
+ *   FILTERS, in this order.  A segment with fewer than min_points members is dropped as FEW.  Then w2 = the squared
+ *     distance between its last and its first member, d2's expression with i = last and l = first; the segment is
+ *     dropped as WIDE unless w2 <= max_width max_width (formed once; written so that a NaN drops it, though members
+ *     give none).  A segment that is both counts as few.
+ *   ROWS.  The kept segments are numbered in the order of their first beam: row k = 0, 1, ..., instance id k + 1.
+ * Outputs, the first four with the dtypes, shapes and meaning of pof_nms_predicted_center's results; every per-row
+ *   field is zero in the rows at and beyond num_det:
+ *   instance_mask [B][N] int32  k + 1 on the members of kept segment k, else 0
+ *   num_det       [B]    int32  the number of kept segments
+ *   det_xy     [B][N][2] float64  per row the mean of its members' p, in the sensor frame like the NMS's det_xy: the
+ *                                 sums are added in ascending beam index from 0.0 with plain adds, then divided by the
+ *                                 count (one true division per coordinate)
+ *   det_cls       [B][N] float64  exactly 1.0 on a kept row: a downstream cls_thresh <= 1 passes it
+ *   det_count, det_first, det_last [B][N] int32  the row's members, its first and its last beam
+ *   det_width2    [B][N] float64  the row's w2
+ *   det_known     [B][N] int32  the row's members that belong to a confident NMS detection: nms_instance_mask in [1,
+ *                                 nms_num_det] and nms_det_cls[id - 1] >= cls_thresh (pof_person_flow's det_valid);
+ *                                 zeros without the NMS results
+ *   seg_count     [B][3] int32  segments before the filters, dropped as few, dropped as wide
+ * Integer maxima and counts use LDS atomics; every float64 sum is added by one lane in beam order.  No global atomics:
+ * the same bits in every run, at every batch position and in a graph replay.
+ * POF_E_BADARG (checked first; nothing written): a NULL required pointer, NMS pointers given in part, jump not > 0,
+ *   max_width not >= 0, min_points < 1, max_skip outside [0, 64], B < 0, N < 1.  POF_E_SHAPE (nothing written): N >
+ *   4096.  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_novel_segments(const float *ranges, const double *tab, const uint8_t *point_class,
+                       const int32_t *nms_instance_mask, const int32_t *nms_num_det, const double *nms_det_cls,
+                       double cls_thresh, double jump, int max_skip, int min_points, double max_width, int B, int N,
+                       int32_t *instance_mask, int32_t *num_det, double *det_xy, double *det_cls, int32_t *det_count,
+                       int32_t *det_first, int32_t *det_last, double *det_width2, int32_t *det_known,
+                       int32_t *seg_count, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

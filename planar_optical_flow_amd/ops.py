@@ -920,7 +920,7 @@ def nms_predicted_center(ranges, tab, pred_cls, pred_reg, min_dist=0.5):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The per-scan stages N5-N16.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
+# The per-scan stages N5-N17.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
 # a dtype and a symbolic shape per field.  ``_zeros_of`` allocates a record, ``_checked`` takes a caller's and
 # ``_out_of`` does whichever an ``out=`` needs; ``stage_settings`` reads a wrapper's tunable scalars off its signature.
 def _record(name, persistent=None, **fields):
@@ -1854,6 +1854,53 @@ def grid_cast(ranges, tab, rot, trans, state, *, res, instance_mask=None, num_de
         _lib.call("pof_grid_cast", _ptr(ranges), _ptr(tab), _ptr(rot), _ptr(trans), *[_ptr(t) for t in gate],
                   _ptr(state.grid), _ptr(state.origin), float(res), float(max_range), float(res if tol is None else tol),
                   int(occ_thresh), int(free_thresh), B, N, H, W, *[_ptr(t) for t in out], _stream())
+    return out
+
+
+NovelSegments = _record("NovelSegments", instance_mask=(_I32, "B", "N"), num_det=(_I32, "B"), det_xy=(_F64, "B", "N", 2),
+                        det_cls=(_F64, "B", "N"), det_count=(_I32, "B", "N"), det_first=(_I32, "B", "N"),
+                        det_last=(_I32, "B", "N"), det_width2=(_F64, "B", "N"), det_known=(_I32, "B", "N"),
+                        seg_count=(_I32, "B", 3))
+
+
+def novel_segments_buffers(B, N, device="cuda"):
+    """The ten outputs of ``novel_segments`` for B scans of N points, zero-filled, as its ``out=`` (allocate once, before
+    a graph capture)."""
+    return _zeros_of(NovelSegments, device, B=B, N=N)
+
+
+def novel_segments(ranges, tab, point_class, *, instance_mask=None, num_det=None, det_cls=None, cls_thresh=0.5,
+                   jump=0.3, max_skip=2, min_points=3, max_width=1.0, out=None):
+    """N17: the NOVEL points of a scan grouped into detections, one launch per batch (include/pof_abi.h states the
+    rules in full).
+
+    ranges [B,N] f32, the scan; tab the angle table; point_class [B,N] u8 as ``grid_cast`` returns it.  A beam is a
+    member when its class is 2 (novel) and its range is finite and > 0.  The members are walked in beam order: one
+    continues the open segment when the member before it is at most ``max_skip`` beams back and at most ``jump`` metres
+    away, else it opens a new one.  A segment of fewer than ``min_points`` members is dropped, then one whose first and
+    last member lie more than ``max_width`` metres apart; the kept ones are numbered in the order of their first beam.
+    With the NMS results instance_mask [B,N] i32, num_det [B] i32, det_cls [B,N] f64 (all three or none) ``det_known``
+    says how many members of a row belong to a detection with a score >= ``cls_thresh``.
+    -> ``NovelSegments``: instance_mask [B,N] i32, num_det [B] i32, det_xy [B,N,2] f64 (the mean of the row's points in
+    the sensor frame), det_cls [B,N] f64 (1.0 on a kept row) -- the four results of ``nms_predicted_center`` in the
+    argument order of ``person_motion``, so ``person_motion(ranges, tab, *rec[:4], ...)`` takes them -- det_count,
+    det_first, det_last [B,N] i32, det_width2 [B,N] f64, det_known [B,N] i32 (rows >= num_det[b] are zeros) and
+    seg_count [B,3] i32 (segments before the filters, dropped as few, dropped as wide).  N <= 4096.  The same bits in
+    every run.  ``out``: a ``NovelSegments`` of preallocated tensors (``novel_segments_buffers``)."""
+    ranges, tab, B, N, dev = _scan_input(ranges, tab)
+    point_class = _dev(point_class, torch.uint8, "point_class")
+    if tuple(point_class.shape) != (B, N):
+        raise ValueError("point_class must be [B,N]")
+    if instance_mask is None and (num_det is not None or det_cls is not None):
+        raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
+    gate = _nms_gate(instance_mask, num_det, det_cls, B, N)
+    out = _out_of(NovelSegments, out, dev, B=B, N=N)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_novel_segments", _ptr(ranges), _ptr(tab), _ptr(point_class), *[_ptr(t) for t in gate],
+                  float(cls_thresh), float(jump), int(max_skip), int(min_points), float(max_width), B, N,
+                  *[_ptr(t) for t in out], _stream())
     return out
 
 

@@ -594,7 +594,8 @@ class OccupancyGrid:
     next update puts its pose in the middle of the grid.  ``logodds`` is the grid [H,W] int16 on the host,
     ``probability(unit)`` the occupancy probability of a count worth ``unit`` nat.  ``localize(scan, odom, ...)``
     corrects a pose against the grid as it stands (``ops.grid_match``) without updating it; ``cast(scan, odom, ...)``
-    ray-casts the grid as it stands along every beam (``ops.grid_cast``), to be called before the scan's ``update``.
+    ray-casts the grid as it stands along every beam (``ops.grid_cast``), to be called before the scan's ``update``;
+    ``novel_segments(scan, odom, ...)`` does that and groups the NOVEL points into detections (``ops.novel_segments``).
     ``scroll=dict(margin=...)`` (None: the grid stays where ``reset`` put it): the grid follows the sensor
     (``ops.grid_scroll``, two more launches in front of ``update`` and ``localize``): within ``margin`` cells of a border
     (None: a quarter of the shorter side in whole tiles) it is shifted by whole tiles of 64 cells so that the sensor
@@ -696,7 +697,11 @@ class OccupancyGrid:
         -> dict: exp_range, exp_far, free_range [N] (+inf without), exp_cell, exp_state (0 none, 1 open, 2 edge, 3
         wall, 4 outside), exp_steps [N], point_class [N] (0 none, 1 map, 2 novel, 3 through, 4 unknown), class_count
         [5], and with predictions det_novel, det_map, det_through [M], dets_cls [M,1] and instance_mask [N]."""
-        _stage_kw(ops.grid_cast, "grid_cast", settings, "res", "max_range")
+        return self._cast(scan, odom, pred_cls, pred_reg, _stage_kw(ops.grid_cast, "grid_cast", settings, "res",
+                                                                    "max_range"))[0]
+
+    def _cast(self, scan, odom, pred_cls, pred_reg, settings):
+        """``cast`` -> (its dict, the scan [1,N] on the device, the ``ops.GridCast``, the NMS gate's keywords)."""
         cur = _to_dev(scan, torch.float32).reshape(1, -1)
         gate, dc = {}, None
         if pred_cls is not None and pred_reg is not None:
@@ -716,6 +721,34 @@ class OccupancyGrid:
             m = int(num[0].item())
             result.update({k: _host(getattr(out, k))[:m] for k in ("det_novel", "det_map", "det_through")},
                           dets_cls=_host(dc)[:m].reshape(-1, 1).astype(dtype), instance_mask=_host(inst))
+        return result, cur, out, gate
+
+    def novel_segments(self, scan, odom=None, pred_cls=None, pred_reg=None, **settings):
+        """``cast(scan, odom, ...)`` and, on its classes, the runs of NOVEL points as detections
+        (``ops.novel_segments``, one more launch; ``settings``: its ``jump``, ``max_skip``, ``min_points``,
+        ``max_width`` and the ``tol``, ``occ_thresh``, ``free_thresh`` of the cast; ``cls_thresh`` is the grid's).  Like
+        ``cast`` it updates nothing and is to be called BEFORE the ``update`` of the same scan; it centres a first pose
+        and scrolls as ``cast`` does.  With predictions ``seg_known`` says how many points of a segment the NMS's
+        confident detections hold.
+        -> the dict of ``cast`` and seg_instance_mask [N] (k + 1 on the points of kept segment k), seg_num (K, the kept
+        segments), seg_xy [K,2] (the mean of the segment's points, sensor frame), seg_cls [K] (ones), seg_points,
+        seg_first, seg_last, seg_known [K], seg_width2 [K] and seg_count [3] (segments before the filters, dropped as
+        few, dropped as wide)."""
+        own = set(ops.stage_settings(ops.novel_segments)) - {"cls_thresh"}
+        cast_kw = {k: v for k, v in settings.items() if k not in own}
+        unknown = set(cast_kw) - (set(ops.stage_settings(ops.grid_cast)) - {"res", "max_range"})
+        if unknown:
+            raise ValueError("unknown novel_segments settings: %s" % sorted(unknown))
+        result, cur, out, gate = self._cast(scan, odom, pred_cls, pred_reg, cast_kw)
+        shared = {k: self._kw[k] for k in ("cls_thresh",) if k in self._kw}
+        seg = ops.novel_segments(cur, self._tab, out.point_class, **gate, **shared,
+                                 **{k: v for k, v in settings.items() if k in own})
+        m = int(seg.num_det[0].item())
+        result.update(seg_instance_mask=_host(seg.instance_mask), seg_num=m, seg_count=_host(seg.seg_count),
+                      **{name: _host(getattr(seg, f))[:m] for name, f in (
+                          ("seg_xy", "det_xy"), ("seg_cls", "det_cls"), ("seg_points", "det_count"),
+                          ("seg_first", "det_first"), ("seg_last", "det_last"), ("seg_width2", "det_width2"),
+                          ("seg_known", "det_known"))})
         return result
 
     @property

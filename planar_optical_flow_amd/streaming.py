@@ -14,7 +14,7 @@ float16 storage (float16 cutout and template).
 Behind the trunk (cutout, model, NMS) a scan runs the stages its detector was built with, always in this order and on
 one stream, so a capture stays one linear chain: the keyframe launch; the scan matcher and its pose launch; the
 grid scroll; the scan-to-grid match; the flow net; the flow fit and its pose launch; the per-person flow; the person motion; the track
-update; the grid cast; the grid map; the map check of the tracks; the copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
+update; the grid cast; the novelty segments; the grid map; the map check of the tracks; the copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
 capture's warm-up and the captured region are each a loop over it, the warm-up puts back exactly the state the table names, and
 ``reset()`` clears exactly that ("The stage table").  The paragraphs below say what each stage is.
 With a ``flow_model`` the step ends in the per-person flow (``ops.person_flow``): a flow net on the previous
@@ -51,6 +51,9 @@ a class -- free-standing, unsupported, background -- that an intermittent false 
 With ``grid_cast`` (and ``grid_map``) ``ops.grid_cast`` stands directly in front of the grid map: every
 beam is walked through the grid as the scans before this one left it, and every point learns whether it lies on the
 surface the map predicts, in front of it in space known to be empty, behind it, or where the map knows nothing.
+With ``novel_segments`` (and ``grid_cast``) ``ops.novel_segments`` stands directly behind the grid cast:
+the runs of points in front of the map's surface become detections in the layout of the NMS's, so a mover the net does
+not report is a detection row all the same; with ``gate_map`` they gate the grid map, which then does not burn them in.
 """
 import gc
 from collections import namedtuple
@@ -69,7 +72,7 @@ _MATCHERS = {"scan_match": ops.scan_match, "keyframe": ops.keyframe_match, "keyf
 
 def stage_defaults(arg, cls_thresh=0.5, method="flow"):
     """What the dict given as the constructor argument ``arg`` ("ego_motion" with its ``method``, "tracks",
-    "person_motion", "grid_map", "grid_match", "grid_scroll", "track_map", "grid_cast") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
+    "person_motion", "grid_map", "grid_match", "grid_scroll", "track_map", "grid_cast", "novel_segments") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
     signature has them (``ops.stage_settings``), and -- stated here and nowhere else -- what the detector overrides or
     adds.  ``cls_thresh``: the detector's."""
     if arg == "ego_motion" and method == "flow":
@@ -86,6 +89,12 @@ def stage_defaults(arg, cls_thresh=0.5, method="flow"):
         return dict(ops.stage_settings(ops.track_update), max_tracks=64)
     if arg == "track_map":
         return ops.stage_settings(ops.track_map)
+    if arg == "novel_segments":
+        # det_known takes the detector's cls_thresh: it is not a key of the dict; gate_map: whether the segments gate
+        # the grid map of the same scan
+        kw = ops.stage_settings(ops.novel_segments)
+        del kw["cls_thresh"]
+        return dict(kw, gate_map=False)
     if arg in ("grid_scroll", "grid_cast"):
         kw = ops.stage_settings({"grid_scroll": ops.grid_scroll, "grid_cast": ops.grid_cast}[arg])
         del kw["res"]                                          # the grid's: a key of grid_map's dict
@@ -202,7 +211,16 @@ class StreamingDetector:
     scan-to-grid match: each beam is walked through the grid as the scans before this one left it, and each point is
     MAP, NOVEL, THROUGH or UNKNOWN (on an empty map every beam runs to the grid's edge and every point is UNKNOWN).
     ``grid_cast()`` returns the predicted scan and the classes.  The stage keeps nothing: ``reset()`` has nothing of
-    its own to forget."""
+    its own to forget.
+
+    ``novel_segments`` (needs ``grid_cast``; with and without ``nms_min_dist``): None, or a dict of ``jump`` (0.3 m),
+    ``max_skip`` (2), ``min_points`` (3) and ``max_width`` (1.0 m) of ``ops.novel_segments`` and ``gate_map`` (False).
+    Every scan, the first of a sequence included, then runs ``ops.novel_segments`` directly behind the grid cast and in
+    front of the grid map: the NOVEL points are grouped into segments, and the kept ones are detections in the layout
+    of the NMS's results.  With ``nms_min_dist`` ``det_known`` says how many points of a segment the detector's own
+    confident detections (``cls_thresh``) hold.  ``gate_map=True`` (only without ``nms_min_dist``: merging two gates is
+    not built) makes the segments the grid map's gate, so what the stage found is not burned in.
+    ``novel_segments()`` returns the record.  The stage keeps nothing: ``reset()`` has nothing of its own to forget."""
 
     # One stage of a scan behind the trunk.  launch(first) enqueues it on the current stream (first: the first scan of a
     # sequence) and writes only fixed buffers; state: the tensors it advances, which a capture's warm-up puts back;
@@ -212,7 +230,8 @@ class StreamingDetector:
 
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
                  nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None,
-                 grid_map=None, grid_match=None, grid_scroll=None, track_map=None, grid_cast=None):
+                 grid_map=None, grid_match=None, grid_scroll=None, track_map=None, grid_cast=None,
+                 novel_segments=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -245,7 +264,7 @@ class StreamingDetector:
         # what a feature was built with, None without it; _filter_kw: the settings of ops.track_update (a detector
         # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
-        self._gm_kw = self._sg_kw = self._gs_kw = self._tm_kw = self._gc_kw = None
+        self._gm_kw = self._sg_kw = self._gs_kw = self._tm_kw = self._gc_kw = self._ns_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
@@ -270,6 +289,12 @@ class StreamingDetector:
             raise ValueError("grid_scroll scrolls the grid of grid_map: give both")
         if grid_cast is not None and grid_map is None:
             raise ValueError("grid_cast walks the grid of grid_map: give both")
+        if novel_segments is not None:
+            if grid_cast is None or grid_map is None:
+                raise ValueError("novel_segments groups the classes of grid_cast: give both (and grid_map)")
+            if dict(novel_segments).get("gate_map") and self._nms is not None:
+                raise ValueError("novel_segments gate_map with nms_min_dist is not built: the grid map takes one gate, "
+                                 "and merging the segments with the NMS's rows is its own change")
         if track_map is not None and (tracks is None or grid_map is None):
             raise ValueError("track_map joins the tracks of tracks with the grid of grid_map: give both")
         self._cls_thresh = float(cls_thresh)
@@ -386,6 +411,18 @@ class StreamingDetector:
                 self._gc_kw = kw
                 self._gc_out = ops.grid_cast_buffers(self.B, self.N, dev)
                 stages.append(Stage(self._grid_cast_stage))
+                if novel_segments is not None:
+                    # directly behind the cast, whose classes it groups, and in front of the grid map, which it may gate;
+                    # it advances nothing
+                    kw = stage_settings("novel_segments", novel_segments)
+                    if not float(kw["jump"]) > 0.0 or not float(kw["max_width"]) >= 0.0 or int(kw["min_points"]) < 1 or \
+                            not 0 <= int(kw["max_skip"]) <= 64:
+                        raise ValueError("novel_segments: jump must be > 0, max_width >= 0, min_points >= 1 and "
+                                         "max_skip in [0, 64]")
+                    self._ns_gates = bool(kw.pop("gate_map"))
+                    self._ns_kw = dict(kw, cls_thresh=self._cls_thresh)
+                    self._ns_out = ops.novel_segments_buffers(self.B, self.N, dev)
+                    stages.append(Stage(self._novel_segments_stage))
             stages.append(Stage(self._grid_stage, tuple(self._gm_state), self._gm_state.grid.zero_))
         if track_map is not None:
             # behind the track update and the grid map, whose outputs of this step it joins; it runs when the track
@@ -539,13 +576,22 @@ class StreamingDetector:
 
     # Behind the pose launch, on every scan of a sequence: the scan into the grid at this step's pose.
     def _grid_stage(self, first):
+        gate = self._match_gate()
+        if self._ns_kw is not None and self._ns_gates:         # the novelty segments of this scan are not burned in
+            o = self._ns_out
+            gate = dict(instance_mask=o.instance_mask, num_det=o.num_det, det_cls=o.det_cls)
         ops.grid_map_update(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._gm_state,
-                            out=self._gm_out, **self._match_gate(), **self._gm_kw)
+                            out=self._gm_out, **gate, **self._gm_kw)
 
     # Directly in front of the grid map, on every scan of a sequence: the scan the grid predicts, before this scan enters it.
     def _grid_cast_stage(self, first):
         ops.grid_cast(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._gm_state,
                       res=self._gm_kw["res"], out=self._gc_out, **self._match_gate(), **self._gc_kw)
+
+    # Directly behind the grid cast, on every scan of a sequence: its NOVEL points as detections.
+    def _novel_segments_stage(self, first):
+        ops.novel_segments(self._scan[:, 0], self.tab, self._gc_out.point_class, out=self._ns_out,
+                           **self._match_gate(), **self._ns_kw)
 
     # Behind the track update and the grid map of this step: the grid's word on every track's detection, per slot.
     def _track_map_stage(self, first):
@@ -749,6 +795,15 @@ class StreamingDetector:
         if self._gc_kw is None or self._seen < 1:
             raise RuntimeError("construct the detector with grid_cast and feed it a scan first")
         return self._gc_out
+
+    def novel_segments(self):
+        """-> the last step's ``ops.NovelSegments``, device-resident and valid until the next call: instance_mask
+        [B,N], num_det [B], det_xy [B,N,2] (sensor frame) and det_cls [B,N] in the layout of the NMS's results, det_count,
+        det_first, det_last, det_width2 and det_known [B,N] per row and seg_count [B,3].  Needs ``novel_segments`` and
+        one scan.  No synchronisation: the tensors stay on the device."""
+        if self._ns_kw is None or self._seen < 1:
+            raise RuntimeError("construct the detector with novel_segments and feed it a scan first")
+        return self._ns_out
 
     def track_map(self):
         """-> (list with one list per sensor of the live tracks, in slot order as ``tracks()`` has them: dicts of id,

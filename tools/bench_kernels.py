@@ -1,5 +1,5 @@
 """Per-kernel timing on the GPU box (events on torch's current stream, which is the
-stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [gridscroll] [cast] ..."""
+stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [gridscroll] [cast] [novel] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -234,7 +234,7 @@ if "person" in which:
             % (M, ms_tm[M], ms_t[M], (tm_state[M].ev_scans > 0).sum().item() / B,
                tm_out[M].class_count.sum(dim=0).tolist()) for M in tracks))
 
-if "grid" in which or "gridmatch" in which or "gridscroll" in which or "cast" in which:
+if which & {"grid", "gridmatch", "gridscroll", "cast", "novel"}:
     # N12: the occupancy grid map, 450 beams into 512 x 512 cells of 0.1 m per sensor, for 1024, 8 and 1 sensors, next
     # to person_motion on the same scans, NMS results and pose (alternating, three repeats of 50 launches).  The same
     # scan every call, with lo / hi at the int16 limits so that no cell saturates inside the run and every launch
@@ -254,6 +254,10 @@ if "grid" in which or "gridmatch" in which or "gridscroll" in which or "cast" in
     # cast: N16 next to grid_map_update, alternating, on a copy of the grid as two updates left it (every endpoint that
     # is nobody's burned in twice, every cell in front of it freed twice: a map that knows the scene), the same scans,
     # NMS results and pose.  Cell reads: the sum of exp_steps, int16 gathers of one lane each.
+    # novel: N17 next to grid_cast and person_motion, alternating, on the cast sub-command's own map.  That map holds the
+    # scan itself, so the scan cast through it has no NOVEL point; the stage is therefore timed on two sets of classes:
+    # `walkers`, the cast of the same scans with every sixth run of 10 beams pulled to 70 % of its range (somebody in
+    # front of the wall, in space the map saw empty), and `all`, every byte NOVEL -- the most members a scan can have.
     N, H, W, RES = 450, 512, 512, 0.1
     rng = np.random.default_rng(1701)
     tab = ops.phi_table()
@@ -338,6 +342,31 @@ if "grid" in which or "gridmatch" in which or "gridscroll" in which or "cast" in
                          torch.bincount(gc_out.exp_state.flatten().long(), minlength=5).tolist(),
                          gc_out.class_count.sum(dim=0).tolist()))
             del gc_state
+        if "novel" in which:
+            ns_state = ops.GridMapState(gm_state.grid.clone(), gm_state.origin.clone())
+            ns_cast_out, ns_out = ops.grid_cast_buffers(B, N, dev), ops.novel_segments_buffers(B, N, dev)
+            near = scans.clone()
+            pulled = (torch.arange(N, device=dev) // 10) % 6 == 2
+            near[:, pulled] *= 0.7
+            ns_cast = lambda: ops.grid_cast(near, tab, rot, trans, ns_state, res=RES, instance_mask=inst, num_det=num,
+                                            det_cls=dc, out=ns_cast_out)
+            ns_cast()
+            walkers = ns_cast_out.point_class.clone()
+            every = torch.full_like(walkers, 2)
+            for name, classes in (("walkers", walkers), ("all", every)):
+                novel = lambda: ops.novel_segments(near, tab, classes, instance_mask=inst, num_det=num, det_cls=dc,
+                                                   out=ns_out)
+                novel()
+                for rep in range(3):
+                    ms_c, ms_pm, ms_n = timeit(ns_cast, iters=50), timeit(motion, iters=50), timeit(novel, iters=50)
+                    print("novel B=%d N=%d classes=%s: novel_segments %.3f ms (%.2f us per sensor) next to grid_cast %.3f ms "
+                          "and person_motion %.3f ms; per scan %.0f members, %.1f segments, %.1f kept, %.1f few, %.1f wide, "
+                          "%.1f points known to the NMS"
+                          % (B, N, name, ms_n, ms_n / B * 1e3, ms_c, ms_pm, (classes == 2).sum().item() / B,
+                             ns_out.seg_count[:, 0].sum().item() / B, ns_out.num_det.sum().item() / B,
+                             ns_out.seg_count[:, 1].sum().item() / B, ns_out.seg_count[:, 2].sum().item() / B,
+                             ns_out.det_known.sum().item() / B))
+            del ns_state
         for rep in range(3 if "grid" in which else 0):
             ms_g, ms_pm = timeit(grid, iters=50), timeit(motion, iters=50)
             bound = B * 2 * H * W * 2

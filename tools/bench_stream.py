@@ -1,5 +1,5 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-scroll] [--grid-cast] [--track-map]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-scroll] [--grid-cast] [--novel] [--track-map]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
@@ -25,6 +25,9 @@ scan-to-grid match.
 grid_scroll=dict() behind the keyframe launch, so one process gives the map step without and with the scrolling grid.
 --grid-cast (with --grid): one more step in the same process, the keyframe step with grid_map=dict() and
 grid_cast=dict() directly in front of the grid map, so one process gives the map step without and with the ray cast.
+--novel (with --grid; brings the --grid-cast step with it): one more step in the same process, that step with
+novel_segments=dict() directly behind the cast, so one process gives the cast step without and with the novelty
+segments.
 --track-map (with --person-motion --tracks --grid, without --flow; --ego=scan_match|keyframe|keyframe_map chooses the
 pose, keyframe by default): the replayed step with person_motion=dict(), tracks=dict() and grid_map=dict() without and
 with track_map=dict() behind the grid map, alternating repeats in one process.
@@ -54,11 +57,12 @@ GRID = "--grid" in sys.argv
 GRID_MATCH = "--grid-match" in sys.argv
 GRID_SCROLL = "--grid-scroll" in sys.argv
 GRID_CAST = "--grid-cast" in sys.argv
+NOVEL = "--novel" in sys.argv
 TRACK_MAP = "--track-map" in sys.argv
 if TRACK_MAP and not (PERSON_MOTION and TRACKS and GRID and FLOW is None):
     sys.exit("--track-map needs --person-motion --tracks --grid and no --flow")
 EAGER = "--eager" in sys.argv
-sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--track-map", "--person-motion", "--grid", "--eager"))]
+sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--track-map", "--person-motion", "--grid", "--novel", "--eager"))]
 
 
 class DiffFlow(torch.nn.Module):
@@ -93,9 +97,12 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             if GRID_SCROLL:
                 scrolling = mk(ego_motion=KEYFRAME, grid_map=dict(), grid_scroll=dict())
                 steps["keyframe + grid_map + grid_scroll"] = lambda t: scrolling(scans[:, t])
-            if GRID_CAST:
+            if GRID_CAST or NOVEL:
                 casting = mk(ego_motion=KEYFRAME, grid_map=dict(), grid_cast=dict())
                 steps["keyframe + grid_map + grid_cast"] = lambda t: casting(scans[:, t])
+            if NOVEL:
+                grouping = mk(ego_motion=KEYFRAME, grid_map=dict(), grid_cast=dict(), novel_segments=dict())
+                steps["keyframe + grid_map + grid_cast + novel_segments"] = lambda t: grouping(scans[:, t])
             if GRID_MATCH:
                 reckoned, corrected = mk(ego_motion=MATCH, grid_map=dict()), mk(ego_motion=MATCH, grid_map=dict(), grid_match=dict())
                 steps["scan_match + grid_map"] = lambda t: reckoned(scans[:, t])
@@ -181,10 +188,14 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             moved_by, _ = scrolling.grid_scroll()
             print("   grid_scroll at the last scan: shift %s, offset %s" % ([m["shift"].tolist() for m in moved_by],
                                                                              [m["offset"].tolist() for m in moved_by]))
-        if GRID and GRID_CAST:
+        if GRID and (GRID_CAST or NOVEL):
             o = casting.grid_cast()
             print("   grid_cast at the last scan: points per class (none, map, novel, through, unknown) %s, cells read %s"
                   % (o.class_count.tolist(), o.exp_steps.sum(dim=1).tolist()))
+        if GRID and NOVEL:
+            o = grouping.novel_segments()
+            print("   novel_segments at the last scan: segments (all, few, wide) %s, kept %s, NOVEL points %s"
+                  % (o.seg_count.tolist(), o.num_det.tolist(), grouping.grid_cast().class_count[:, 2].tolist()))
         if GRID and GRID_MATCH:
             found, _ = corrected.grid_match()
             print("   grid_match at the last scan: votes %s, score per voting point %s, ok %s, moved %s"
