@@ -118,7 +118,7 @@ def spatial_attention(emb_x: torch.Tensor, emb_t: torch.Tensor, x: torch.Tensor,
 def _(emb_x, emb_t, x, tmpl, alpha, window):
     B, N, _ = emb_x.shape
     w = 2 * int(window / 2) + 1
-    return (torch.empty_like(x), emb_x.new_empty((B, N, w), dtype=torch.float32),
+    return (x.new_empty(x.shape), emb_x.new_empty((B, N, w), dtype=torch.float32),      # contiguous whatever came in
             emb_x.new_empty((B, N, w), dtype=torch.float32))
 
 
@@ -127,15 +127,16 @@ def spatial_attention_backward(emb_x: torch.Tensor, emb_t: torch.Tensor, tmpl: t
                                g_out: torch.Tensor, g_band: Optional[torch.Tensor], alpha: float, window: int
                                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     gb = None if g_band is None else g_band.contiguous().float()
-    dex, det, dx, dt = ops.spatial_attention_backward(emb_x, emb_t, tmpl, prob, g_out.contiguous().float(), gb, alpha,
-                                                      window)
+    # autograd saves the forward's own arguments: strided views arrive here as they went in there
+    dex, det, dx, dt = ops.spatial_attention_backward(emb_x.contiguous(), emb_t.contiguous(), tmpl.contiguous(),
+                                                      prob.contiguous(), g_out.contiguous().float(), gb, alpha, window)
     return dex, det, dx, dt
 
 
 @spatial_attention_backward.register_fake
 def _(emb_x, emb_t, tmpl, prob, g_out, g_band, alpha, window):
-    return (torch.empty_like(emb_x), torch.empty_like(emb_t), torch.empty_like(tmpl, dtype=torch.float32),
-            torch.empty_like(tmpl, dtype=torch.float32))
+    return (emb_x.new_empty(emb_x.shape), emb_t.new_empty(emb_t.shape), tmpl.new_empty(tmpl.shape, dtype=torch.float32),
+            tmpl.new_empty(tmpl.shape, dtype=torch.float32))
 
 
 def _attn_setup(ctx, inputs, output):
