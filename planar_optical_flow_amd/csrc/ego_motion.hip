@@ -268,10 +268,7 @@ extern "C" int pof_ego_motion(const float *ranges, const double *xy, const doubl
     a.huber_delta = huber_delta; a.flow_f64 = flow_f64; a.canonical = canonical; a.sign = sign; a.model = model;
     a.iters = iters; a.N = N; a.motion = motion; a.count = count; a.rms = rms; a.ok = ok;
     a.flow_residual = flow_residual; a.weight_out = weight_out;
-    if (N <= kWaveMaxN)
-        ego_motion_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a);
-    else
-        ego_motion_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a);
+    POF_LAUNCH_PER_SENSOR(ego_motion_kernel, N, B, stream, a);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

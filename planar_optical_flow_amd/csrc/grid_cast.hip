@@ -9,9 +9,8 @@
 //     long as the walk.  Neighbouring lanes read the same cells near the sensor and fan out with range; the trip count
 //     differs per lane, and a wave runs as long as its longest beam.  The per-sensor form of pof_sensor.h (one wave per
 //     sensor, eight beams per lane in series) would make that chain eight walks long and is not used here.
-// (b) grid_cast_counts_kernel, the per-sensor workgroup of pof_sensor.h (one wave up to N = 512, 512 threads up to
-//     4096): the class histogram of the scan and the three counts per detection row, with integer LDS atomics as the
-//     points launch of grid_map.hip counts: integer sums have no order.
+// (b) grid_cast_counts_kernel, the per-sensor workgroup of pof_sensor.h: the class histogram of the scan and the three
+//     counts per detection row, with integer LDS atomics as the points launch of grid_map.hip counts (no order).
 //
 // No global atomics and no floating-point sum: the same bits in every run, at every batch position and in a replay.
 // The walk calls no libm function: multiplies, adds, true divisions and floor.
@@ -23,7 +22,7 @@
 namespace {
 
 using namespace pof_sensor;
-using namespace pof_grid;                       // kMinSide, kMaxSide, kTile
+using namespace pof_grid;
 
 constexpr int kAhead = 4;                       // steps formed, and loads issued, before the first of them is tested
 constexpr int kBeams = 64;                      // beams per workgroup of the walk: one wave
@@ -73,18 +72,20 @@ __global__ __launch_bounds__(kBeams) void grid_cast_walk_kernel(GridCastArgs a, 
     const int b = blockIdx.x / chunks, i = (blockIdx.x - b * chunks) * kBeams + threadIdx.x;
     if (i >= N) return;
     const long long at = (long long)b * N + i;
-    const float *R = a.rot + 4 * (long long)b;
-    const double ux = (a.trans[2 * b] - a.origin[2 * b]) / a.res, uy = (a.trans[2 * b + 1] - a.origin[2 * b + 1]) / a.res;
-    const double cx = floor(ux), cy = floor(uy);
-    const bool inside = cx >= 0.0 && cx < (double)W && cy >= 0.0 && cy < (double)H;      // a NaN is outside
+    const SensorPose pose(a.rot, a.trans, b);
+    const double ux = cell_coord(pose.tx, a.origin[2 * b], a.res), uy = cell_coord(pose.ty, a.origin[2 * b + 1], a.res);
+    const Cell start = {floor(ux), floor(uy)};                 // the sensor's cell
+    const bool inside = start.within(0, H, W);
     const int16_t *grid = a.grid + (long long)b * H * W;
 
     double exp_range = INFINITY, exp_far = INFINITY, free_range = INFINITY;
     int exp_cell = -1, state = inside ? kNone : kOutside, steps = 0;
     if (inside) {
         const double c = a.tab[N + 2 * i], s = a.tab[N + 2 * i + 1];
-        const Axis ax((double)R[0] * c + (double)R[1] * s, ux, cx), ay((double)R[2] * c + (double)R[3] * s, uy, cy);
-        int ix = (int)cx, iy = (int)cy, kx = 0, ky = 0;
+        double dx, dy;
+        pose.rotate(c, s, dx, dy);
+        const Axis ax(dx, ux, start.gx), ay(dy, uy, start.gy);
+        int ix = (int)start.gx, iy = (int)start.gy, kx = 0, ky = 0;
         bool done = false, in_run = false, seen = false;
         const int limit = H + W;                               // every step leaves the start by one cell on one axis
         for (int base = 0; base < limit && !done; base += kAhead) {
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(kBeams) void grid_cast_walk_kernel(GridCastArgs a, 
 
     const double r = (double)a.ranges[at];
     int cls = kClsNone;
-    if (isfinite(r) && r > 0.0 && r < a.max_range && state != kNone && state != kOutside) {
+    if (is_hit(r, a.max_range) && state != kNone && state != kOutside) {
         if (state == kWall && r >= exp_range - a.tol && r <= exp_far + a.tol) cls = kClsMap;
         else if (state == kWall && r > exp_far + a.tol) cls = kClsThrough;
         else if (r + a.tol < exp_range && r < free_range) cls = kClsNovel;
@@ -192,12 +193,10 @@ extern "C" int pof_grid_cast(const float *ranges, const double *tab, const float
     if (!ranges || !tab || !rot || !trans || !grid || !origin || !exp_range || !exp_far || !free_range || !exp_cell ||
         !exp_state || !exp_steps || !point_class || !det_novel || !det_map || !det_through || !class_count)
         return POF_E_BADARG;
-    const int given = (instance_mask != nullptr) + (num_det != nullptr) + (det_cls != nullptr);
-    if (given != 0 && given != 3) return POF_E_BADARG;
+    if (!nms_gate_ok(instance_mask, num_det, det_cls)) return POF_E_BADARG;
     if (!(res > 0.0) || !(max_range > 0.0) || !(tol >= 0.0) || occ_thresh < 1 || free_thresh < 0 || B < 0 || N < 1)
         return POF_E_BADARG;
-    if (N > kGroupMaxN || H < kMinSide || H > kMaxSide || W < kMinSide || W > kMaxSide || H % kTile || W % kTile)
-        return POF_E_SHAPE;
+    if (N > kGroupMaxN || !shape_ok(H, W)) return POF_E_SHAPE;
     const int chunks = (N + kBeams - 1) / kBeams;
     if ((long long)B * chunks > 0x7fffffffLL) return POF_E_SHAPE;
     if (B == 0) return POF_OK;
@@ -210,10 +209,7 @@ extern "C" int pof_grid_cast(const float *ranges, const double *tab, const float
     a.class_count = class_count;
     grid_cast_walk_kernel<<<B * chunks, kBeams, 0, pof_stream(stream)>>>(a, chunks);
     POF_CHECK_LAUNCH();
-    if (N <= kWaveMaxN)
-        grid_cast_counts_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a);
-    else
-        grid_cast_counts_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a);
+    POF_LAUNCH_PER_SENSOR(grid_cast_counts_kernel, N, B, stream, a);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

@@ -1,17 +1,16 @@
 // N12: occupancy grid map, a per-sensor int16 log-odds grid updated per scan.  One entry point, two launches on the
 // caller's stream; include/pof_abi.h has the contract.
 //
-// (a) grid_points_kernel, the per-sensor workgroup of pof_sensor.h (one wave up to N = 512, 512 threads up to 4096, beams
-//     t, t + THREADS, ... per thread): per beam the endpoint in the world frame by N11's expression (SensorPose), its
-//     cell (true division, floor, compared in double), the grid value there as the grid stands -- the cells launch runs
-//     behind it on the stream -- and whether the beam marks its cell (a hit inside the grid that is no person's point,
-//     pof_ego_motion's gate: NmsGate).  det_points / det_free are counted with integer LDS atomics: integer sums have no order.
-// (b) grid_cells_kernel, one workgroup of 256 threads per (sensor, tile of 64 x 64 cells): a row of a tile is one
-//     128-byte line of int16, a thread owns 8 neighbouring cells of a row (one 16-byte load and store) in each of the
-//     two passes of 32 rows.  The tile's hit flags are staged in LDS from point_cell / point_mark (N int32 + N uint8 from
-//     L2; no float64 of the points is redone per tile), the ranges as float32 next to them, and every thread applies the
-//     cell rule to its cells: +hit where a flag is set, else -miss when the cell's beam and its two neighbours all see
-//     past the cell, else nothing.  A thread stores only when one of its 8 cells changed.
+// (a) grid_points_kernel, the per-sensor workgroup of pof_sensor.h: per beam the endpoint in the world frame by N11's
+//     expression (SensorPose), its cell (pof_grid.h's Cell), the grid value there as the grid stands -- the cells launch
+//     runs behind it on the stream -- and whether the beam marks its cell (a hit inside the grid that is no person's
+//     point, pof_ego_motion's gate: NmsGate).  det_points / det_free are counted with integer LDS atomics: integer sums
+//     have no order.
+// (b) grid_cells_kernel, the tile form of pof_grid.h.  The tile's hit flags are staged in LDS from point_cell /
+//     point_mark (N int32 + N uint8 from L2; no float64 of the points is redone per tile), the ranges as float32 next
+//     to them, and every thread applies the cell rule to its cells: +hit where a flag is set, else -miss when the cell's
+//     beam and its two neighbours all see past the cell, else nothing.  A thread stores only when one of its 8 cells
+//     changed.
 //
 // No global atomics and no order-dependent sum: the same bits in every run, at every batch position and in a replay.
 //
@@ -37,7 +36,7 @@
 namespace {
 
 using namespace pof_sensor;
-using namespace pof_grid;                       // the tile form: kTile, kCellThreads, kRun, kMinSide, kMaxSide
+using namespace pof_grid;
 
 struct GridMapArgs {
     const float *ranges;
@@ -71,12 +70,11 @@ __global__ __launch_bounds__(THREADS) void grid_points_kernel(GridMapArgs a)
     pof_lds_order<THREADS>();
     for (int i = tid; i < N; i += THREADS) {
         const double r = (double)a.ranges[row + i];
-        const bool hit = isfinite(r) && r > 0.0 && r < a.max_range;
         double wx, wy;
         pose.point_to_world(r * a.tab[N + 2 * i], r * a.tab[N + 2 * i + 1], wx, wy);
-        const double gx = floor((wx - ox) / a.res), gy = floor((wy - oy) / a.res);
-        const bool inside = hit && gx >= 0.0 && gx < (double)W && gy >= 0.0 && gy < (double)H;    // a NaN is outside
-        const int cell = inside ? (int)gy * W + (int)gx : -1;
+        const Cell g = Cell::of(wx, wy, ox, oy, a.res);
+        const bool inside = is_hit(r, a.max_range) && g.within(0, H, W);
+        const int cell = inside ? g.index(W) : -1;
         const int prior = inside ? (int)grid[cell] : -32768;
         const int id = a.gate.id_of(row, i);
         const int k = a.gate.row_of(id, nd);
@@ -109,12 +107,11 @@ __global__ __launch_bounds__(kCellThreads) void grid_cells_kernel(GridMapArgs a,
     __shared__ float s_r[kGroupMaxN];                          // the scan; only beams inside [0, N) are read
     __shared__ uint8_t s_hit[kTile * kTile];
     const int N = a.N, H = a.H, W = a.W, tid = threadIdx.x;
-    const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
-    const int x0 = (tile % tiles_x) * kTile, y0 = (tile / tiles_x) * kTile;
+    const TileThread me(tiles_x, tiles);
+    const int b = me.b, x0 = me.tx * kTile, y0 = me.ty * kTile, lx0 = me.lx0;
     const long long row = (long long)b * N;
-    const float *R = a.rot + 4 * (long long)b;
-    const double r00 = (double)R[0], r01 = (double)R[1], r10 = (double)R[2], r11 = (double)R[3];
-    const double tx = a.trans[2 * b], ty = a.trans[2 * b + 1];
+    const SensorPose pose(a.rot, a.trans, b);
+    const double tx = pose.tx, ty = pose.ty;
     const double ox = a.origin[2 * b], oy = a.origin[2 * b + 1];
     const double res = a.res, max_range = a.max_range;
 
@@ -123,14 +120,14 @@ __global__ __launch_bounds__(kCellThreads) void grid_cells_kernel(GridMapArgs a,
     {
         const double dxa = (ox + ((double)x0 + 0.5) * res) - tx, dxb = (ox + ((double)(x0 + kTile - 1) + 0.5) * res) - tx;
         const double dya = (oy + ((double)y0 + 0.5) * res) - ty, dyb = (oy + ((double)(y0 + kTile - 1) + 0.5) * res) - ty;
-        const double lbx = corner_bound(r00 * dxa + r10 * dya, r00 * dxa + r10 * dyb, r00 * dxb + r10 * dya,
-                                        r00 * dxb + r10 * dyb);
-        const double lby = corner_bound(r01 * dxa + r11 * dya, r01 * dxa + r11 * dyb, r01 * dxb + r11 * dya,
-                                        r01 * dxb + r11 * dyb);
+        double cx[4], cy[4];                                   // the tile's corners in the sensor frame
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pose.to_sensor(q & 2 ? dxb : dxa, q & 1 ? dyb : dya, cx[q], cy[q]);
+        const double lbx = corner_bound(cx[0], cx[1], cx[2], cx[3]), lby = corner_bound(cy[0], cy[1], cy[2], cy[3]);
         const double rho_lb = sqrt(lbx * lbx + lby * lby);
         can_free = !(rho_lb + a.tol >= max_range);
-        const double ex = fabs(r00) * max_range + fabs(r01) * max_range;
-        const double ey = fabs(r10) * max_range + fabs(r11) * max_range;
+        const double ex = fabs((double)pose.r00) * max_range + fabs((double)pose.r01) * max_range;
+        const double ey = fabs((double)pose.r10) * max_range + fabs((double)pose.r11) * max_range;
         const double gxa = floor(((tx - ex) - ox) / res), gxb = floor(((tx + ex) - ox) / res);
         const double gya = floor(((ty - ey) - oy) / res), gyb = floor(((ty + ey) - oy) / res);
         can_hit = !(gxb < (double)x0 || gxa > (double)(x0 + kTile - 1) || gyb < (double)y0 ||
@@ -153,10 +150,9 @@ __global__ __launch_bounds__(kCellThreads) void grid_cells_kernel(GridMapArgs a,
     __syncthreads();
 
     const double phi0 = a.tab[0], dphi = N > 1 ? a.tab[1] - phi0 : 0.0;
-    const int lx0 = (tid % (kTile / kRun)) * kRun;
-    for (int pass = 0; pass < kTile; pass += kCellThreads / (kTile / kRun)) {
-        const int ly = pass + tid / (kTile / kRun), iy = y0 + ly;
-        int16_t *at = a.grid + ((long long)b * H + iy) * W + x0 + lx0;            // 16-byte aligned
+    for (int pass = 0; pass < kTile; pass += kRowsPerPass) {
+        const int ly = pass + me.ly0, iy = y0 + ly;
+        int16_t *at = a.grid + me.run(H, W, me.tx, me.ty, pass);
         union {
             uint4 q;
             int16_t v[kRun];
@@ -171,7 +167,8 @@ __global__ __launch_bounds__(kCellThreads) void grid_cells_kernel(GridMapArgs a,
                 delta = a.hit;
             } else if (can_free) {
                 const double dx = (ox + ((double)(x0 + lx0 + c) + 0.5) * res) - tx;
-                const double sx = r00 * dx + r10 * dy, sy = r01 * dx + r11 * dy;
+                double sx, sy;
+                pose.to_sensor(dx, dy, sx, sy);
                 const double rho = sqrt(sx * sx + sy * sy);
                 const double t = rint((atan2(sy, sx) - phi0) / dphi);
                 if (t >= 0.0 && t < (double)N) {               // a NaN and an infinity are outside
@@ -215,16 +212,14 @@ extern "C" int pof_grid_map_update(const float *ranges, const double *tab, const
     if (!ranges || !tab || !rot || !trans || !grid || !origin || !point_cell || !point_mark || !point_prior ||
         !det_points || !det_free)
         return POF_E_BADARG;
-    const int given = (instance_mask != nullptr) + (num_det != nullptr) + (det_cls != nullptr);
-    if (given != 0 && given != 3) return POF_E_BADARG;
+    if (!nms_gate_ok(instance_mask, num_det, det_cls)) return POF_E_BADARG;
     if (!(res > 0.0) || !(tol >= 0.0) || !(max_range > 0.0) || hit < 0 || miss < 0 || lo < -32767 || lo > 0 ||
         hi < 0 || hi > 32767 || free_thresh < 0 || B < 0 || N < 1)
         return POF_E_BADARG;
-    if (N > kGroupMaxN || H < kMinSide || H > kMaxSide || W < kMinSide || W > kMaxSide || H % kTile || W % kTile)
-        return POF_E_SHAPE;
+    if (N > kGroupMaxN || !shape_ok(H, W)) return POF_E_SHAPE;
     if (reinterpret_cast<uintptr_t>(grid) % 16) return POF_E_SHAPE;           // the cells launch moves 16 bytes at a time
-    const int tiles_x = W / kTile, tiles = tiles_x * (H / kTile);
-    if ((long long)B * tiles > 0x7fffffffLL) return POF_E_SHAPE;
+    const Tiles tiles(H, W);
+    if (!tiles.fit(B)) return POF_E_SHAPE;
     if (B == 0) return POF_OK;
     GridMapArgs a;
     a.ranges = ranges; a.tab = tab; a.rot = rot; a.trans = trans; a.gate = {instance_mask, num_det, det_cls, cls_thresh};
@@ -232,12 +227,9 @@ extern "C" int pof_grid_map_update(const float *ranges, const double *tab, const
     a.miss = miss; a.lo = lo; a.hi = hi; a.free_thresh = free_thresh; a.N = N; a.H = H; a.W = W; a.grid = grid;
     a.origin = origin; a.point_cell = point_cell; a.point_mark = point_mark; a.point_prior = point_prior;
     a.det_points = det_points; a.det_free = det_free;
-    if (N <= kWaveMaxN)
-        grid_points_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a);
-    else
-        grid_points_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a);
+    POF_LAUNCH_PER_SENSOR(grid_points_kernel, N, B, stream, a);
     POF_CHECK_LAUNCH();
-    grid_cells_kernel<<<B * tiles, kCellThreads, 0, pof_stream(stream)>>>(a, tiles_x, tiles);
+    grid_cells_kernel<<<B * tiles.all, kCellThreads, 0, pof_stream(stream)>>>(a, tiles.x, tiles.all);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

@@ -4,7 +4,7 @@
 //
 // (a) grid_match_scores_kernel, one workgroup of 256 threads per (sensor, rotation).  The N cells of the rotated scan are
 //     staged once in LDS as a packed pair of int16 (g_x, g_y) -- the only float64 work of the launch, N points per
-//     workgroup, by N12's point_cell arithmetic (SensorPose, a true division, floor) behind the rotation of the table
+//     workgroup, by N12's point_cell arithmetic (SensorPose, then pof_grid.h's Cell) behind the rotation of the table
 //     row.  Only points that vote and can reach the grid within R are staged: they are appended through an integer LDS
 //     counter, so the walk below has no sentinel to test (their order differs from run to run; an integer sum has none).
 //     The T T translations are then split over the threads together with the staged points: with S = max(1, 256 / (T T))
@@ -22,16 +22,17 @@
 // No global atomics, integer sums only: the same bits in every run, at every batch position and in a replay.
 #include <cmath>
 
+#include "pof_grid.h"
 #include "pof_sensor.h"
 
 namespace {
 
 using namespace pof_sensor;
+using pof_grid::Cell;
 
 constexpr int kScoreThreads = 256;
 constexpr int kMaxReach = 16, kMaxRotations = 33;
 constexpr int kMaxT = 2 * kMaxReach + 1;
-constexpr int kMinSide = 64, kMaxSide = 2048, kTile = 64;      // N12's rule for H and W
 
 struct GridMatchArgs {
     const float *ranges;
@@ -71,15 +72,14 @@ __global__ __launch_bounds__(kScoreThreads) void grid_match_scores_kernel(GridMa
     __syncthreads();
     for (int i = tid; i < N; i += kScoreThreads) {
         const double r = (double)a.ranges[row + i];
-        if (!(isfinite(r) && r > 0.0 && r < a.max_range) || a.gate.is_person(row, i, nd)) continue;
+        if (!is_hit(r, a.max_range) || a.gate.is_person(row, i, nd)) continue;
         atomicAdd(&s_votes, 1);
         const double px = r * a.tab[N + 2 * i], py = r * a.tab[N + 2 * i + 1];
         double wx, wy;
         pose.point_to_world(ck * px - sk * py, sk * px + ck * py, wx, wy);
-        const double gx = floor((wx - ox) / a.res), gy = floor((wy - oy) / a.res);
-        // within R of the grid, compared in double: a NaN, an infinity and whatever an int could not hold stay out
-        if (gx >= (double)-R && gx < (double)(W + R) && gy >= (double)-R && gy < (double)(H + R))
-            s_cell[atomicAdd(&s_staged, 1)] = (int)((unsigned)(int)gy << 16 | ((unsigned)(int)gx & 0xffffu));
+        const Cell g = Cell::of(wx, wy, ox, oy, a.res);
+        if (g.within(R, H, W))
+            s_cell[atomicAdd(&s_staged, 1)] = (int)((unsigned)(int)g.gy << 16 | ((unsigned)(int)g.gx & 0xffffu));
     }
     __syncthreads();
     const int n = s_staged;
@@ -178,14 +178,12 @@ extern "C" int pof_grid_match(const float *ranges, const double *tab, const int3
     if (!ranges || !tab || !grid || !origin || !rot_tab || !pose || !rot || !trans || !scores || !best || !score ||
         !votes || !ok || !moved || !correction)
         return POF_E_BADARG;
-    const int given = (instance_mask != nullptr) + (num_det != nullptr) + (det_cls != nullptr);
-    if (given != 0 && given != 3) return POF_E_BADARG;
+    if (!nms_gate_ok(instance_mask, num_det, det_cls)) return POF_E_BADARG;
     if (!(res > 0.0) || !(max_range > 0.0) || reach < 0 || reach > kMaxReach || rotations < 1 ||
         rotations > kMaxRotations || rotations % 2 == 0 || min_points < 0 || min_score < 0 || min_gain < 0 || B < 0 ||
         N < 1)
         return POF_E_BADARG;
-    if (N > kGroupMaxN || H < kMinSide || H > kMaxSide || W < kMinSide || W > kMaxSide || H % kTile || W % kTile)
-        return POF_E_SHAPE;
+    if (N > kGroupMaxN || !pof_grid::shape_ok(H, W)) return POF_E_SHAPE;
     if ((long long)B * rotations > 0x7fffffffLL) return POF_E_SHAPE;
     if (B == 0) return POF_OK;
     GridMatchArgs a;

@@ -1,10 +1,8 @@
 // N14: the occupancy grid of N12 scrolls with its sensor, by whole tiles, on the device.  One entry point, two launches
 // on the caller's stream; include/pof_abi.h has the contract.
 //
-// Both launches have grid_cells_kernel's form (pof_grid.h): one workgroup of 256 threads per (sensor, tile of 64 x 64
-// cells), a thread moves 8 neighbouring cells of a row (one 16-byte load and store) in each of the two passes of 32
-// rows.  A shift is a whole number of tiles, so a destination tile has one source tile, wholly inside the grid or wholly
-// outside it, and every row moved is one 128-byte line read and one written.
+// Both launches have the tile form of pof_grid.h.  A shift is a whole number of tiles, so a destination tile has one
+// source tile, wholly inside the grid or wholly outside it, and every row moved is one 128-byte line read and one written.
 // (a) grid_scroll_stage_kernel: every workgroup forms the decision of its sensor from trans, origin and offset -- eight
 //     scalars, all read only in this launch, the same value in every workgroup of the sensor -- and leaves when nothing
 //     moves.  Otherwise it writes its DESTINATION tile into scratch: the source tile of grid, or zeros where that lies
@@ -20,7 +18,6 @@
 // the order of workgroups is not the launch's to choose, so that form is not built.
 #include <cmath>
 
-#include "pof_common.h"
 #include "pof_grid.h"
 
 namespace {
@@ -46,7 +43,7 @@ struct GridScrollArgs {
 // the shift of one axis in tiles: t the sensor, o the origin, side the cells of the axis, off the offset so far
 __device__ __forceinline__ int axis_shift(double t, double o, double res, int margin, int side, int off)
 {
-    const double c = floor((t - o) / res);                      // N12's point_cell arithmetic, a true division
+    const double c = floor(cell_coord(t, o, res));
     if (!(fabs(c) < kMaxCell)) return 0;                        // a NaN and an infinity included
     const int ci = (int)c;
     if (ci >= margin && ci < side - margin) return 0;
@@ -59,38 +56,35 @@ __device__ __forceinline__ int axis_shift(double t, double o, double res, int ma
 __global__ __launch_bounds__(kCellThreads) void grid_scroll_stage_kernel(GridScrollArgs a, int tiles_x, int tiles)
 {
     const int H = a.H, W = a.W, tid = threadIdx.x;
-    const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
+    const TileThread me(tiles_x, tiles);
+    const int b = me.b;
     const int sx = axis_shift(a.trans[2 * b], a.origin[2 * b], a.res, a.margin, W, a.offset[2 * b]);
     const int sy = axis_shift(a.trans[2 * b + 1], a.origin[2 * b + 1], a.res, a.margin, H, a.offset[2 * b + 1]);
-    if (tile == 0 && tid == 0) {
+    if (me.tile == 0 && tid == 0) {
         a.shift[2 * b] = sx;
         a.shift[2 * b + 1] = sy;
         a.scrolled[b] = (sx | sy) != 0 ? 1 : 0;
     }
     if ((sx | sy) == 0) return;
 
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const long long ux = (long long)tx + sx, uy = (long long)ty + sy;          // the source tile
+    const long long ux = (long long)me.tx + sx, uy = (long long)me.ty + sy;    // the source tile
     const bool inside = ux >= 0 && ux < tiles_x && uy >= 0 && uy < tiles / tiles_x;
-    const int lx0 = (tid % (kTile / kRun)) * kRun;
     for (int pass = 0; pass < kTile; pass += kRowsPerPass) {
-        const int ly = pass + tid / (kTile / kRun);
         uint4 cells = make_uint4(0u, 0u, 0u, 0u);                              // unknown
-        if (inside)
-            cells = *reinterpret_cast<const uint4 *>(a.grid + ((long long)b * H + (int)uy * kTile + ly) * W +
-                                                     (int)ux * kTile + lx0);
-        *reinterpret_cast<uint4 *>(a.scratch + ((long long)b * H + ty * kTile + ly) * W + tx * kTile + lx0) = cells;
+        if (inside) cells = *reinterpret_cast<const uint4 *>(a.grid + me.run(H, W, (int)ux, (int)uy, pass));
+        *reinterpret_cast<uint4 *>(a.scratch + me.run(H, W, me.tx, me.ty, pass)) = cells;
     }
 }
 
 __global__ __launch_bounds__(kCellThreads) void grid_scroll_commit_kernel(GridScrollArgs a, int tiles_x, int tiles)
 {
     const int H = a.H, W = a.W, tid = threadIdx.x;
-    const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
+    const TileThread me(tiles_x, tiles);
+    const int b = me.b;
     const int sx = a.shift[2 * b], sy = a.shift[2 * b + 1];
     if ((sx | sy) == 0) return;
 
-    if (tile == 0 && tid == 0) {
+    if (me.tile == 0 && tid == 0) {
         // from base, not accumulated: a sensor that scrolls away and back gets its origin's old bits back
         const int ox = a.offset[2 * b] + sx, oy = a.offset[2 * b + 1] + sy;
         a.offset[2 * b] = ox;
@@ -98,10 +92,8 @@ __global__ __launch_bounds__(kCellThreads) void grid_scroll_commit_kernel(GridSc
         a.origin[2 * b] = a.base[2 * b] + (double)(kTile * ox) * a.res;
         a.origin[2 * b + 1] = a.base[2 * b + 1] + (double)(kTile * oy) * a.res;
     }
-    const int x0 = (tile % tiles_x) * kTile, y0 = (tile / tiles_x) * kTile;
-    const int lx0 = (tid % (kTile / kRun)) * kRun;
     for (int pass = 0; pass < kTile; pass += kRowsPerPass) {
-        const long long at = ((long long)b * H + y0 + pass + tid / (kTile / kRun)) * W + x0 + lx0;
+        const long long at = me.run(H, W, me.tx, me.ty, pass);
         *reinterpret_cast<uint4 *>(a.grid + at) = *reinterpret_cast<const uint4 *>(a.scratch + at);
     }
 }
@@ -115,19 +107,19 @@ extern "C" int pof_grid_scroll(const double *trans, double res, int margin, int 
     POF_CLEAR_STALE_ERROR();
     if (!trans || !grid || !origin || !base || !offset || !scratch || !shift || !scrolled) return POF_E_BADARG;
     if (!(res > 0.0) || margin < 0 || B < 0) return POF_E_BADARG;
-    if (H < kMinSide || H > kMaxSide || W < kMinSide || W > kMaxSide || H % kTile || W % kTile) return POF_E_SHAPE;
+    if (!shape_ok(H, W)) return POF_E_SHAPE;
     // a re-centred sensor stands on tile TW / 2: the bound keeps it outside the margin
     if (margin > kTile * ((W / kTile - 1) / 2) || margin > kTile * ((H / kTile - 1) / 2)) return POF_E_BADARG;
     if (reinterpret_cast<uintptr_t>(grid) % 16 || reinterpret_cast<uintptr_t>(scratch) % 16) return POF_E_SHAPE;
-    const int tiles_x = W / kTile, tiles = tiles_x * (H / kTile);
-    if ((long long)B * tiles > 0x7fffffffLL) return POF_E_SHAPE;
+    const Tiles tiles(H, W);
+    if (!tiles.fit(B)) return POF_E_SHAPE;
     if (B == 0) return POF_OK;
     GridScrollArgs a;
     a.trans = trans; a.res = res; a.margin = margin; a.H = H; a.W = W; a.grid = grid; a.origin = origin; a.base = base;
     a.offset = offset; a.scratch = scratch; a.shift = shift; a.scrolled = scrolled;
-    grid_scroll_stage_kernel<<<B * tiles, kCellThreads, 0, pof_stream(stream)>>>(a, tiles_x, tiles);
+    grid_scroll_stage_kernel<<<B * tiles.all, kCellThreads, 0, pof_stream(stream)>>>(a, tiles.x, tiles.all);
     POF_CHECK_LAUNCH();
-    grid_scroll_commit_kernel<<<B * tiles, kCellThreads, 0, pof_stream(stream)>>>(a, tiles_x, tiles);
+    grid_scroll_commit_kernel<<<B * tiles.all, kCellThreads, 0, pof_stream(stream)>>>(a, tiles.x, tiles.all);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

@@ -301,10 +301,7 @@ int keyframe_launch(const KeyframeArgs &a, const RingT &g, int B, pof_stream_t s
 {
     if (a.N > kGroupMaxN) return POF_E_SHAPE;                  // the limit of pof_scan_match and the NMS
     if (B == 0) return POF_OK;
-    if (a.N <= kWaveMaxN)
-        keyframe_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a, g);
-    else
-        keyframe_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a, g);
+    POF_LAUNCH_PER_SENSOR(keyframe_kernel, a.N, B, stream, a, g);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

@@ -227,8 +227,7 @@ extern "C" int pof_novel_segments(const float *ranges, const double *tab, const 
     if (!ranges || !tab || !point_class || !instance_mask || !num_det || !det_xy || !det_cls || !det_count ||
         !det_first || !det_last || !det_width2 || !det_known || !seg_count)
         return POF_E_BADARG;
-    const int given = (nms_instance_mask != nullptr) + (nms_num_det != nullptr) + (nms_det_cls != nullptr);
-    if (given != 0 && given != 3) return POF_E_BADARG;
+    if (!nms_gate_ok(nms_instance_mask, nms_num_det, nms_det_cls)) return POF_E_BADARG;
     if (!(jump > 0.0) || !(max_width >= 0.0) || min_points < 1 || max_skip < 0 || max_skip > 64 || B < 0 || N < 1)
         return POF_E_BADARG;
     if (N > kGroupMaxN) return POF_E_SHAPE;
@@ -240,10 +239,7 @@ extern "C" int pof_novel_segments(const float *ranges, const double *tab, const 
     a.instance_mask = instance_mask; a.num_det = num_det; a.det_xy = det_xy; a.det_cls = det_cls;
     a.det_count = det_count; a.det_first = det_first; a.det_last = det_last; a.det_width2 = det_width2;
     a.det_known = det_known; a.seg_count = seg_count;
-    if (N <= kWaveMaxN)
-        novel_segments_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a);
-    else
-        novel_segments_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a);
+    POF_LAUNCH_PER_SENSOR(novel_segments_kernel, N, B, stream, a);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

@@ -168,10 +168,7 @@ extern "C" int pof_person_flow(const float *flow_canonical, const double *tab, c
     a.cls_thresh = cls_thresh; a.N = N;
     a.flow_global = flow_global; a.flow_world = flow_world; a.rgb = rgb; a.det_xy_world = det_xy_world;
     a.det_flow = det_flow; a.det_rgb = det_rgb; a.det_count = det_count; a.det_valid = det_valid;
-    if (N <= kWaveMaxN)
-        person_flow_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a);
-    else
-        person_flow_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a);
+    POF_LAUNCH_PER_SENSOR(person_flow_kernel, N, B, stream, a);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

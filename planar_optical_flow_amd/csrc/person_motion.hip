@@ -268,10 +268,7 @@ extern "C" int pof_person_motion(const float *ranges, const double *tab, const i
     a.reach = reach; a.min_points = min_points; a.N = N; a.prev_centre = prev_centre; a.prev_cand = prev_cand;
     a.prev_num = prev_num; a.det_xy_world = det_xy_world; a.det_flow = det_flow; a.det_centre = det_centre;
     a.det_count = det_count; a.det_valid = det_valid; a.det_prev = det_prev;
-    if (N <= kWaveMaxN)
-        person_motion_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a);
-    else
-        person_motion_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a);
+    POF_LAUNCH_PER_SENSOR(person_motion_kernel, N, B, stream, a);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

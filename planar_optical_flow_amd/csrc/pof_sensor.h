@@ -1,5 +1,6 @@
-// What the per-scan stages behind the detector trunk share: one workgroup per sensor.  pof_icp.h (N8-N10),
-// ego_motion.hip (N6), person_flow.hip (N5), person_motion.hip (N11) and the points launch of grid_map.hip (N12).
+// What the per-scan stages behind the detector trunk share: one workgroup per sensor.  person_flow (N5), ego_motion (N6),
+// pof_icp.h (N8-N10), person_motion (N11), the points launch of grid_map (N12), track_map (N15), the counts launch of
+// grid_cast (N16) and novel_segments (N17); grid_match (N13) and grid_cast's walk take gate, pose and hit rule only.
 //
 // Workgroup b owns sensor b.  Thread t holds the entries t, t + THREADS, ... of the sensor -- points, or detection
 // rows -- in kSlots register slots: slot c of thread t is entry t + THREADS * c, so a load or store over t is coalesced
@@ -23,6 +24,14 @@ constexpr int kWaveMaxN = 64 * kSlots;
 constexpr int kGroupThreads = 512;
 constexpr int kGroupMaxN = kGroupThreads * kSlots;
 constexpr int kChunk = 512;                // points staged in LDS at a time
+
+// The two launch forms of a kernel template `kernel<THREADS>`, one workgroup per sensor on the stream.  A macro: the
+// kernel is a template name.
+#define POF_LAUNCH_PER_SENSOR(kernel, N, B, stream, ...)                                                           \
+    do {                                                                                                           \
+        if ((N) <= pof_sensor::kWaveMaxN) kernel<64><<<B, 64, 0, pof_stream(stream)>>>(__VA_ARGS__);               \
+        else kernel<pof_sensor::kGroupThreads><<<B, pof_sensor::kGroupThreads, 0, pof_stream(stream)>>>(__VA_ARGS__); \
+    } while (0)
 
 // a count inside [0, N], one value for the workgroup: loop bounds and tests on it are scalar
 __device__ __forceinline__ int clamped_count(int nd, int N)
@@ -62,6 +71,16 @@ struct NmsGate {
     }
 };
 
+// the NMS results come together or not at all; a launcher answers POF_E_BADARG without it
+inline bool nms_gate_ok(const int32_t *instance_mask, const int32_t *num_det, const double *det_cls)
+{
+    const int given = (instance_mask != nullptr) + (num_det != nullptr) + (det_cls != nullptr);
+    return !(given != 0 && given != 3);
+}
+
+// a beam with an endpoint the map stages use: a NaN, an infinity, 0 and whatever reaches max_range have none
+__device__ __forceinline__ bool is_hit(double r, double max_range) { return isfinite(r) && r > 0.0 && r < max_range; }
+
 // The pose terms of sensor b (pof_write_pose_terms): rot[b] row-major in float, trans[b]; the ABI's two expressions.
 struct SensorPose {
     float r00, r01, r10, r11;
@@ -74,11 +93,23 @@ struct SensorPose {
         tx = trans[2 * b], ty = trans[2 * b + 1];
     }
 
-    // a scan point p = r (cos, sin): two roundings per product and sum, no fma
+    // a direction in the sensor frame to the world frame: two roundings per product and sum, no fma
+    __device__ __forceinline__ void rotate(double px, double py, double &wx, double &wy) const
+    {
+        wx = (double)r00 * px + (double)r01 * py, wy = (double)r10 * px + (double)r11 * py;
+    }
+
+    // a difference of world points to the sensor frame: the transpose
+    __device__ __forceinline__ void to_sensor(double dx, double dy, double &sx, double &sy) const
+    {
+        sx = (double)r00 * dx + (double)r10 * dy, sy = (double)r01 * dx + (double)r11 * dy;
+    }
+
+    // a scan point p = r (cos, sin)
     __device__ __forceinline__ void point_to_world(double px, double py, double &wx, double &wy) const
     {
-        wx = ((double)r00 * px + (double)r01 * py) + tx;
-        wy = ((double)r10 * px + (double)r11 * py) + ty;
+        rotate(px, py, wx, wy);
+        wx += tx, wy += ty;
     }
 
     // a detection centre d (det_xy_world): the only fma of these stages

@@ -119,10 +119,7 @@ extern "C" int pof_scan_match(const float *ranges_prev, const float *ranges_cur,
     a.ranges_prev = ranges_prev; a.init = init; a.N = N;
     a.motion = motion; a.count = count; a.rms = rms; a.ok = ok; a.iters_used = iters_used; a.obs = obs; a.corr = corr;
     a.flow_residual = flow_residual;
-    if (N <= kWaveMaxN)
-        scan_match_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a);
-    else
-        scan_match_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a);
+    POF_LAUNCH_PER_SENSOR(scan_match_kernel, N, B, stream, a);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

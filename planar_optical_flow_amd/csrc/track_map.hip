@@ -1,5 +1,5 @@
 // N15: map-checked tracks, per-track evidence from the occupancy grid.  One launch per batch in the per-sensor workgroup
-// form of pof_sensor.h (one wave up to N = 512, 512 threads up to 4096); include/pof_abi.h has the contract.
+// form of pof_sensor.h; include/pof_abi.h has the contract.
 //
 // The detection row of the NMS is a rank that changes with every scan; only the track slot carries identity.  The
 // launch joins what pof_grid_map_update says about the row a track was matched with (det_points, det_free, and how many
@@ -184,10 +184,7 @@ extern "C" int pof_track_map(const int32_t *instance_mask, const int32_t *num_de
     a.track_class = track_class; a.det_class = det_class; a.point_class = point_class; a.class_count = class_count;
     a.occ_thresh = occ_thresh; a.free_pct = free_pct; a.occ_pct = occ_pct; a.min_points = min_points;
     a.min_scans = min_scans; a.cap = cap; a.travel = travel;
-    if (N <= kWaveMaxN)
-        track_map_kernel<64><<<B, 64, 0, pof_stream(stream)>>>(a);
-    else
-        track_map_kernel<kGroupThreads><<<B, kGroupThreads, 0, pof_stream(stream)>>>(a);
+    POF_LAUNCH_PER_SENSOR(track_map_kernel, N, B, stream, a);
     POF_CHECK_LAUNCH();
     return POF_OK;
 }

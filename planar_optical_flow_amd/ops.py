@@ -1049,10 +1049,14 @@ def person_flow(flow_canonical, tab, instance_mask, num_det, det_xy, det_cls, ro
     return out
 
 
-def _nms_gate(instance_mask, num_det, det_cls, B=None, N=None):
+def _nms_gate(instance_mask, num_det, det_cls, B=None, N=None, strict=False):
     """The NMS results that gate people out of a fit.  Without B and N (before any tensor is looked at): only that
-    instance_mask comes with the other two.  With them -> the three tensors, checked, or three Nones."""
+    instance_mask comes with the other two.  With them -> the three tensors, checked, or three Nones.  ``strict``
+    refuses a num_det or det_cls that would pass unused, without an instance_mask: for the stages that also report per
+    detection (the map stages)."""
     if instance_mask is None:
+        if strict and (num_det is not None or det_cls is not None):
+            raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
         return None, None, None
     if num_det is None or det_cls is None:
         raise ValueError("instance_mask needs num_det and det_cls (the NMS results)")
@@ -1073,6 +1077,34 @@ def _check_pose_terms(B, rot, trans, flow_trans):
     for t, name in ((trans, "trans"), (flow_trans, "flow_trans")):
         if t is not None and tuple(_dev(t, torch.float64, name).shape) != (B, 2):
             raise ValueError("%s must be [B,2]" % name)
+
+
+def _pose_input(B, rot, trans, *pose):
+    """The pose terms a stage cannot do without, checked: rot and trans, and pose [B,3] where the stage takes one."""
+    if rot is None or trans is None or any(p is None for p in pose):
+        raise TypeError("%s must be tensors on the HIP device (no CPU path)"
+                        % ("rot, trans and pose" if pose else "rot and trans"))
+    _check_pose_terms(B, rot, trans, None)
+    if pose and tuple(_dev(pose[0], torch.float64, "pose").shape) != (B, 3):
+        raise ValueError("pose must be [B,3]")
+
+
+def _grid_state(state, B):
+    """A caller's ``GridMapState`` for B sensors, checked -> (state, H, W)."""
+    state = GridMapState(*state)
+    if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
+        raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
+    H, W = state.grid.shape[1:]
+    return _checked(GridMapState, state, "state", B=B, H=H, W=W), H, W
+
+
+def grid_shape(size):
+    """The (H, W) of an occupancy grid from a ``size`` setting, one number or a pair: multiples of 64 in [64, 2048],
+    the launchers' rule (csrc/pof_grid.h), or this raises.  What wraps a map stage checks its setting here."""
+    shape = tuple(int(s) for s in ((size, size) if np.ndim(size) == 0 else size))
+    if len(shape) != 2 or any(s % 64 or not 64 <= s <= 2048 for s in shape):
+        raise ValueError("size must be a multiple of 64 in [64, 2048] (or two of them, (H, W))")
+    return shape
 
 
 def _check_matcher_settings(window, iters, **not_negative):
@@ -1488,9 +1520,7 @@ def person_motion(ranges, tab, instance_mask, num_det, det_xy, det_cls, rot, tra
     of preallocated tensors (``person_motion_buffers``)."""
     ranges, tab, B, N, dev = _scan_input(ranges, tab)
     instance_mask, num_det, det_xy, det_cls = _nms_results(instance_mask, num_det, det_xy, det_cls, B, N)
-    if rot is None or trans is None:
-        raise TypeError("rot and trans must be tensors on the HIP device (no CPU path)")
-    _check_pose_terms(B, rot, trans, None)
+    _pose_input(B, rot, trans)
     state = _checked(PersonMotionState, state, "state", B=B, N=N)
     out = _out_of(PersonMotion, out, dev, B=B, N=N)
     if B == 0:
@@ -1552,19 +1582,9 @@ def grid_map_update(ranges, tab, rot, trans, state, *, res, instance_mask=None, 
     of them lie on cells that held <= -``free_thresh``; zeros without the NMS results).  The same bits in every run.
     ``out``: a ``GridMapOut`` of preallocated tensors (``grid_map_buffers``)."""
     ranges, tab, B, N, dev = _scan_input(ranges, tab)
-    if rot is None or trans is None:
-        raise TypeError("rot and trans must be tensors on the HIP device (no CPU path)")
-    _check_pose_terms(B, rot, trans, None)
-    # stricter than _nms_gate, which lets num_det and det_cls pass (unused) without an instance_mask: this stage also
-    # reports per detection, so the three come together or not at all
-    if instance_mask is None and (num_det is not None or det_cls is not None):
-        raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
-    gate = _nms_gate(instance_mask, num_det, det_cls, B, N)
-    state = GridMapState(*state)
-    if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
-        raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
-    H, W = state.grid.shape[1:]
-    state = _checked(GridMapState, state, "state", B=B, H=H, W=W)
+    _pose_input(B, rot, trans)
+    gate = _nms_gate(instance_mask, num_det, det_cls, B, N, strict=True)
+    state, H, W = _grid_state(state, B)
     out = _out_of(GridMapOut, out, dev, B=B, N=N)
     if B == 0:
         return out
@@ -1624,19 +1644,9 @@ def grid_match(ranges, tab, rot, trans, pose, state, *, res, table=None, instanc
     f64 = (dx res, dy res, theta), zeros without ``moved``.  The same bits in every run.  ``out``: a ``GridMatch`` of
     preallocated tensors (``grid_match_buffers``)."""
     ranges, tab, B, N, dev = _scan_input(ranges, tab)
-    if rot is None or trans is None or pose is None:
-        raise TypeError("rot, trans and pose must be tensors on the HIP device (no CPU path)")
-    _check_pose_terms(B, rot, trans, None)
-    if tuple(_dev(pose, torch.float64, "pose").shape) != (B, 3):
-        raise ValueError("pose must be [B,3]")
-    if instance_mask is None and (num_det is not None or det_cls is not None):
-        raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
-    gate = _nms_gate(instance_mask, num_det, det_cls, B, N)
-    state = GridMapState(*state)
-    if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
-        raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
-    H, W = state.grid.shape[1:]
-    state = _checked(GridMapState, state, "state", B=B, H=H, W=W)
+    _pose_input(B, rot, trans, pose)
+    gate = _nms_gate(instance_mask, num_det, det_cls, B, N, strict=True)
+    state, H, W = _grid_state(state, B)
     _check_search(reach, rotations)
     if table is None:
         table = grid_match_table(rot_step, rotations, dev)
@@ -1711,11 +1721,7 @@ def grid_scroll(trans, state, scroll, *, res, margin=None, out=None):
     if trans.dim() != 2 or trans.shape[1] != 2:
         raise ValueError("trans must be [B,2]")
     B, dev = trans.shape[0], trans.device
-    state = GridMapState(*state)
-    if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
-        raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
-    H, W = state.grid.shape[1:]
-    state = _checked(GridMapState, state, "state", B=B, H=H, W=W)
+    state, H, W = _grid_state(state, B)
     scroll = _checked(GridScrollState, scroll, "scroll", B=B, H=H, W=W)
     out = _out_of(GridScroll, out, dev, B=B)
     if B == 0:
@@ -1835,18 +1841,9 @@ def grid_cast(ranges, tab, rot, trans, state, *, res, instance_mask=None, num_de
     det_through [B,N] i32 per detection row (zeros without the NMS results), class_count [B,5] i32.  N <= 4096.  The
     same bits in every run.  ``out``: a ``GridCast`` of preallocated tensors (``grid_cast_buffers``)."""
     ranges, tab, B, N, dev = _scan_input(ranges, tab)
-    if rot is None or trans is None:
-        raise TypeError("rot and trans must be tensors on the HIP device (no CPU path)")
-    _check_pose_terms(B, rot, trans, None)
-    # as grid_map_update: the stage reports per detection, so the three come together or not at all
-    if instance_mask is None and (num_det is not None or det_cls is not None):
-        raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
-    gate = _nms_gate(instance_mask, num_det, det_cls, B, N)
-    state = GridMapState(*state)
-    if not isinstance(state.grid, torch.Tensor) or state.grid.dim() != 3:
-        raise TypeError("state.grid must be a [B,H,W] tensor on the HIP device (no CPU path)")
-    H, W = state.grid.shape[1:]
-    state = _checked(GridMapState, state, "state", B=B, H=H, W=W)
+    _pose_input(B, rot, trans)
+    gate = _nms_gate(instance_mask, num_det, det_cls, B, N, strict=True)
+    state, H, W = _grid_state(state, B)
     out = _out_of(GridCast, out, dev, B=B, N=N)
     if B == 0:
         return out
@@ -1891,9 +1888,7 @@ def novel_segments(ranges, tab, point_class, *, instance_mask=None, num_det=None
     point_class = _dev(point_class, torch.uint8, "point_class")
     if tuple(point_class.shape) != (B, N):
         raise ValueError("point_class must be [B,N]")
-    if instance_mask is None and (num_det is not None or det_cls is not None):
-        raise ValueError("instance_mask, num_det and det_cls (the NMS results) come together or not at all")
-    gate = _nms_gate(instance_mask, num_det, det_cls, B, N)
+    gate = _nms_gate(instance_mask, num_det, det_cls, B, N, strict=True)
     out = _out_of(NovelSegments, out, dev, B=B, N=N)
     if B == 0:
         return out

@@ -607,12 +607,10 @@ class OccupancyGrid:
         self._min_dist = kw.pop("min_dist", 0.5)
         self._scroll_kw = None if scroll is None else dict(_stage_kw(ops.grid_scroll, "scroll", dict(scroll), "res"))
         _stage_kw(ops.grid_map_update, "grid_map", kw, "res")
-        H, W = (size, size) if np.ndim(size) == 0 else size
-        self.res, self.shape = float(res), (int(H), int(W))
+        self.res = float(res)
         if not self.res > 0.0:
             raise ValueError("res must be > 0")
-        if any(s % 64 or not 64 <= s <= 2048 for s in self.shape):
-            raise ValueError("size must be a multiple of 64 in [64, 2048]")
+        self.shape = ops.grid_shape(size)
         if self._scroll_kw is not None:
             ops.grid_scroll_margin(*self.shape, self._scroll_kw.get("margin"))
         self._kw = kw

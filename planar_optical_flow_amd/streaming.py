@@ -350,7 +350,7 @@ class StreamingDetector:
             # allocated below, so the stage reads self._gm_state when it runs; the grid and its origin are in the grid
             # stage's snapshot, base and offset in this one's
             self._gs_kw = stage_settings("grid_scroll", grid_scroll)
-            shape = self._grid_shape(stage_settings("grid_map", grid_map)["size"])
+            shape = ops.grid_shape(stage_settings("grid_map", grid_map)["size"])
             ops.grid_scroll_margin(*shape, self._gs_kw["margin"])
             self._gs_state = ops.grid_scroll_state(self.B, *shape, dev)
             self._gs_out = ops.grid_scroll_buffers(self.B, dev)
@@ -393,7 +393,7 @@ class StreamingDetector:
                                 lambda: ops.track_reset(self._track_state), from_first=person_motion is not None))
         if grid_map is not None:
             kw = stage_settings("grid_map", grid_map)
-            shape = self._grid_shape(kw.pop("size"))
+            shape = ops.grid_shape(kw.pop("size"))
             if not float(kw["res"]) > 0.0:
                 raise ValueError("grid_map res must be > 0")
             self._gm_kw = dict(kw, cls_thresh=self._cls_thresh)
@@ -442,13 +442,6 @@ class StreamingDetector:
             # not in a warm-up: the captured step behind it reads the scan before this one
             stages.append(Stage(self._keep_scan, warm_up=False))
         self._stages = tuple(stages)
-
-    @staticmethod
-    def _grid_shape(size):
-        shape = tuple(int(s) for s in ((size, size) if np.ndim(size) == 0 else size))
-        if len(shape) != 2 or any(s % 64 or not 64 <= s <= 2048 for s in shape):
-            raise ValueError("grid_map size must be a multiple of 64 in [64, 2048] (or two of them, (H, W))")
-        return shape
 
     def _alloc_pose_terms(self, dev):
         # trans | flow_trans | rot of every sensor in one buffer: one small copy per scan from a pinned staging

@@ -105,3 +105,48 @@ def test_settings_and_defaults_have_one_source():
         unknown = "cls_thresh" if arg in ("person_motion", "grid_map") else "no_such_setting"
         with pytest.raises(ValueError, match="unknown %s settings" % arg):
             streaming.stage_settings(arg, {unknown: 0.5}, 0.7, method)
+
+
+def test_grid_shape_is_the_rule_of_the_four_launchers():
+    """``ops.grid_shape`` (what the detector and ``OccupancyGrid`` check a ``size`` with) and the launchers' shape rule
+    (csrc/pof_grid.h) accept the same sides.  B = 0: a launcher returns in front of any launch, so no pointer is
+    followed and no GPU is needed; every other argument is legal, so POF_E_SHAPE can only come from H and W."""
+    import ctypes
+    import os
+    from planar_optical_flow_amd import _lib, build
+    if not os.path.exists(_lib.LIB_PATH) and not os.path.exists(build.HIPCC):
+        pytest.skip("the library is not built and there is no hipcc to build it")
+    build.build(verbose=False)
+    lib = _lib.load()
+    buf = (ctypes.c_char * 32)()
+    word = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)     # non-null and 16-byte aligned
+
+    def w(n):
+        return [word] * n
+
+    launchers = {
+        "pof_grid_map_update": lambda H, W: lib.pof_grid_map_update(*w(7), 0.1, 0.1, 20.0, 0.5, 17, 8, -40, 70, 16, 0, 8,
+                                                                    H, W, *w(7), None),
+        "pof_grid_match": lambda H, W: lib.pof_grid_match(*w(5), 0.5, 20.0, word, word, 0.1, word, 4, 9, 50, 20, 8, 0, 8,
+                                                          H, W, *w(10), None),
+        "pof_grid_scroll": lambda H, W: lib.pof_grid_scroll(word, 0.1, 0, 0, H, W, *w(7), None),
+        "pof_grid_cast": lambda H, W: lib.pof_grid_cast(*w(9), 0.1, 20.0, 0.1, 17, 16, 0, 8, H, W, *w(11), None),
+    }
+    seen = set()
+    for side in (-64, 0, 32, 63, 64, 96, 128, 2048, 2112, 4096):
+        for H, W in ((side, 64), (64, side)):
+            try:
+                assert ops.grid_shape((H, W)) == (H, W)
+                want = _lib.POF_OK
+            except ValueError:
+                want = _lib.POF_E_SHAPE
+            seen.add(want)
+            for name, call in launchers.items():
+                assert call(H, W) == want, (name, H, W)
+        # one number is the square of it
+        if want == _lib.POF_OK:
+            assert ops.grid_shape(side) == (side, side)
+        else:
+            with pytest.raises(ValueError):
+                ops.grid_shape(side)
+    assert seen == {_lib.POF_OK, _lib.POF_E_SHAPE}
