@@ -883,6 +883,57 @@ int pof_novel_segments(const float *ranges, const double *tab, const uint8_t *po
                        int32_t *seg_count, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N18 merged detections: two detection records made one.  N17's segments and the NMS's rows are both records in the
+ * layout of pof_nms_predicted_center's results; the person stages (pof_person_motion, pof_track_update, pof_track_map)
+ * and the gate of pof_grid_map_update take one.  This stage appends to the primary record A (the NMS's) the rows of
+ * the secondary record B (the segments') that A's confident detections do not already hold, and hands every point to
+ * one row.  The reference has nothing of the kind; the specification is this comment (restated in NumPy by
+ * tests/test_merge_detections.py).  One sensor per batch entry, one launch, the per-sensor workgroup of pof_sensor.h:
+ * one wave up to N = 512, 512 threads up to N = 4096, chosen by the launcher from N alone.  No state.
+ * Inputs: B, the secondary record, b_instance_mask [B][N] int32, b_num_det [B] int32, b_det_xy [B][N][2] float64,
+ *   b_det_cls [B][N] float64, all required; A, the primary record, a_instance_mask, a_num_det, a_det_xy, a_det_cls of the
+ *   same shapes, all four or none (NULL: an empty A).  Settings: cls_thresh; absorb_pct, an int in [0, 101] (50).
+ *   nA and nB are a_num_det and b_num_det clamped to [0, N] (nA = 0 without A).
+ * Everything is integers and bitwise copies: no floating-point arithmetic except the compare a_det_cls >= cls_thresh.
+ *   CONFIDENT.  Point i is confident when its A id a_instance_mask[i] is in [1, nA] and a_det_cls[id - 1] >= cls_thresh
+ *     (pof_person_flow's det_valid, the gate of the map stages); a NaN score is not confident.
+ *   MEMBERS.  Point i is a member of B row k < nB when b_instance_mask[i] == k + 1; any other id belongs to no row.  Per
+ *     B row, b_count[k] is the number of its members and b_known[k] the number of its members that are confident.
+ *   ABSORBED.  B row k is absorbed when b_count[k] == 0 or 100 b_known[k] >= absorb_pct b_count[k] (in int32: N <= 4096).
+ *     absorb_pct = 0 absorbs every row, absorb_pct = 101 only the empty ones.
+ *   ROWS.  Merged rows 0 .. nA - 1 are A's rows, det_xy and det_cls bit for bit (negative zero and NaN payloads
+ *     included).  The B rows that are not absorbed are appended in ascending k at the rows nA, nA + 1, ... while the row
+ *     index is < N; a row that would land at or beyond N is dropped.  An appended row's det_xy and det_cls are B's, bit
+ *     for bit.
+ *   MASK.  instance_mask[i] is the appended row + 1 when i is a member of an appended B row and i is not confident;
+ *     otherwise a_instance_mask[i] when that is in [1, nA], else 0.  So a confident detection keeps all its points, an
+ *     unconfident A row loses the points an appended row claims, and the members of absorbed and dropped rows stay with
+ *     A.
+ * Outputs, the first four with the dtypes, shapes and meaning of pof_nms_predicted_center's results, in the argument
+ *   order of pof_person_motion; every per-row field is zero in the rows at and beyond num_det (b_count and b_known: at
+ *   and beyond nB), except b_row, which is -1 at and beyond nB:
+ *   instance_mask [B][N] int32  the merged id per point
+ *   num_det       [B]    int32  nA + the appended rows
+ *   det_xy     [B][N][2] float64, det_cls [B][N] float64  the rows
+ *   det_points    [B][N] int32  the points that carry the row's id in the merged mask
+ *   det_src       [B][N] uint8  1 = the row is A's, 2 = B's
+ *   det_row       [B][N] int32  the row's index in its own record
+ *   b_row         [B][N] int32  per B row its merged row; -1 absorbed, -2 dropped
+ *   b_count, b_known [B][N] int32  per B row
+ *   merge_count   [B][4] int32  nA, appended, absorbed, dropped (the last three sum to nB)
+ * Integer counts use LDS atomics; no global atomics: the same bits in every run, at every batch position and in a
+ * graph replay.
+ * POF_E_BADARG (checked first; nothing written): a NULL required pointer, A pointers given in part, absorb_pct outside
+ *   [0, 101], B < 0, N < 1.  POF_E_SHAPE (nothing written): N > 4096.  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_merge_detections(const int32_t *b_instance_mask, const int32_t *b_num_det, const double *b_det_xy,
+                         const double *b_det_cls, const int32_t *a_instance_mask, const int32_t *a_num_det,
+                         const double *a_det_xy, const double *a_det_cls, double cls_thresh, int absorb_pct, int B, int N,
+                         int32_t *instance_mask, int32_t *num_det, double *det_xy, double *det_cls, int32_t *det_points,
+                         uint8_t *det_src, int32_t *det_row, int32_t *b_row, int32_t *b_count, int32_t *b_known,
+                         int32_t *merge_count, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A12 flow_loss / loss_fn_eval
  *   src/depracted/model/prototype.py:27-32, src/depracted/model/dr_spaam.py:22-27,
  *   src/utils/eval_utils.py:129-134

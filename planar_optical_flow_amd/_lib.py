@@ -63,6 +63,7 @@ SIGNATURES = {
     "pof_track_map": (_i, [_p] * 9 + [_i] * 3 + [_p] * 12 + [_i] * 5 + [_d, _i, _p]),
     "pof_grid_cast": (_i, [_p] * 9 + [_d] * 3 + [_i] * 6 + [_p] * 12),
     "pof_novel_segments": (_i, [_p] * 6 + [_d, _d, _i, _i, _d, _i, _i] + [_p] * 11),
+    "pof_merge_detections": (_i, [_p] * 8 + [_d, _i, _i, _i] + [_p] * 12),
     "pof_flow_errors": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "pof_band_correlation": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pof_band_correlation_f16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),

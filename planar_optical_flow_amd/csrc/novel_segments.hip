@@ -43,37 +43,6 @@ struct NovelArgs {
     int32_t *det_known, *seg_count;
 };
 
-// exclusive prefix of v over the workgroup in thread order, total = the sum; s_part: THREADS / 64 ints
-template <int THREADS>
-__device__ __forceinline__ int group_exclusive(int v, int *s_part, int &total)
-{
-    const int lane = threadIdx.x & 63;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
-    if (THREADS == 64) {
-        total = __shfl(incl, 63, 64);
-        return incl - v;
-    }
-    constexpr int kWaves = THREADS / 64;
-    const int wave = threadIdx.x >> 6;
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const int p = s_part[w];
-        if (w < wave) before += p;
-        sum += p;
-    }
-    __syncthreads();                                           // the next call writes s_part
-    total = sum;
-    return before + incl - v;
-}
-
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void novel_segments_kernel(NovelArgs a)
 {

@@ -1,6 +1,6 @@
 // What the per-scan stages behind the detector trunk share: one workgroup per sensor.  person_flow (N5), ego_motion (N6),
 // pof_icp.h (N8-N10), person_motion (N11), the points launch of grid_map (N12), track_map (N15), the counts launch of
-// grid_cast (N16) and novel_segments (N17); grid_match (N13) and grid_cast's walk take gate, pose and hit rule only.
+// grid_cast (N16), novel_segments (N17) and merge_detections (N18); grid_match (N13) and grid_cast's walk take gate, pose and hit rule only.
 //
 // Workgroup b owns sensor b.  Thread t holds the entries t, t + THREADS, ... of the sensor -- points, or detection
 // rows -- in kSlots register slots: slot c of thread t is entry t + THREADS * c, so a load or store over t is coalesced
@@ -119,6 +119,37 @@ struct SensorPose {
         oy = fma(d1, (double)r11, d0 * (double)r10) + ty;
     }
 };
+
+// exclusive prefix of v over the workgroup in thread order, total = the sum; s_part: THREADS / 64 ints
+template <int THREADS>
+__device__ __forceinline__ int group_exclusive(int v, int *s_part, int &total)
+{
+    const int lane = threadIdx.x & 63;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += u;
+    }
+    if (THREADS == 64) {
+        total = __shfl(incl, 63, 64);
+        return incl - v;
+    }
+    constexpr int kWaves = THREADS / 64;
+    const int wave = threadIdx.x >> 6;
+    if (lane == 63) s_part[wave] = incl;
+    __syncthreads();
+    int before = 0, sum = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        const int p = s_part[w];
+        if (w < wave) before += p;
+        sum += p;
+    }
+    __syncthreads();                                           // the next call writes s_part
+    total = sum;
+    return before + incl - v;
+}
 
 // An empty statement the compiler may not speculate: a block that holds it stays behind its branch.  Without it the
 // wave-uniform tests on the register slot become selects and the float64 work of all kSlots slots runs for every entry.

@@ -920,7 +920,7 @@ def nms_predicted_center(ranges, tab, pred_cls, pred_reg, min_dist=0.5):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The per-scan stages N5-N17.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
+# The per-scan stages N5-N18.  Each keeps its tensors in records: a namedtuple class declared once by ``_record``, with
 # a dtype and a symbolic shape per field.  ``_zeros_of`` allocates a record, ``_checked`` takes a caller's and
 # ``_out_of`` does whichever an ``out=`` needs; ``stage_settings`` reads a wrapper's tunable scalars off its signature.
 def _record(name, persistent=None, **fields):
@@ -965,7 +965,7 @@ def _out_of(cls, out, device, **sizes):
     return _zeros_of(cls, device, **sizes) if out is None else _checked(cls, out, "out", **sizes)
 
 
-_STAGE_TENSORS = frozenset(("init", "xy", "weight", "instance_mask", "num_det", "det_cls", "out", "rot", "trans",
+_STAGE_TENSORS = frozenset(("init", "xy", "weight", "instance_mask", "num_det", "det_xy", "det_cls", "out", "rot", "trans",
                             "flow_trans", "table"))
 REQUIRED = inspect.Parameter.empty
 
@@ -1896,6 +1896,58 @@ def novel_segments(ranges, tab, point_class, *, instance_mask=None, num_det=None
         _lib.call("pof_novel_segments", _ptr(ranges), _ptr(tab), _ptr(point_class), *[_ptr(t) for t in gate],
                   float(cls_thresh), float(jump), int(max_skip), int(min_points), float(max_width), B, N,
                   *[_ptr(t) for t in out], _stream())
+    return out
+
+
+MergedDetections = _record("MergedDetections", instance_mask=(_I32, "B", "N"), num_det=(_I32, "B"),
+                           det_xy=(_F64, "B", "N", 2), det_cls=(_F64, "B", "N"), det_points=(_I32, "B", "N"),
+                           det_src=(_U8, "B", "N"), det_row=(_I32, "B", "N"), b_row=(_I32, "B", "N"),
+                           b_count=(_I32, "B", "N"), b_known=(_I32, "B", "N"), merge_count=(_I32, "B", 4))
+
+
+def merge_detections_buffers(B, N, device="cuda"):
+    """The eleven outputs of ``merge_detections`` for B scans of N points, zero-filled, as its ``out=`` (allocate once,
+    before a graph capture)."""
+    return _zeros_of(MergedDetections, device, B=B, N=N)
+
+
+def merge_detections(b_instance_mask, b_num_det, b_det_xy, b_det_cls, *, instance_mask=None, num_det=None, det_xy=None,
+                     det_cls=None, cls_thresh=0.5, absorb_pct=50, out=None):
+    """N18: two detection records made one, one launch per batch (include/pof_abi.h states the rules in full).
+
+    b_instance_mask [B,N] i32, b_num_det [B] i32, b_det_xy [B,N,2] f64, b_det_cls [B,N] f64: the secondary record, e.g.
+    the first four fields of ``novel_segments``.  instance_mask, num_det, det_xy, det_cls: the primary record of the same
+    shapes, as ``nms_predicted_center`` returns it, all four or none (an empty one).  A point is confident when its
+    primary row has a score >= ``cls_thresh``.  A secondary row is absorbed when it has no points or at least
+    ``absorb_pct`` per cent (an int in [0, 101]) of them are confident; the others are appended behind the primary rows
+    in their order while there is room below N, and take their points that are not confident.  The primary rows, and the
+    appended rows' centres and scores, are copied bit for bit.
+    -> ``MergedDetections``: instance_mask [B,N] i32, num_det [B] i32, det_xy [B,N,2] f64, det_cls [B,N] f64 -- the
+    argument order of ``person_motion``, so ``person_motion(ranges, tab, *rec[:4], ...)`` takes them -- det_points
+    [B,N] i32, det_src [B,N] u8 (1 primary, 2 secondary), det_row [B,N] i32 (the row in its own record) per merged row
+    (rows >= num_det[b] are zeros); b_row [B,N] i32 (the merged row, -1 absorbed, -2 dropped, -1 beyond b_num_det),
+    b_count, b_known [B,N] i32 per secondary row; merge_count [B,4] i32 (primary rows, appended, absorbed, dropped).
+    N <= 4096.  The same bits in every run.  ``out``: a ``MergedDetections`` of preallocated tensors
+    (``merge_detections_buffers``)."""
+    b_instance_mask = _dev(b_instance_mask, torch.int32, "b_instance_mask")
+    if b_instance_mask.dim() != 2:
+        raise ValueError("b_instance_mask must be [B,N]")
+    B, N = b_instance_mask.shape
+    dev = b_instance_mask.device
+    sec = (b_instance_mask, _dev(b_num_det, torch.int32, "b_num_det"), _dev(b_det_xy, torch.float64, "b_det_xy"),
+           _dev(b_det_cls, torch.float64, "b_det_cls"))
+    if [tuple(t.shape) for t in sec[1:]] != [(B,), (B, N, 2), (B, N)]:
+        raise ValueError("b_instance_mask and b_det_cls must be [B,N], b_num_det [B] and b_det_xy [B,N,2]")
+    given = sum(t is not None for t in (instance_mask, num_det, det_xy, det_cls))
+    if given not in (0, 4):
+        raise ValueError("instance_mask, num_det, det_xy and det_cls (the primary record) come together or not at all")
+    prim = _nms_results(instance_mask, num_det, det_xy, det_cls, B, N) if given else (None,) * 4
+    out = _out_of(MergedDetections, out, dev, B=B, N=N)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_merge_detections", *[_ptr(t) for t in sec], *[_ptr(t) for t in prim], float(cls_thresh),
+                  int(absorb_pct), B, N, *[_ptr(t) for t in out], _stream())
     return out
 
 

@@ -595,7 +595,8 @@ class OccupancyGrid:
     ``probability(unit)`` the occupancy probability of a count worth ``unit`` nat.  ``localize(scan, odom, ...)``
     corrects a pose against the grid as it stands (``ops.grid_match``) without updating it; ``cast(scan, odom, ...)``
     ray-casts the grid as it stands along every beam (``ops.grid_cast``), to be called before the scan's ``update``;
-    ``novel_segments(scan, odom, ...)`` does that and groups the NOVEL points into detections (``ops.novel_segments``).
+    ``novel_segments(scan, odom, ...)`` does that and groups the NOVEL points into detections (``ops.novel_segments``);
+    ``merged_detections(scan, odom, ...)`` does that and merges them with the NMS's (``ops.merge_detections``).
     ``scroll=dict(margin=...)`` (None: the grid stays where ``reset`` put it): the grid follows the sensor
     (``ops.grid_scroll``, two more launches in front of ``update`` and ``localize``): within ``margin`` cells of a border
     (None: a quarter of the shorter side in whole tiles) it is shifted by whole tiles of 64 cells so that the sensor
@@ -699,11 +700,12 @@ class OccupancyGrid:
                                                                     "max_range"))[0]
 
     def _cast(self, scan, odom, pred_cls, pred_reg, settings):
-        """``cast`` -> (its dict, the scan [1,N] on the device, the ``ops.GridCast``, the NMS gate's keywords)."""
+        """``cast`` -> (its dict, the scan [1,N] on the device, the ``ops.GridCast``, the NMS gate's keywords, the NMS's
+        det_xy or None)."""
         cur = _to_dev(scan, torch.float32).reshape(1, -1)
-        gate, dc = {}, None
+        gate, dc, xy = {}, None, None
         if pred_cls is not None and pred_reg is not None:
-            _, dc, num, inst, dtype = _nms(cur, self._tab, pred_cls, pred_reg, self._min_dist)
+            xy, dc, num, inst, dtype = _nms(cur, self._tab, pred_cls, pred_reg, self._min_dist)
             gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
         rot, trans, _ = _pose_terms(None if odom is None else np.asarray(odom, dtype=np.float64)[None])
         if self._centre:                                       # as ``update``: the first pose in the middle of the grid
@@ -719,7 +721,7 @@ class OccupancyGrid:
             m = int(num[0].item())
             result.update({k: _host(getattr(out, k))[:m] for k in ("det_novel", "det_map", "det_through")},
                           dets_cls=_host(dc)[:m].reshape(-1, 1).astype(dtype), instance_mask=_host(inst))
-        return result, cur, out, gate
+        return result, cur, out, gate, xy
 
     def novel_segments(self, scan, odom=None, pred_cls=None, pred_reg=None, **settings):
         """``cast(scan, odom, ...)`` and, on its classes, the runs of NOVEL points as detections
@@ -732,12 +734,17 @@ class OccupancyGrid:
         segments), seg_xy [K,2] (the mean of the segment's points, sensor frame), seg_cls [K] (ones), seg_points,
         seg_first, seg_last, seg_known [K], seg_width2 [K] and seg_count [3] (segments before the filters, dropped as
         few, dropped as wide)."""
+        return self._segments(scan, odom, pred_cls, pred_reg, settings)[0]
+
+    def _segments(self, scan, odom, pred_cls, pred_reg, settings):
+        """``novel_segments`` -> (its dict, the ``ops.NovelSegments``, the NMS gate's keywords, the NMS's det_xy or
+        None)."""
         own = set(ops.stage_settings(ops.novel_segments)) - {"cls_thresh"}
         cast_kw = {k: v for k, v in settings.items() if k not in own}
         unknown = set(cast_kw) - (set(ops.stage_settings(ops.grid_cast)) - {"res", "max_range"})
         if unknown:
             raise ValueError("unknown novel_segments settings: %s" % sorted(unknown))
-        result, cur, out, gate = self._cast(scan, odom, pred_cls, pred_reg, cast_kw)
+        result, cur, out, gate, xy = self._cast(scan, odom, pred_cls, pred_reg, cast_kw)
         shared = {k: self._kw[k] for k in ("cls_thresh",) if k in self._kw}
         seg = ops.novel_segments(cur, self._tab, out.point_class, **gate, **shared,
                                  **{k: v for k, v in settings.items() if k in own})
@@ -747,6 +754,29 @@ class OccupancyGrid:
                           ("seg_xy", "det_xy"), ("seg_cls", "det_cls"), ("seg_points", "det_count"),
                           ("seg_first", "det_first"), ("seg_last", "det_last"), ("seg_width2", "det_width2"),
                           ("seg_known", "det_known"))})
+        return result, seg, gate, xy
+
+    def merged_detections(self, scan, odom=None, pred_cls=None, pred_reg=None, **settings):
+        """``novel_segments(scan, odom, ...)`` and its segments merged with the NMS's detections of the same call
+        (``ops.merge_detections``, one more launch; ``settings``: its ``absorb_pct`` and the settings of
+        ``novel_segments``; ``cls_thresh`` is the grid's).  Like ``cast`` it updates nothing and is to be called BEFORE
+        the ``update`` of the same scan.  Without predictions the merged record is the segments'.
+        -> the dict of ``novel_segments`` and merged_instance_mask [N], merged_num (M, the merged rows), merged_xy [M,2],
+        merged_cls [M], merged_points [M], merged_src [M] (1 the NMS's, 2 a segment), merged_row [M] (the row in its own
+        record), seg_row [K] (per segment its merged row; -1 absorbed, -2 dropped) and merge_count [4] (the NMS's rows,
+        appended, absorbed, dropped)."""
+        own = set(ops.stage_settings(ops.merge_detections)) - {"cls_thresh"}
+        result, seg, gate, xy = self._segments(scan, odom, pred_cls, pred_reg,
+                                               {k: v for k, v in settings.items() if k not in own})
+        shared = {k: self._kw[k] for k in ("cls_thresh",) if k in self._kw}
+        out = ops.merge_detections(*seg[:4], **gate, **({} if xy is None else dict(det_xy=xy)), **shared,
+                                   **{k: v for k, v in settings.items() if k in own})
+        m = int(out.num_det[0].item())
+        result.update(merged_instance_mask=_host(out.instance_mask), merged_num=m,
+                      seg_row=_host(out.b_row)[:result["seg_num"]], merge_count=_host(out.merge_count),
+                      **{name: _host(getattr(out, f))[:m] for name, f in (
+                          ("merged_xy", "det_xy"), ("merged_cls", "det_cls"), ("merged_points", "det_points"),
+                          ("merged_src", "det_src"), ("merged_row", "det_row"))})
         return result
 
     @property

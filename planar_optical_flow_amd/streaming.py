@@ -54,6 +54,12 @@ surface the map predicts, in front of it in space known to be empty, behind it, 
 With ``novel_segments`` (and ``grid_cast``) ``ops.novel_segments`` stands directly behind the grid cast:
 the runs of points in front of the map's surface become detections in the layout of the NMS's, so a mover the net does
 not report is a detection row all the same; with ``gate_map`` they gate the grid map, which then does not burn them in.
+With ``merge_detections`` (and ``novel_segments``) ``ops.merge_detections`` stands directly behind the segments (DESIGN 8,
+N18) and the cast, the segments and the merge move in front of the person stages: the segments the NMS's confident
+detections do not already hold are appended to the NMS's rows, and the person motion, the tracks, the map check of the
+tracks and (with ``gate_map``) the grid map read that one record -- a person the net scores low is tracked and not burned
+in.  The order is then: the pose launch; the grid scroll; the scan-to-grid match; the grid cast; the novelty segments; the
+merge; the person motion; the track update; the grid map; the map check of the tracks; the copy of the scan.
 """
 import gc
 from collections import namedtuple
@@ -72,7 +78,7 @@ _MATCHERS = {"scan_match": ops.scan_match, "keyframe": ops.keyframe_match, "keyf
 
 def stage_defaults(arg, cls_thresh=0.5, method="flow"):
     """What the dict given as the constructor argument ``arg`` ("ego_motion" with its ``method``, "tracks",
-    "person_motion", "grid_map", "grid_match", "grid_scroll", "track_map", "grid_cast", "novel_segments") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
+    "person_motion", "grid_map", "grid_match", "grid_scroll", "track_map", "grid_cast", "novel_segments", "merge_detections") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
     signature has them (``ops.stage_settings``), and -- stated here and nowhere else -- what the detector overrides or
     adds.  ``cls_thresh``: the detector's."""
     if arg == "ego_motion" and method == "flow":
@@ -95,6 +101,12 @@ def stage_defaults(arg, cls_thresh=0.5, method="flow"):
         kw = ops.stage_settings(ops.novel_segments)
         del kw["cls_thresh"]
         return dict(kw, gate_map=False)
+    if arg == "merge_detections":
+        # who is confident is decided by the detector's cls_thresh: it is not a key of the dict; gate_map: whether the
+        # merged record, not the NMS's, gates the grid map of the same scan
+        kw = ops.stage_settings(ops.merge_detections)
+        del kw["cls_thresh"]
+        return dict(kw, gate_map=True)
     if arg in ("grid_scroll", "grid_cast"):
         kw = ops.stage_settings({"grid_scroll": ops.grid_scroll, "grid_cast": ops.grid_cast}[arg])
         del kw["res"]                                          # the grid's: a key of grid_map's dict
@@ -161,7 +173,7 @@ class StreamingDetector:
     update on the per-person result: ``tracks()`` returns the live tracks and the track id of every detection from the
     second scan of a sequence on, and ``reset()`` forgets them (ids restart at 1).
 
-    ``person_motion`` (needs ``nms_min_dist``, excludes ``flow_model``): None, or a dict of ``reach`` (0.5),
+    ``person_motion`` (needs ``nms_min_dist`` or ``merge_detections``, excludes ``flow_model``): None, or a dict of ``reach`` (0.5),
     ``min_points`` (3) and ``max_range`` (20.0) of ``ops.person_motion``.  Every step, the first of a sequence included,
     then ends in that launch behind the pose launch: with ``method="scan_match"`` ``ops.pose_advance`` writes the pose
     terms it reads, with ``"keyframe"`` / ``"keyframe_map"`` the keyframe launch does, and without ``ego_motion``
@@ -220,7 +232,20 @@ class StreamingDetector:
     of the NMS's results.  With ``nms_min_dist`` ``det_known`` says how many points of a segment the detector's own
     confident detections (``cls_thresh``) hold.  ``gate_map=True`` (only without ``nms_min_dist``: merging two gates is
     not built) makes the segments the grid map's gate, so what the stage found is not burned in.
-    ``novel_segments()`` returns the record.  The stage keeps nothing: ``reset()`` has nothing of its own to forget."""
+    ``novel_segments()`` returns the record.  The stage keeps nothing: ``reset()`` has nothing of its own to forget.
+
+    ``merge_detections`` (needs ``novel_segments``, and so ``grid_cast`` and ``grid_map``; with and without
+    ``nms_min_dist``; with a ``flow_model`` it is refused, not built): None, or a dict of ``absorb_pct`` (50) of
+    ``ops.merge_detections`` and ``gate_map`` (True).  Every scan, the first of a sequence included, then runs the grid
+    cast, the segments and ``ops.merge_detections`` in front of the person stages: a segment is absorbed when at least
+    ``absorb_pct`` per cent of its points belong to a detection of the NMS with a score >= ``cls_thresh``, the others are
+    appended to the NMS's rows.  ``person_motion``, ``tracks`` and ``track_map`` read the merged record, and
+    ``person_motion()``, ``tracks()`` and ``track_map()`` answer per merged row; ``detections()`` stays the NMS's.  With
+    ``gate_map`` the grid map takes the merged record as its gate (``novel_segments=dict(gate_map=True)`` is refused
+    beside it: one gate), without it the NMS's as before.  Without ``nms_min_dist`` the primary record is absent, every
+    segment with a point is a row, and ``person_motion`` is accepted without ``nms_min_dist``: the chain needs no
+    detector net.  ``merged_detections()`` returns the record.  The stage keeps nothing: ``reset()`` has nothing of its
+    own to forget."""
 
     # One stage of a scan behind the trunk.  launch(first) enqueues it on the current stream (first: the first scan of a
     # sequence) and writes only fixed buffers; state: the tensors it advances, which a capture's warm-up puts back;
@@ -231,7 +256,7 @@ class StreamingDetector:
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
                  nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None,
                  grid_map=None, grid_match=None, grid_scroll=None, track_map=None, grid_cast=None,
-                 novel_segments=None):
+                 novel_segments=None, merge_detections=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -264,11 +289,11 @@ class StreamingDetector:
         # what a feature was built with, None without it; _filter_kw: the settings of ops.track_update (a detector
         # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
-        self._gm_kw = self._sg_kw = self._gs_kw = self._tm_kw = self._gc_kw = self._ns_kw = None
+        self._gm_kw = self._sg_kw = self._gs_kw = self._tm_kw = self._gc_kw = self._ns_kw = self._mg_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
-            if self._nms is None:
+            if self._nms is None and merge_detections is None:
                 raise ValueError("person_motion needs nms_min_dist: the centroids are taken over the NMS masks")
         method = "flow" if ego_motion is None else dict(ego_motion).get("method", "flow")
         if method not in ("flow", "scan_match", "keyframe", "keyframe_map"):
@@ -295,6 +320,19 @@ class StreamingDetector:
             if dict(novel_segments).get("gate_map") and self._nms is not None:
                 raise ValueError("novel_segments gate_map with nms_min_dist is not built: the grid map takes one gate, "
                                  "and merging the segments with the NMS's rows is its own change")
+        if merge_detections is not None:
+            missing = [k for k, v in (("novel_segments", novel_segments), ("grid_cast", grid_cast),
+                                      ("grid_map", grid_map)) if v is None]
+            if missing:
+                raise ValueError("merge_detections appends the rows of novel_segments, which groups the classes of "
+                                 "grid_cast over grid_map: %s missing" % " and ".join(missing))
+            if flow_model is not None:
+                raise ValueError("merge_detections with a flow_model is not built: the per-person flow is aggregated "
+                                 "over the NMS masks")
+            if dict(novel_segments).get("gate_map"):
+                raise ValueError("merge_detections with novel_segments gate_map: the grid map takes one gate -- "
+                                 "merge_detections=dict(gate_map=True) gates it by the merged record, which holds the "
+                                 "segments; drop novel_segments' gate_map")
         if track_map is not None and (tracks is None or grid_map is None):
             raise ValueError("track_map joins the tracks of tracks with the grid of grid_map: give both")
         self._cls_thresh = float(cls_thresh)
@@ -367,6 +405,46 @@ class StreamingDetector:
                     raise ValueError("grid_match %s must be >= 0" % k)
             self._sg_kw = dict(kw, cls_thresh=self._cls_thresh)
             stages.append(Stage(self._grid_match_stage))
+        def cast_stages():
+            # the grid cast, the novelty segments and the merge: directly in front of the grid map, or with
+            # merge_detections in front of the person stages, which then read the merged record; the grid is allocated
+            # below and read when a stage runs
+            if grid_cast is None:
+                return
+            # directly in front of the grid map, which it reads as the scans before this one left it, and behind the
+            # scroll and the scan-to-grid match; it advances nothing
+            kw = stage_settings("grid_cast", grid_cast)
+            if not float(kw["max_range"]) > 0.0 or (kw["tol"] is not None and not float(kw["tol"]) >= 0.0) or \
+                    int(kw["occ_thresh"]) < 1 or int(kw["free_thresh"]) < 0:
+                raise ValueError("grid_cast: max_range must be > 0, tol >= 0 (or None), occ_thresh >= 1 and "
+                                 "free_thresh >= 0")
+            self._gc_kw = kw
+            self._gc_out = ops.grid_cast_buffers(self.B, self.N, dev)
+            stages.append(Stage(self._grid_cast_stage))
+            if novel_segments is not None:
+                # directly behind the cast, whose classes it groups, and in front of the grid map, which it may gate;
+                # it advances nothing
+                kw = stage_settings("novel_segments", novel_segments)
+                if not float(kw["jump"]) > 0.0 or not float(kw["max_width"]) >= 0.0 or int(kw["min_points"]) < 1 or \
+                        not 0 <= int(kw["max_skip"]) <= 64:
+                    raise ValueError("novel_segments: jump must be > 0, max_width >= 0, min_points >= 1 and "
+                                     "max_skip in [0, 64]")
+                self._ns_gates = bool(kw.pop("gate_map"))
+                self._ns_kw = dict(kw, cls_thresh=self._cls_thresh)
+                self._ns_out = ops.novel_segments_buffers(self.B, self.N, dev)
+                stages.append(Stage(self._novel_segments_stage))
+            if merge_detections is not None:
+                # directly behind the segments, whose rows it appends to the NMS's; it advances nothing
+                kw = stage_settings("merge_detections", merge_detections)
+                if not 0 <= int(kw["absorb_pct"]) <= 101:
+                    raise ValueError("merge_detections: absorb_pct must be in [0, 101]")
+                self._mg_gates = bool(kw.pop("gate_map"))
+                self._mg_kw = dict(kw, cls_thresh=self._cls_thresh)
+                self._mg_out = ops.merge_detections_buffers(self.B, self.N, dev)
+                stages.append(Stage(self._merge_stage))
+
+        if merge_detections is not None:
+            cast_stages()
         if flow_model is not None:
             self._flow_model = flow_model.to(dev).eval()
             self._pf_out = ops.person_flow_buffers(self.B, self.N, dev)
@@ -400,29 +478,8 @@ class StreamingDetector:
             self._gm_state = ops.grid_map_state(self.B, *shape, dev)
             self._gm_out = ops.grid_map_buffers(self.B, self.N, dev)
             self._gm_centre(np.zeros((self.B, 2)))
-            if grid_cast is not None:
-                # directly in front of the grid map, which it reads as the scans before this one left it, and behind the
-                # scroll and the scan-to-grid match; it advances nothing
-                kw = stage_settings("grid_cast", grid_cast)
-                if not float(kw["max_range"]) > 0.0 or (kw["tol"] is not None and not float(kw["tol"]) >= 0.0) or \
-                        int(kw["occ_thresh"]) < 1 or int(kw["free_thresh"]) < 0:
-                    raise ValueError("grid_cast: max_range must be > 0, tol >= 0 (or None), occ_thresh >= 1 and "
-                                     "free_thresh >= 0")
-                self._gc_kw = kw
-                self._gc_out = ops.grid_cast_buffers(self.B, self.N, dev)
-                stages.append(Stage(self._grid_cast_stage))
-                if novel_segments is not None:
-                    # directly behind the cast, whose classes it groups, and in front of the grid map, which it may gate;
-                    # it advances nothing
-                    kw = stage_settings("novel_segments", novel_segments)
-                    if not float(kw["jump"]) > 0.0 or not float(kw["max_width"]) >= 0.0 or int(kw["min_points"]) < 1 or \
-                            not 0 <= int(kw["max_skip"]) <= 64:
-                        raise ValueError("novel_segments: jump must be > 0, max_width >= 0, min_points >= 1 and "
-                                         "max_skip in [0, 64]")
-                    self._ns_gates = bool(kw.pop("gate_map"))
-                    self._ns_kw = dict(kw, cls_thresh=self._cls_thresh)
-                    self._ns_out = ops.novel_segments_buffers(self.B, self.N, dev)
-                    stages.append(Stage(self._novel_segments_stage))
+            if merge_detections is None:
+                cast_stages()
             stages.append(Stage(self._grid_stage, tuple(self._gm_state), self._gm_state.grid.zero_))
         if track_map is not None:
             # behind the track update and the grid map, whose outputs of this step it joins; it runs when the track
@@ -519,6 +576,14 @@ class StreamingDetector:
                 self._dets = ops.nms_predicted_center(self._scan[:, 0], self.tab, conf, reg.double().contiguous(), self._nms)
         return cls, reg, tmpl, fused
 
+    def _person_dets(self):
+        """The detection record the person stages read, in the order of ``_dets`` (xy, scores, counts, masks): the merged
+        one with merge_detections, else the NMS's."""
+        if self._mg_kw is None:
+            return self._dets
+        o = self._mg_out
+        return o.det_xy, o.det_cls, o.num_det, o.instance_mask
+
     def _match_gate(self):
         """With the NMS the points of this scan's confident detections do not vote in a scan match."""
         if self._dets is None:
@@ -558,13 +623,13 @@ class StreamingDetector:
 
     # Behind the pose launch, on every scan of a sequence (the first one seeds).
     def _motion_stage(self, first):
-        xy, conf, num, inst = self._dets
+        xy, conf, num, inst = self._person_dets()
         ops.person_motion(self._scan[:, 0], self.tab, inst, num, xy, conf, self._pose_rot, self._pose_trans,
                           self._pm_state, out=self._pm_out, **self._pm_kw)
 
     # On the result of whichever per-person stage the detector has.
     def _track_stage(self, first):
-        o, (_, _, num, inst) = self._pf_out if self._pm_kw is None else self._pm_out, self._dets
+        o, (_, _, num, inst) = self._pf_out if self._pm_kw is None else self._pm_out, self._person_dets()
         ops.track_update(o.det_xy_world, o.det_flow, o.det_valid, num, inst, self._track_state, **self._filter_kw)
 
     # Behind the pose launch, on every scan of a sequence: the scan into the grid at this step's pose.
@@ -572,6 +637,9 @@ class StreamingDetector:
         gate = self._match_gate()
         if self._ns_kw is not None and self._ns_gates:         # the novelty segments of this scan are not burned in
             o = self._ns_out
+            gate = dict(instance_mask=o.instance_mask, num_det=o.num_det, det_cls=o.det_cls)
+        if self._mg_kw is not None and self._mg_gates:         # nor is what the merge appended to the NMS's rows
+            o = self._mg_out
             gate = dict(instance_mask=o.instance_mask, num_det=o.num_det, det_cls=o.det_cls)
         ops.grid_map_update(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._gm_state,
                             out=self._gm_out, **gate, **self._gm_kw)
@@ -586,9 +654,17 @@ class StreamingDetector:
         ops.novel_segments(self._scan[:, 0], self.tab, self._gc_out.point_class, out=self._ns_out,
                            **self._match_gate(), **self._ns_kw)
 
+    # Directly behind the novelty segments, on every scan of a sequence: their rows appended to the NMS's; without
+    # nms_min_dist there are none of those and the primary record is absent.
+    def _merge_stage(self, first):
+        gate = self._match_gate()
+        if gate:
+            gate["det_xy"] = self._dets[0]
+        ops.merge_detections(*self._ns_out[:4], out=self._mg_out, **gate, **self._mg_kw)
+
     # Behind the track update and the grid map of this step: the grid's word on every track's detection, per slot.
     def _track_map_stage(self, first):
-        _, _, num, inst = self._dets
+        _, _, num, inst = self._person_dets()
         ops.track_map(self._track_state, self._gm_out, inst, num, self._tm_state, out=self._tm_out, **self._tm_kw)
 
     # Behind the scan matcher's pose launch and in front of everything that reads the pose terms: the pose against the
@@ -718,7 +794,7 @@ class StreamingDetector:
     def _per_detection(self, o, **fields):
         """One dict per sensor of the rows of its detections: the scores, and under every key the field of ``o`` it
         names."""
-        _, conf, num, _ = self._dets
+        _, conf, num, _ = self._person_dets()
         host = lambda t, b, m: t[b, :m].cpu().numpy()
         return [dict({k: host(getattr(o, f), b, m) for k, f in fields.items()}, dets_cls=host(conf, b, m),
                      valid=host(o.det_valid, b, m).astype(bool)) for b, m in enumerate(num.cpu().numpy())]
@@ -798,6 +874,17 @@ class StreamingDetector:
             raise RuntimeError("construct the detector with novel_segments and feed it a scan first")
         return self._ns_out
 
+    def merged_detections(self):
+        """-> the last step's ``ops.MergedDetections``, device-resident and valid until the next call: instance_mask
+        [B,N], num_det [B], det_xy [B,N,2] (sensor frame) and det_cls [B,N] in the layout of the NMS's results -- the
+        rows ``person_motion()``, ``tracks()`` and ``track_map()`` answer for -- det_points, det_src (1 the NMS's, 2 a
+        segment) and det_row [B,N] per row, b_row, b_count and b_known [B,N] per row of ``novel_segments()`` and
+        merge_count [B,4].  Needs ``merge_detections`` and one scan.  No synchronisation: the tensors stay on the
+        device."""
+        if self._mg_kw is None or self._seen < 1:
+            raise RuntimeError("construct the detector with merge_detections and feed it a scan first")
+        return self._mg_out
+
     def track_map(self):
         """-> (list with one list per sensor of the live tracks, in slot order as ``tracks()`` has them: dicts of id,
         cls (0 undecided, 1 free-standing, 2 unsupported, 3 background), points, free, occ (the three sums), scans,
@@ -809,7 +896,7 @@ class StreamingDetector:
         s, o = self._tm_state, self._tm_out
         h = {k: getattr(s, k).cpu().numpy() for k in s._fields}
         ids, cls = self._track_state.track_id.cpu().numpy(), o.track_class.cpu().numpy()
-        det_class, counts = o.det_class.cpu().numpy(), self._dets[2].cpu().numpy()
+        det_class, counts = o.det_class.cpu().numpy(), self._person_dets()[2].cpu().numpy()
         live = [[{"id": int(ids[b, t]), "cls": int(cls[b, t]), "points": int(h["ev_points"][b, t]),
                   "free": int(h["ev_free"][b, t]), "occ": int(h["ev_occ"][b, t]), "scans": int(h["ev_scans"][b, t]),
                   "moved": bool(h["ev_moved"][b, t]), "start": h["ev_start"][b, t].copy()}
@@ -861,7 +948,7 @@ class StreamingDetector:
             raise RuntimeError("construct the detector with tracks and feed it two scans of a sequence first")
         s = self._track_state
         h = {k: getattr(s, k).cpu().numpy() for k in s._fields}
-        counts = self._dets[2].cpu().numpy()
+        counts = self._person_dets()[2].cpu().numpy()
         live = [[{"id": int(h["track_id"][b, t]), "xy": h["track_state"][b, t, :2].copy(),
                   "velocity": h["track_state"][b, t, 2:].copy(), "cov": h["track_cov"][b, t].copy(),
                   "hits": int(h["track_hits"][b, t]), "misses": int(h["track_misses"][b, t]),

@@ -1,5 +1,5 @@
 """Per-kernel timing on the GPU box (events on torch's current stream, which is the
-stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [gridscroll] [cast] [novel] ..."""
+stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [gridscroll] [cast] [novel] [merge] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -234,7 +234,7 @@ if "person" in which:
             % (M, ms_tm[M], ms_t[M], (tm_state[M].ev_scans > 0).sum().item() / B,
                tm_out[M].class_count.sum(dim=0).tolist()) for M in tracks))
 
-if which & {"grid", "gridmatch", "gridscroll", "cast", "novel"}:
+if which & {"grid", "gridmatch", "gridscroll", "cast", "novel", "merge"}:
     # N12: the occupancy grid map, 450 beams into 512 x 512 cells of 0.1 m per sensor, for 1024, 8 and 1 sensors, next
     # to person_motion on the same scans, NMS results and pose (alternating, three repeats of 50 launches).  The same
     # scan every call, with lo / hi at the int16 limits so that no cell saturates inside the run and every launch
@@ -258,6 +258,10 @@ if which & {"grid", "gridmatch", "gridscroll", "cast", "novel"}:
     # scan itself, so the scan cast through it has no NOVEL point; the stage is therefore timed on two sets of classes:
     # `walkers`, the cast of the same scans with every sixth run of 10 beams pulled to 70 % of its range (somebody in
     # front of the wall, in space the map saw empty), and `all`, every byte NOVEL -- the most members a scan can have.
+    # merge: N18 next to novel_segments and person_motion, alternating, on the novel sub-command's `walkers` scans and
+    # classes: the segments of that cast merged with the NMS record.  Two legs: `nms`, the scores as the NMS gave them
+    # (segments over confident detections are absorbed), and `all kept`, A's scores lowered to 0 so that every segment
+    # with a point is appended -- the most rows the stage copies.
     N, H, W, RES = 450, 512, 512, 0.1
     rng = np.random.default_rng(1701)
     tab = ops.phi_table()
@@ -367,6 +371,30 @@ if which & {"grid", "gridmatch", "gridscroll", "cast", "novel"}:
                              ns_out.seg_count[:, 1].sum().item() / B, ns_out.seg_count[:, 2].sum().item() / B,
                              ns_out.det_known.sum().item() / B))
             del ns_state
+        if "merge" in which:
+            mg_state = ops.GridMapState(gm_state.grid.clone(), gm_state.origin.clone())
+            mg_cast_out = ops.grid_cast_buffers(B, N, dev)
+            ns_out, mg_out = ops.novel_segments_buffers(B, N, dev), ops.merge_detections_buffers(B, N, dev)
+            near = scans.clone()
+            near[:, (torch.arange(N, device=dev) // 10) % 6 == 2] *= 0.7
+            ops.grid_cast(near, tab, rot, trans, mg_state, res=RES, instance_mask=inst, num_det=num, det_cls=dc,
+                          out=mg_cast_out)
+            walkers = mg_cast_out.point_class
+            novel = lambda: ops.novel_segments(near, tab, walkers, instance_mask=inst, num_det=num, det_cls=dc, out=ns_out)
+            novel()
+            for name, scores in (("nms", dc), ("all kept", torch.zeros_like(dc))):
+                merge = lambda: ops.merge_detections(*ns_out[:4], instance_mask=inst, num_det=num, det_xy=xy,
+                                                     det_cls=scores, out=mg_out)
+                merge()
+                for rep in range(3):
+                    ms_n, ms_pm, ms_m = timeit(novel, iters=50), timeit(motion, iters=50), timeit(merge, iters=50)
+                    mc = mg_out.merge_count.sum(dim=0).tolist()
+                    print("merge B=%d N=%d scores=%s: merge_detections %.3f ms (%.2f us per sensor) next to novel_segments "
+                          "%.3f ms and person_motion %.3f ms; per scan %.1f NMS rows, %.1f segments: %.1f appended, %.1f "
+                          "absorbed, %.1f dropped; %.1f points changed rows"
+                          % (B, N, name, ms_m, ms_m / B * 1e3, ms_n, ms_pm, mc[0] / B, ns_out.num_det.sum().item() / B,
+                             mc[1] / B, mc[2] / B, mc[3] / B, (mg_out.instance_mask != inst).sum().item() / B))
+            del mg_state
         for rep in range(3 if "grid" in which else 0):
             ms_g, ms_pm = timeit(grid, iters=50), timeit(motion, iters=50)
             bound = B * 2 * H * W * 2

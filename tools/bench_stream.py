@@ -1,5 +1,5 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-scroll] [--grid-cast] [--novel] [--track-map]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-scroll] [--grid-cast] [--novel] [--merge] [--track-map]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
@@ -28,6 +28,9 @@ grid_cast=dict() directly in front of the grid map, so one process gives the map
 --novel (with --grid; brings the --grid-cast step with it): one more step in the same process, that step with
 novel_segments=dict() directly behind the cast, so one process gives the cast step without and with the novelty
 segments.
+--merge (with --grid --novel; implies --nms): instead of those steps, the keyframe step with grid_map=dict(),
+grid_cast=dict(), novel_segments=dict(), person_motion=dict() and tracks=dict() without and with merge_detections=dict()
+behind the segments, alternating repeats in one process.
 --track-map (with --person-motion --tracks --grid, without --flow; --ego=scan_match|keyframe|keyframe_map chooses the
 pose, keyframe by default): the replayed step with person_motion=dict(), tracks=dict() and grid_map=dict() without and
 with track_map=dict() behind the grid map, alternating repeats in one process.
@@ -45,7 +48,7 @@ EMBED = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--embed=")] or [
 STORAGE = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--storage=")] or ["float32"])[0]
 FLOW = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--flow=")] or [None])[0]
 PERSON_MOTION = "--person-motion" in sys.argv
-NMS = 0.5 if (FLOW or "--nms" in sys.argv or PERSON_MOTION) else None
+NMS = 0.5 if (FLOW or "--nms" in sys.argv or PERSON_MOTION or "--merge" in sys.argv) else None
 EGO_METHOD = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--ego=")] or ["flow"])[0]
 EGO = any(a == "--ego" or a.startswith("--ego=") for a in sys.argv)
 MATCH = dict(method="scan_match")
@@ -58,11 +61,14 @@ GRID_MATCH = "--grid-match" in sys.argv
 GRID_SCROLL = "--grid-scroll" in sys.argv
 GRID_CAST = "--grid-cast" in sys.argv
 NOVEL = "--novel" in sys.argv
+MERGE = "--merge" in sys.argv
+if MERGE and not (GRID and NOVEL):
+    sys.exit("--merge needs --grid --novel")
 TRACK_MAP = "--track-map" in sys.argv
 if TRACK_MAP and not (PERSON_MOTION and TRACKS and GRID and FLOW is None):
     sys.exit("--track-map needs --person-motion --tracks --grid and no --flow")
 EAGER = "--eager" in sys.argv
-sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--track-map", "--person-motion", "--grid", "--novel", "--eager"))]
+sys.argv = [a for a in sys.argv if not a.startswith(("--embed=", "--storage=", "--flow=", "--nms", "--ego", "--tracks", "--track-map", "--person-motion", "--grid", "--novel", "--merge", "--eager"))]
 
 
 class DiffFlow(torch.nn.Module):
@@ -91,6 +97,12 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             unchecked, checked = mk(**chain), mk(track_map=dict(), **chain)
             steps = {"person_motion + tracks + grid_map": lambda t: unchecked(scans[:, t]),
                      "person_motion + tracks + grid_map + track_map": lambda t: checked(scans[:, t])}
+        elif MERGE:
+            chain = dict(ego_motion=KEYFRAME, grid_map=dict(), grid_cast=dict(), novel_segments=dict(),
+                         person_motion=dict(), tracks=dict())
+            apart, merged = mk(**chain), mk(merge_detections=dict(), **chain)
+            steps = {"grid_map + grid_cast + novel_segments + person_motion + tracks": lambda t: apart(scans[:, t]),
+                     "the same + merge_detections": lambda t: merged(scans[:, t])}
         elif GRID:
             keyed_only, gridded = mk(ego_motion=KEYFRAME), mk(ego_motion=KEYFRAME, grid_map=dict())
             steps = {"keyframe": lambda t: keyed_only(scans[:, t]), "keyframe + grid_map": lambda t: gridded(scans[:, t])}
@@ -155,6 +167,15 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             live, _, state, out = checked.track_map()
             print("   track_map after 40 scans: live tracks %s, with evidence %s, classes (0-3) %s"
                   % ([len(l) for l in live], (state.ev_scans > 0).sum(dim=1).tolist(), out.class_count.tolist()))
+            print("streaming step B=%d, %s per scan, 4 alternating repeats of 32 steps: %s"
+                  % (B, "eager launches" if EAGER else "hipGraph replay",
+                     ", ".join("%s %s ms" % (k, " ".join("%.3f" % v for v in vs)) for k, vs in ms.items())), flush=True)
+            continue
+        if MERGE:
+            o = merged.merged_detections()
+            print("   merge_detections at the last scan: (NMS rows, appended, absorbed, dropped) %s; live tracks %s without, "
+                  "%s with" % (o.merge_count.tolist(), [len(l) for l in apart.tracks()[0]],
+                               [len(l) for l in merged.tracks()[0]]))
             print("streaming step B=%d, %s per scan, 4 alternating repeats of 32 steps: %s"
                   % (B, "eager launches" if EAGER else "hipGraph replay",
                      ", ".join("%s %s ms" % (k, " ".join("%.3f" % v for v in vs)) for k, vs in ms.items())), flush=True)
