@@ -678,6 +678,63 @@ int pof_grid_match(const float *ranges, const double *tab, const int32_t *instan
                    double *correction, pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N19 grid refine: the pose of a sensor fitted to its own occupancy grid (N12) below the size of a cell.  N13 is a
+ * whole-cell search that stays silent while the pose is good; this stage runs every scan and removes the slow drift of a
+ * pose composed from scan pairs: a Gauss-Newton fit of the scan's endpoints to the bilinearly interpolated, clamped
+ * log-odds, as Hector SLAM does it.  The reference has nothing of the kind; the specification is this comment (restated
+ * in NumPy, the order of the sums included, by tests/test_grid_refine.py).  One sensor per batch entry, one launch.
+ * Settings: cap in [1, 32767] (32): the count at which a cell is taken as certainly occupied; iters in [1, 32] (8);
+ *   min_points >= 0 (50); min_pivot >= 0 (1e-6); max_shift >= 0 in cells (2.0); max_turn >= 0 in radians (0.05);
+ *   eps_shift in cells (1e-3); eps_turn in radians (1e-5); max_range and cls_thresh as N13.
+ * Inputs: ranges [B][N] float32, the current scan; tab the angle table; optionally the NMS results instance_mask
+ *   [B][N], num_det [B] (clamped to [0, N]) and det_cls [B][N], all three or none (NULL); grid [B][H][W] int16 and
+ *   origin [B][2] float64 of N12, both read only; res.
+ * In/out: pose [B][3] float64 = (x, y, phi), rot [B][4] float32 row-major and trans [B][2] float64, as for N13.
+ * A point i VOTES by N13's rule (r finite, 0 < r < max_range, no person's point); V = their number;
+ *   p = (r cos_i, r sin_i).  All arithmetic is float64 with plain multiplies and adds (no FMA).
+ * Evaluation at (x, y, phi):
+ *   (s, c) = sincos(phi) in double -- from the pose, not from the float rot.
+ *   d = (c p_x - s p_y, s p_x + c p_y)
+ *   u = ((d_x + x) - o_x) / res - 0.5,  v = ((d_y + y) - o_y) / res - 0.5  (true divisions; cell values sit at cell
+ *     centres);  i0 = floor(u), j0 = floor(v), f = (u - i0, v - j0).
+ *   The point is INSIDE when -1 <= i0 < W and -1 <= j0 < H, compared in double; a NaN is outside.
+ *   m(i, j) = (double)clamp(grid[j][i], -cap, cap) / (double)cap, and 0 for a cell outside the grid;
+ *     m00, m10, m01, m11 = m at (i0, j0), (i0 + 1, j0), (i0, j0 + 1), (i0 + 1, j0 + 1).
+ *   M   = (m00 (1 - f_x) + m10 f_x) (1 - f_y) + (m01 (1 - f_x) + m11 f_x) f_y
+ *   g_x = (m10 - m00) (1 - f_y) + (m11 - m01) f_y,   g_y = (m01 - m00) (1 - f_x) + (m11 - m10) f_x   (per cell)
+ *   l = d / res,  J = (g_x, g_y, g_y l_x - g_x l_y),  e = 1 - M.
+ *   Eleven sums over the inside voting points, in the FIXED ORDER of csrc/pof_sensor.h: J_a J_b for ab = 00 01 02 11 12
+ *   22 -> A, J_a e -> b, M, and 1 -> n.
+ * The fit: the correction (c_x, c_y, c_phi) in cells, cells and radians starts at zero; evaluation k is at
+ *   (x_in + c_x res, y_in + c_y res, phi_in + c_phi) -- always the incoming pose plus the accumulated correction.
+ *   count = n and s0 = sum M / n of the first evaluation.  An update solves A delta = b by the Cholesky of
+ *   csrc/pof_icp.h (pivots tested against min_pivot * dmax as they are formed, obs = the smallest pivot formed over dmax,
+ *   of the last solve; 0 before any) and adds delta to the correction.  After `iters` updates, or after an update with
+ *   max(|delta_x|, |delta_y|) < eps_shift and |delta_phi| < eps_turn, one more evaluation gives s1 = sum M / n: there
+ *   are iters_used + 1 evaluations.
+ *   ok    = V >= min_points  and  n >= min_points at every evaluation  and  every pivot passed.  The fit stops at the
+ *           first evaluation or solve that fails it.  An empty grid has A = 0 and is not ok.
+ *   moved = ok  and  max(|c_x|, |c_y|) <= max_shift  and  |c_phi| <= max_turn  and  s1 > s0.
+ * With moved: pose = (x_in + c_x res, y_in + c_y res, phi_in + c_phi), and rot, trans are written from it as
+ *   pof_pose_advance writes them.  Without moved pose, rot and trans keep their bits: nothing is stored.
+ * Outputs: correction [B][3] float64 = (c_x res, c_y res, c_phi), zeros without moved; score [B][2] float64 = (s0, s1),
+ *   s1 NaN when not ok, s0 NaN when count = 0; obs [B] float64; votes [B] int32 = V; count [B] int32; iters_used [B]
+ *   int32 = the updates made; ok [B], moved [B] uint8.
+ * No atomics, one order of additions: the same bits in every run, at every batch position and in a graph replay.
+ * POF_E_BADARG (checked first; nothing written): a NULL pointer other than the three NMS results, NMS pointers given
+ *   in part, res not > 0, max_range not > 0, cap outside [1, 32767], iters outside [1, 32], min_points < 0, min_pivot,
+ *   max_shift or max_turn not >= 0, B < 0, N < 1.  POF_E_SHAPE (nothing written): N > 4096, H or W not a multiple of 64
+ *   or outside [64, 2048].  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_grid_refine(const float *ranges, const double *tab, const int32_t *instance_mask, const int32_t *num_det,
+                    const double *det_cls, double cls_thresh, double max_range, const int16_t *grid,
+                    const double *origin, double res, int cap, int iters, int min_points, double min_pivot,
+                    double max_shift, double max_turn, double eps_shift, double eps_turn, int B, int N, int H, int W,
+                    double *pose, float *rot, double *trans, double *correction, double *score, double *obs,
+                    int32_t *votes, int32_t *count, int32_t *iters_used, uint8_t *ok, uint8_t *moved,
+                    pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * N14 scrolling occupancy grid: the grid of N12 follows its sensor.  When the sensor comes within `margin` cells of a
  * border the grid is shifted by whole tiles of 64 cells so that the sensor's tile is the middle tile again -- the tile
  * a reset centres it on -- and what scrolls in is unknown.  The reference has nothing of the kind; the specification

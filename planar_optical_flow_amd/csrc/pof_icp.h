@@ -180,6 +180,50 @@ __device__ __forceinline__ bool correspond(const double *ax, const double *ay, i
     return true;
 }
 
+// The 3 x 3 solve of the header comment, shared with pof_grid_refine (N19, grid_refine.hip): A x = -g with A = (A00 A01
+// A02; . A11 A12; . . A22) by Cholesky, every pivot tested against min_pivot * dmax as it is formed; obs as above.  x
+// is not formed when a pivot fails.
+struct Solve3 {
+    bool failed;
+    double obs, x0, x1, x2;
+};
+
+__device__ __forceinline__ Solve3 cholesky3(double A00, double A01, double A02, double A11, double A12, double A22,
+                                            double g0, double g1, double g2, double min_pivot)
+{
+    Solve3 o = {false, 0.0, 0.0, 0.0, 0.0};
+    const double dmax = fmax(A00, fmax(A11, A22));
+    const double floor_ = min_pivot * dmax;
+    const double p0 = A00;
+    double pmin = p0, l00 = 0.0, l10 = 0.0, l20 = 0.0, l11 = 0.0, l21 = 0.0, l22 = 0.0;
+    o.failed = !(p0 > floor_);
+    if (!o.failed) {
+        l00 = sqrt(p0);
+        l10 = A01 / l00;
+        l20 = A02 / l00;
+        const double p1 = A11 - l10 * l10;
+        pmin = p1 < pmin ? p1 : pmin;
+        o.failed = !(p1 > floor_);
+        if (!o.failed) {
+            l11 = sqrt(p1);
+            l21 = (A12 - l20 * l10) / l11;
+            const double p2 = (A22 - l20 * l20) - l21 * l21;
+            pmin = p2 < pmin ? p2 : pmin;
+            o.failed = !(p2 > floor_);
+            if (!o.failed) l22 = sqrt(p2);
+        }
+    }
+    o.obs = dmax > 0.0 ? pmin / dmax : 0.0;
+    if (o.failed) return o;
+    const double y0 = -g0 / l00;
+    const double y1 = (-g1 - l10 * y0) / l11;
+    const double y2 = ((-g2 - l20 * y0) - l21 * y1) / l22;
+    o.x2 = y2 / l22;
+    o.x1 = (y1 - l21 * o.x2) / l11;
+    o.x0 = ((y0 - l10 * o.x1) - l20 * o.x2) / l00;
+    return o;
+}
+
 // The iterations from the start value in m, which ends as the final (theta, u).  `part`: the LDS of group_sum<kSums>.
 template <int THREADS, class Centre>
 __device__ __forceinline__ Result iterate(const double *ax, const double *ay, double *part, int N, const Settings st,
@@ -226,35 +270,11 @@ __device__ __forceinline__ Result iterate(const double *ax, const double *ay, do
             res.obs = 0.0;
             break;                                             // uniform: every thread holds the same bits
         }
-        const double dmax = fmax(S[0], fmax(S[3], S[5]));
-        const double floor_ = st.min_pivot * dmax;
-        const double p0 = S[0];
-        double pmin = p0, l00 = 0.0, l10 = 0.0, l20 = 0.0, l11 = 0.0, l21 = 0.0, l22 = 0.0;
-        res.failed = !(p0 > floor_);
-        if (!res.failed) {
-            l00 = sqrt(p0);
-            l10 = S[1] / l00;
-            l20 = S[2] / l00;
-            const double p1 = S[3] - l10 * l10;
-            pmin = p1 < pmin ? p1 : pmin;
-            res.failed = !(p1 > floor_);
-            if (!res.failed) {
-                l11 = sqrt(p1);
-                l21 = (S[4] - l20 * l10) / l11;
-                const double p2 = (S[5] - l20 * l20) - l21 * l21;
-                pmin = p2 < pmin ? p2 : pmin;
-                res.failed = !(p2 > floor_);
-                if (!res.failed) l22 = sqrt(p2);
-            }
-        }
-        res.obs = dmax > 0.0 ? pmin / dmax : 0.0;
+        const Solve3 sol = cholesky3(S[0], S[1], S[2], S[3], S[4], S[5], S[6], S[7], S[8], st.min_pivot);
+        res.failed = sol.failed;
+        res.obs = sol.obs;
         if (res.failed) break;
-        const double y0 = -S[6] / l00;
-        const double y1 = (-S[7] - l10 * y0) / l11;
-        const double y2 = ((-S[8] - l20 * y0) - l21 * y1) / l22;
-        const double x2 = y2 / l22;
-        const double x1 = (y1 - l21 * x2) / l11;
-        const double x0 = ((y0 - l10 * x1) - l20 * x2) / l00;
+        const double x0 = sol.x0, x1 = sol.x1, x2 = sol.x2;
         double s0, c0;
         sincos(x0, &s0, &c0);
         const double nux = (c0 * m.ux - s0 * m.uy) + x1, nuy = (s0 * m.ux + c0 * m.uy) + x2;

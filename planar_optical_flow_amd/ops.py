@@ -1663,6 +1663,69 @@ def grid_match(ranges, tab, rot, trans, pose, state, *, res, table=None, instanc
     return out
 
 
+GridRefine = _record("GridRefine", correction=(_F64, "B", 3), score=(_F64, "B", 2), obs=(_F64, "B"), votes=(_I32, "B"),
+                     count=(_I32, "B"), iters_used=(_I32, "B"), ok=(_U8, "B"), moved=(_U8, "B"))
+
+
+def grid_refine_check(cap, iters, min_points, **not_negative):
+    """The settings of ``grid_refine`` with a range, checked as its launcher checks them, or this raises; the keywords
+    (``min_pivot``, ``max_shift``, ``max_turn``) must be >= 0.  What wraps the stage checks its settings here, before
+    anything is allocated."""
+    if not 1 <= int(cap) <= 32767:
+        raise ValueError("cap must be in [1, 32767]")
+    if not 1 <= int(iters) <= 32:
+        raise ValueError("iters must be in [1, 32]")
+    if int(min_points) < 0:
+        raise ValueError("min_points must be >= 0")
+    for name, v in not_negative.items():
+        if not float(v) >= 0.0:
+            raise ValueError("%s must be >= 0" % name)
+
+
+def grid_refine_buffers(B, device="cuda"):
+    """The eight outputs of ``grid_refine`` for B sensors, zero-filled, as its ``out=`` (allocate once, before a graph
+    capture)."""
+    return _zeros_of(GridRefine, device, B=B)
+
+
+def grid_refine(ranges, tab, rot, trans, pose, state, *, res, instance_mask=None, num_det=None, det_cls=None,
+                cls_thresh=0.5, max_range=20.0, cap=32, iters=8, min_points=50, min_pivot=1e-6, max_shift=2.0,
+                max_turn=0.05, eps_shift=1e-3, eps_turn=1e-5, out=None):
+    """N19: the pose of every sensor fitted to its occupancy grid below the size of a cell, one launch per batch
+    (include/pof_abi.h states the rules in full).
+
+    ranges [B,N] f32, the current scan; tab the angle table; rot [B,2,2] (or [B,4]) f32, trans [B,2] f64 and pose [B,3]
+    f64 = (x, y, phi), the sensor's pose at this scan as ``pose_advance`` (and ``grid_match``) leave it, all three
+    UPDATED IN PLACE when a sensor is moved.  ``state``: the ``GridMapState`` of ``grid_map_update``, read only; ``res``:
+    its metres per cell.  The endpoints of the points that vote (finite, 0 < r < ``max_range``, no point of a detection
+    of score >= ``cls_thresh`` when the NMS results instance_mask [B,N] i32, num_det [B] i32, det_cls [B,N] f64 are
+    given, all three or none) are fitted to the grid's counts, clamped to +-``cap``, scaled to [-1, 1] and interpolated
+    bilinearly between cell centres: up to ``iters`` Gauss-Newton updates of (x, y, phi), stopped early by an update
+    below ``eps_shift`` cells and ``eps_turn`` radians.  The fit is ``ok`` with at least ``min_points`` voting points
+    inside the grid at every evaluation and a 3 x 3 system whose pivots pass ``min_pivot`` (a corridor does not); the
+    sensor is ``moved`` when the correction stays within ``max_shift`` cells and ``max_turn`` radians and the mean
+    interpolated value under the scan rose.
+    -> ``GridRefine``: correction [B,3] f64 = what was added to (x, y, phi), zeros without ``moved``; score [B,2] f64 =
+    the mean interpolated value (before, after; after is NaN when not ``ok``); obs [B] f64, the smallest pivot over the
+    largest diagonal entry; votes, count (the voting points inside the grid at the incoming pose), iters_used [B] i32;
+    ok, moved [B] u8.  The same bits in every run.  ``out``: a ``GridRefine`` of preallocated tensors
+    (``grid_refine_buffers``)."""
+    ranges, tab, B, N, dev = _scan_input(ranges, tab)
+    _pose_input(B, rot, trans, pose)
+    gate = _nms_gate(instance_mask, num_det, det_cls, B, N, strict=True)
+    state, H, W = _grid_state(state, B)
+    grid_refine_check(cap, iters, min_points, min_pivot=min_pivot, max_shift=max_shift, max_turn=max_turn)
+    out = _out_of(GridRefine, out, dev, B=B)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_grid_refine", _ptr(ranges), _ptr(tab), *[_ptr(t) for t in gate], float(cls_thresh),
+                  float(max_range), _ptr(state.grid), _ptr(state.origin), float(res), int(cap), int(iters),
+                  int(min_points), float(min_pivot), float(max_shift), float(max_turn), float(eps_shift),
+                  float(eps_turn), B, N, H, W, _ptr(pose), _ptr(rot), _ptr(trans), *[_ptr(t) for t in out], _stream())
+    return out
+
+
 GridScrollState = _record("GridScrollState", persistent=dict(base=(_F64, "B", 2), offset=(_I32, "B", 2)),
                           scratch=(_I16, "B", "H", "W"))
 GridScroll = _record("GridScroll", shift=(_I32, "B", 2), scrolled=(_U8, "B"))

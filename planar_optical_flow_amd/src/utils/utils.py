@@ -593,7 +593,8 @@ class OccupancyGrid:
     ``reset(origin)``: every cell unknown; origin [2] = the world position of the grid's lower corner -- by default the
     next update puts its pose in the middle of the grid.  ``logodds`` is the grid [H,W] int16 on the host,
     ``probability(unit)`` the occupancy probability of a count worth ``unit`` nat.  ``localize(scan, odom, ...)``
-    corrects a pose against the grid as it stands (``ops.grid_match``) without updating it; ``cast(scan, odom, ...)``
+    corrects a pose against the grid as it stands (``ops.grid_match``) without updating it and ``refine(scan, odom,
+    ...)`` fits it below the size of a cell (``ops.grid_refine``), the caller updating afterwards; ``cast(scan, odom, ...)``
     ray-casts the grid as it stands along every beam (``ops.grid_cast``), to be called before the scan's ``update``;
     ``novel_segments(scan, odom, ...)`` does that and groups the NOVEL points into detections (``ops.novel_segments``);
     ``merged_detections(scan, odom, ...)`` does that and merges them with the NMS's (``ops.merge_detections``).
@@ -685,6 +686,31 @@ class OccupancyGrid:
         return _host(pose), dict(shift, best=_host(out.best), score=_host(out.score), votes=int(out.votes[0].item()),
                                  ok=bool(out.ok[0].item()), moved=bool(out.moved[0].item()),
                                  correction=_host(out.correction))
+
+    def refine(self, scan, odom, pred_cls=None, pred_reg=None, **settings):
+        """The pose ``odom`` = (x, y, phi) fitted to the grid as it stands below the size of a cell (``ops.grid_refine``,
+        one launch; ``settings``: its ``cap``, ``iters``, ``min_points``, ``min_pivot``, ``max_shift``, ``max_turn``,
+        ``eps_shift``, ``eps_turn``).  The grid is not updated: the caller enters the scan at the returned pose
+        afterwards.  With predictions the centre NMS runs first and people's points do not vote.
+        -> (the refined (x, y, phi) [3], dict of correction [3], score [2] = the mean interpolated grid value (before,
+        after), obs, votes, count, iters_used, ok and moved (bool))."""
+        _stage_kw(ops.grid_refine, "grid_refine", settings, "res", "cls_thresh", "max_range")
+        cur = _to_dev(scan, torch.float32).reshape(1, -1)
+        gate = {}
+        if pred_cls is not None and pred_reg is not None:
+            _, dc, num, inst, _ = _nms(cur, self._tab, pred_cls, pred_reg, self._min_dist)
+            gate = dict(instance_mask=inst, num_det=num, det_cls=dc)
+        pose = np.asarray(odom, dtype=np.float64).reshape(1, 3)
+        rot, trans, _ = _pose_terms(pose)
+        pose, trans = _to_dev(pose, torch.float64), _to_dev(trans, torch.float64)
+        shift = self._scrolled(trans)
+        shared = {k: self._kw[k] for k in ("cls_thresh", "max_range") if k in self._kw}
+        out = ops.grid_refine(cur, self._tab, _to_dev(rot, torch.float32), trans, pose, self._state, res=self.res,
+                              **gate, **shared, **settings)
+        return _host(pose), dict(shift, correction=_host(out.correction), score=_host(out.score),
+                                 obs=float(out.obs[0].item()), votes=int(out.votes[0].item()),
+                                 count=int(out.count[0].item()), iters_used=int(out.iters_used[0].item()),
+                                 ok=bool(out.ok[0].item()), moved=bool(out.moved[0].item()))
 
     def cast(self, scan, odom=None, pred_cls=None, pred_reg=None, **settings):
         """The scan the grid predicts at the pose ``odom`` = (x, y, phi), and what it says about every point of ``scan``

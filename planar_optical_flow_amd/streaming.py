@@ -13,7 +13,7 @@ float16 storage (float16 cutout and template).
 
 Behind the trunk (cutout, model, NMS) a scan runs the stages its detector was built with, always in this order and on
 one stream, so a capture stays one linear chain: the keyframe launch; the scan matcher and its pose launch; the
-grid scroll; the scan-to-grid match; the flow net; the flow fit and its pose launch; the per-person flow; the person motion; the track
+grid scroll; the scan-to-grid match; the grid refine; the flow net; the flow fit and its pose launch; the per-person flow; the person motion; the track
 update; the grid cast; the novelty segments; the grid map; the map check of the tracks; the copy of the scan into the previous-scan buffer.  The detector holds them as one table, built once: the eager step, a
 capture's warm-up and the captured region are each a loop over it, the warm-up puts back exactly the state the table names, and
 ``reset()`` clears exactly that ("The stage table").  The paragraphs below say what each stage is.
@@ -42,6 +42,9 @@ With ``grid_match`` (and ``method="scan_match"`` plus ``grid_map``) ``ops.grid_m
 matcher's pose launch: the scan is scored against the grid at whole-cell shifts and a few rotations
 around the pose, in integers, and a pose that has lost a scan pair is put back before any later stage reads it and
 before the scan is entered into the map.
+With ``grid_refine`` (and ``method="scan_match"`` plus ``grid_map``) ``ops.grid_refine`` stands directly behind that
+position: a Gauss-Newton fit of the scan's endpoints to the interpolated grid, every scan, that ties the
+dead-reckoned pose to the map below the size of a cell.
 With ``grid_scroll`` (and ``grid_map``) ``ops.grid_scroll`` stands behind the pose launch and in front of every stage
 that reads cells: a sensor that comes near a border of its grid has the grid shifted by whole tiles so
 that it stands on the middle tile again, origin included, on the device -- the map follows a sensor that travels.
@@ -58,7 +61,7 @@ With ``merge_detections`` (and ``novel_segments``) ``ops.merge_detections`` stan
 N18) and the cast, the segments and the merge move in front of the person stages: the segments the NMS's confident
 detections do not already hold are appended to the NMS's rows, and the person motion, the tracks, the map check of the
 tracks and (with ``gate_map``) the grid map read that one record -- a person the net scores low is tracked and not burned
-in.  The order is then: the pose launch; the grid scroll; the scan-to-grid match; the grid cast; the novelty segments; the
+in.  The order is then: the pose launch; the grid scroll; the scan-to-grid match; the grid refine; the grid cast; the novelty segments; the
 merge; the person motion; the track update; the grid map; the map check of the tracks; the copy of the scan.
 """
 import gc
@@ -78,7 +81,7 @@ _MATCHERS = {"scan_match": ops.scan_match, "keyframe": ops.keyframe_match, "keyf
 
 def stage_defaults(arg, cls_thresh=0.5, method="flow"):
     """What the dict given as the constructor argument ``arg`` ("ego_motion" with its ``method``, "tracks",
-    "person_motion", "grid_map", "grid_match", "grid_scroll", "track_map", "grid_cast", "novel_segments", "merge_detections") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
+    "person_motion", "grid_map", "grid_match", "grid_refine", "grid_scroll", "track_map", "grid_cast", "novel_segments", "merge_detections") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
     signature has them (``ops.stage_settings``), and -- stated here and nowhere else -- what the detector overrides or
     adds.  ``cls_thresh``: the detector's."""
     if arg == "ego_motion" and method == "flow":
@@ -111,11 +114,12 @@ def stage_defaults(arg, cls_thresh=0.5, method="flow"):
         kw = ops.stage_settings({"grid_scroll": ops.grid_scroll, "grid_cast": ops.grid_cast}[arg])
         del kw["res"]                                          # the grid's: a key of grid_map's dict
         return kw
-    # person_motion, grid_map and grid_match always take the detector's cls_thresh: it is not a key of their dicts
+    # person_motion, grid_map, grid_match and grid_refine always take the detector's cls_thresh: it is not a key of
+    # their dicts
     kw = ops.stage_settings({"person_motion": ops.person_motion, "grid_map": ops.grid_map_update,
-                             "grid_match": ops.grid_match}[arg])
+                             "grid_match": ops.grid_match, "grid_refine": ops.grid_refine}[arg])
     del kw["cls_thresh"]
-    if arg == "grid_match":
+    if arg in ("grid_match", "grid_refine"):
         del kw["res"]                                          # the grid's: a key of grid_map's dict
     return dict(kw, res=0.1, size=512) if arg == "grid_map" else kw
 
@@ -199,6 +203,15 @@ class StreamingDetector:
     stages and the grid update read the pose.  ``grid_match()`` returns what was found; ``reset()`` needs nothing new
     (an empty grid scores 0 and moves nothing).
 
+    ``grid_refine`` (needs ``grid_map`` and ``ego_motion=dict(method="scan_match")``, with or without ``grid_match``;
+    with ``"keyframe"``, ``"keyframe_map"``, a pose per call or a ``flow_model`` it is refused, not built): None, or a
+    dict of ``cap`` (32), ``iters`` (8), ``min_points`` (50), ``min_pivot`` (1e-6), ``max_shift`` (2.0 cells),
+    ``max_turn`` (0.05 rad), ``eps_shift`` (1e-3 cells), ``eps_turn`` (1e-5 rad) and ``max_range`` of
+    ``ops.grid_refine``.  Every step, the first of a sequence included, then fits the dead-reckoned pose to the
+    sensor's grid below the size of a cell, directly behind ``grid_match``'s position and in front of every stage that
+    reads the pose terms: the slow drift of a pose composed from scan pairs does not reach the map.
+    ``grid_refine()`` returns the fit; ``reset()`` needs nothing new (an empty grid is not ok and moves nothing).
+
     ``grid_scroll`` (needs ``grid_map``; works with every way that argument gets its pose, ``det(scan, pose=...)``
     included): None, or a dict of ``margin`` (None: a quarter of the grid's shorter side in whole tiles of 64 cells) of
     ``ops.grid_scroll``.  Every step, the first of a sequence included, then looks where the sensor stands in its grid,
@@ -256,7 +269,7 @@ class StreamingDetector:
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
                  nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None,
                  grid_map=None, grid_match=None, grid_scroll=None, track_map=None, grid_cast=None,
-                 novel_segments=None, merge_detections=None):
+                 novel_segments=None, merge_detections=None, grid_refine=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -290,6 +303,7 @@ class StreamingDetector:
         # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
         self._gm_kw = self._sg_kw = self._gs_kw = self._tm_kw = self._gc_kw = self._ns_kw = self._mg_kw = None
+        self._gr_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
@@ -310,6 +324,12 @@ class StreamingDetector:
                                  "'keyframe', 'keyframe_map' or det(scan, pose=...) it is not built")
             if flow_model is not None:
                 raise ValueError("grid_match with a flow_model is not built: flow_trans is not corrected")
+        if grid_refine is not None:
+            if grid_map is None or method != "scan_match" or ego_motion is None:
+                raise ValueError("grid_refine fits the pose of ego_motion method='scan_match' to grid_map: with "
+                                 "'keyframe', 'keyframe_map' or det(scan, pose=...) it is not built")
+            if flow_model is not None:
+                raise ValueError("grid_refine with a flow_model is not built: flow_trans is not corrected")
         if grid_scroll is not None and grid_map is None:
             raise ValueError("grid_scroll scrolls the grid of grid_map: give both")
         if grid_cast is not None and grid_map is None:
@@ -405,6 +425,17 @@ class StreamingDetector:
                     raise ValueError("grid_match %s must be >= 0" % k)
             self._sg_kw = dict(kw, cls_thresh=self._cls_thresh)
             stages.append(Stage(self._grid_match_stage))
+        if grid_refine is not None:
+            # directly behind grid_match's position -- behind the pose launch and the scroll, and behind the whole-cell
+            # search where that runs -- and in front of every stage that reads the pose terms.  Like grid_match it reads
+            # self._gm_state when it runs and advances nothing but the pose, which is in the match stage's snapshot;
+            # from an empty grid it is not ok
+            kw = stage_settings("grid_refine", grid_refine)
+            ops.grid_refine_check(kw["cap"], kw["iters"], kw["min_points"], min_pivot=kw["min_pivot"],
+                              max_shift=kw["max_shift"], max_turn=kw["max_turn"])
+            self._gr_out = ops.grid_refine_buffers(self.B, dev)
+            self._gr_kw = dict(kw, cls_thresh=self._cls_thresh)
+            stages.append(Stage(self._grid_refine_stage))
         def cast_stages():
             # the grid cast, the novelty segments and the merge: directly in front of the grid map, or with
             # merge_detections in front of the person stages, which then read the merged record; the grid is allocated
@@ -674,6 +705,12 @@ class StreamingDetector:
                        res=self._gm_kw["res"], table=self._sg_table, out=self._sg_out, **self._match_gate(),
                        **self._sg_kw)
 
+    # Behind grid_match's position and in front of everything that reads the pose terms: the pose fitted to the grid as
+    # the scans before this one left it, below the size of a cell.
+    def _grid_refine_stage(self, first):
+        ops.grid_refine(self._scan[:, 0], self.tab, self._pose_rot, self._pose_trans, self._pose_state, self._gm_state,
+                        res=self._gm_kw["res"], out=self._gr_out, **self._match_gate(), **self._gr_kw)
+
     # Behind the pose launch and in front of every stage that reads cells: the grid follows the sensor.
     def _grid_scroll_stage(self, first):
         ops.grid_scroll(self._pose_trans, self._gm_state, self._gs_state, res=self._gm_kw["res"], out=self._gs_out,
@@ -841,6 +878,19 @@ class StreamingDetector:
         h = {k: getattr(o, k).cpu().numpy() for k in ("best", "score", "votes", "ok", "moved", "correction")}
         return [{"best": h["best"][b], "score": h["score"][b], "votes": int(h["votes"][b]), "ok": bool(h["ok"][b]),
                  "moved": bool(h["moved"][b]), "correction": h["correction"][b]} for b in range(self.B)], o
+
+    def grid_refine(self):
+        """-> (list with one dict per sensor of the last step's fit to the grid: correction [3] = what was added to
+        (x, y, phi), score [2] = the mean interpolated grid value under the scan (before, after), obs, votes, count,
+        iters_used, ok and moved;  the device-resident ``ops.GridRefine``, valid until the next call).  Needs
+        ``grid_refine`` and one scan.  Synchronises."""
+        if self._gr_kw is None or self._seen < 1:
+            raise RuntimeError("construct the detector with grid_refine and feed it a scan first")
+        o = self._gr_out
+        h = {k: getattr(o, k).cpu().numpy() for k in o._fields}
+        return [{"correction": h["correction"][b], "score": h["score"][b], "obs": float(h["obs"][b]),
+                 "votes": int(h["votes"][b]), "count": int(h["count"][b]), "iters_used": int(h["iters_used"][b]),
+                 "ok": bool(h["ok"][b]), "moved": bool(h["moved"][b])} for b in range(self.B)], o
 
     def grid_scroll(self):
         """-> (list with one dict per sensor of the last step's scroll: shift [2] = this step's shift in tiles of 64

@@ -1,5 +1,5 @@
 """Per-kernel timing on the GPU box (events on torch's current stream, which is the
-stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [gridscroll] [cast] [novel] [merge] ..."""
+stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [refine] [gridscroll] [cast] [novel] [merge] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -234,7 +234,7 @@ if "person" in which:
             % (M, ms_tm[M], ms_t[M], (tm_state[M].ev_scans > 0).sum().item() / B,
                tm_out[M].class_count.sum(dim=0).tolist()) for M in tracks))
 
-if which & {"grid", "gridmatch", "gridscroll", "cast", "novel", "merge"}:
+if which & {"grid", "gridmatch", "refine", "gridscroll", "cast", "novel", "merge"}:
     # N12: the occupancy grid map, 450 beams into 512 x 512 cells of 0.1 m per sensor, for 1024, 8 and 1 sensors, next
     # to person_motion on the same scans, NMS results and pose (alternating, three repeats of 50 launches).  The same
     # scan every call, with lo / hi at the int16 limits so that no cell saturates inside the run and every launch
@@ -245,6 +245,12 @@ if which & {"grid", "gridmatch", "gridscroll", "cast", "novel", "merge"}:
     # so that the search reads the same cells every call), defaults: 9 rotations x 81 translations.  The pose starts
     # off by (0.23, -0.17) m and 0.02 rad; a moved pose stays moved, so from the second launch on the search starts
     # where the first one ended (the work of a launch does not depend on it).  Gathers: 9 * 81 * votes int16.
+    # refine: N19 next to grid_match and scan_match, alternating, on the same scans, NMS results and grid (a copy, as two
+    # updates left it, cloned before any other sub-command updates it again: every burned-in cell holds 34, above the
+    # cap of 32, every freed cell -16).  Every launch starts from the map's pose
+    # moved by (0.03, -0.02) m and 0.004 rad: three small copies on the stream put pose, rot and trans back in front
+    # of it, timed on their own as well.  scan_match: the previous scan is the same scene with range noise of its own,
+    # every pair from rest, defaults.  Gathers: 4 * (iters_used + 1) * count int16.
     # gridscroll: N14 next to grid_map_update on a copy of the same grid, two cases.  `stays`: the sensor in the middle
     # of its grid as it stands, what every step pays (two launches that leave at once).  `scrolls`: every sensor scrolls
     # in every call -- the position alternates between tile 7 of 8 and, seen from the grid so scrolled, tile 1, on both
@@ -285,6 +291,7 @@ if which & {"grid", "gridmatch", "gridscroll", "cast", "novel", "merge"}:
         grid()
         runs = int((gm_state.grid != before).view(B, H, W // 8, 8).any(dim=3).sum().item())
         touched = (gm_state.grid != 0).view(B, H // 64, 64, W // 64, 64).any(dim=4).any(dim=2).float().mean().item()
+        two_updates = gm_state.grid.clone()                    # the grid as these two updates left it, for `refine`
         del before
         if "gridmatch" in which:
             sg_state = ops.GridMapState(gm_state.grid.clone(), gm_state.origin.clone())
@@ -304,6 +311,45 @@ if which & {"grid", "gridmatch", "gridscroll", "cast", "novel", "merge"}:
                       "of %d" % (B, N, H, W, RES, ms_m, ms_m / B * 1e3, ms_g, sg_out.votes.sum().item() / B,
                                  9 * 81 * sg_out.votes.sum().item() / 1e6, first[1], first[0], B))
             del sg_state
+        if "refine" in which:
+            gr_state = ops.GridMapState(two_updates, gm_state.origin.clone())
+            gr_out, sg_out = ops.grid_refine_buffers(B, dev), ops.grid_match_buffers(B, device=dev)
+            sg_table, sm_out = ops.grid_match_table(device=dev), ops.scan_match_buffers(B, N, dev)
+            prev = torch.from_numpy(synth.make_batch(seed=3, B=B, T=2).scans[:, 1].copy()).to(dev)
+            off = torch.tensor([0.03, -0.02, 0.004], dtype=torch.float64, device=dev)
+            pose0 = torch.cat([trans, torch.from_numpy(ang).to(dev)[:, None]], dim=1) + off
+            rot0 = torch.stack([pose0[:, 2].cos(), -pose0[:, 2].sin(), pose0[:, 2].sin(), pose0[:, 2].cos()], 1).float().contiguous()
+            trans0 = pose0[:, :2].contiguous()
+            pose, gr_rot, gr_trans = pose0.clone(), rot0.clone(), trans0.clone()
+
+            def put_back():
+                pose.copy_(pose0); gr_rot.copy_(rot0); gr_trans.copy_(trans0)
+
+            def refine():
+                put_back()
+                ops.grid_refine(scans, tab, gr_rot, gr_trans, pose, gr_state, res=RES, instance_mask=inst, num_det=num,
+                                det_cls=dc, out=gr_out)
+
+            def whole_cell():
+                put_back()
+                ops.grid_match(scans, tab, gr_rot, gr_trans, pose, gr_state, res=RES, table=sg_table, instance_mask=inst,
+                               num_det=num, det_cls=dc, out=sg_out)
+
+            pair = lambda: ops.scan_match(prev, scans, tab, instance_mask=inst, num_det=num, det_cls=dc, out=sm_out)
+            refine()
+            left = (pose - (pose0 - off))[gr_out.moved.bool()].abs().max(dim=0).values.tolist() if gr_out.moved.any() else []
+            for rep in range(3):
+                ms_r, ms_m, ms_s, ms_c = (timeit(f, iters=50) for f in (refine, whole_cell, pair, put_back))
+                print("refine B=%d N=%d %dx%d at %.2f m: grid_refine %.3f ms (%.2f us per sensor) next to grid_match %.3f ms "
+                      "and scan_match %.3f ms (%.1f iterations per pair); the three copies in front of the first two "
+                      "%.3f ms; %.0f voting points per scan, %.0f inside, %.2f updates per sensor, %.2f M int16 gathers per "
+                      "launch; ok %d, moved %d of %d, left of the offset %s"
+                      % (B, N, H, W, RES, ms_r, ms_r / B * 1e3, ms_m, ms_s, sm_out.iters_used.float().mean().item(), ms_c,
+                         gr_out.votes.sum().item() / B, gr_out.count.sum().item() / B,
+                         gr_out.iters_used.float().mean().item(),
+                         4 * ((gr_out.iters_used + 1) * gr_out.count).sum().item() / 1e6, gr_out.ok.sum().item(),
+                         gr_out.moved.sum().item(), B, ["%.4f" % v for v in left]))
+            del gr_state
         if "gridscroll" in which:
             gs_state = ops.GridMapState(gm_state.grid.clone(), gm_state.origin.clone())
             gs_scroll = ops.grid_scroll_reset(ops.grid_scroll_state(B, H, W, dev), gs_state)

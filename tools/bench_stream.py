@@ -1,5 +1,5 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-scroll] [--grid-cast] [--novel] [--merge] [--track-map]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-refine] [--grid-scroll] [--grid-cast] [--novel] [--merge] [--track-map]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
@@ -21,6 +21,8 @@ grid_map=dict() (512 x 512 cells of 0.1 m per sensor) as its last stage, alterna
 --grid-match (with --grid): two more steps in the same process, ego_motion=dict(method="scan_match") with grid_map=dict()
 and that one with grid_match=dict() behind the scan matcher, so one process gives the map step without and with the
 scan-to-grid match.
+--grid-refine (with --grid): the scan_match + grid_map step (and with --grid-match the one with grid_match=dict()) once more
+with grid_refine=dict() behind the pose launch, so one process gives those steps without and with the grid refine.
 --grid-scroll (with --grid): one more step in the same process, the keyframe step with grid_map=dict() and
 grid_scroll=dict() behind the keyframe launch, so one process gives the map step without and with the scrolling grid.
 --grid-cast (with --grid): one more step in the same process, the keyframe step with grid_map=dict() and
@@ -58,6 +60,7 @@ KEYED = ("keyframe", "keyframe_map")
 TRACKS = "--tracks" in sys.argv
 GRID = "--grid" in sys.argv
 GRID_MATCH = "--grid-match" in sys.argv
+GRID_REFINE = "--grid-refine" in sys.argv
 GRID_SCROLL = "--grid-scroll" in sys.argv
 GRID_CAST = "--grid-cast" in sys.argv
 NOVEL = "--novel" in sys.argv
@@ -119,6 +122,13 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
                 reckoned, corrected = mk(ego_motion=MATCH, grid_map=dict()), mk(ego_motion=MATCH, grid_map=dict(), grid_match=dict())
                 steps["scan_match + grid_map"] = lambda t: reckoned(scans[:, t])
                 steps["scan_match + grid_map + grid_match"] = lambda t: corrected(scans[:, t])
+            if GRID_REFINE:
+                if not GRID_MATCH:
+                    reckoned = mk(ego_motion=MATCH, grid_map=dict())
+                    steps["scan_match + grid_map"] = lambda t: reckoned(scans[:, t])
+                kw = dict(grid_match=dict()) if GRID_MATCH else {}
+                refined = mk(ego_motion=MATCH, grid_map=dict(), grid_refine=dict(), **kw)
+                steps["scan_match + grid_map + %sgrid_refine" % ("grid_match + " if GRID_MATCH else "")] = lambda t: refined(scans[:, t])
         elif TRACKS:
             kw = dict(ego_motion={"scan_match": MATCH, "keyframe": KEYFRAME, "keyframe_map": KEYFRAME_MAP}.get(EGO_METHOD, dict())) if EGO else {}
             plain, tracked = mk(tracks=None, **kw), mk(tracks=dict(), **kw)
@@ -222,6 +232,11 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             print("   grid_match at the last scan: votes %s, score per voting point %s, ok %s, moved %s"
                   % ([f["votes"] for f in found], ["%.1f" % (f["score"][0] / max(f["votes"], 1)) for f in found],
                      [f["ok"] for f in found], [f["moved"] for f in found]))
+        if GRID and GRID_REFINE:
+            found, _ = refined.grid_refine()
+            print("   grid_refine at the last scan: votes %s, inside %s, updates %s, score before and after %s, ok %s, moved %s"
+                  % ([f["votes"] for f in found], [f["count"] for f in found], [f["iters_used"] for f in found],
+                     [["%.3f" % v for v in f["score"]] for f in found], [f["ok"] for f in found], [f["moved"] for f in found]))
         if TRACKS and not GRID:
             live, _, state = tracked.tracks()
             print("   tracks after 40 scans: %s live, next_id %s" % ([len(l) for l in live], state.next_id.tolist()))
