@@ -770,6 +770,47 @@ int pof_grid_scroll(const double *trans, double res, int margin, int B, int H, i
                     pof_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * N20 tile store behind the scrolling grid: N14's scroll, and what scrolls out of the window is kept per sensor in a
+ * store of S = `slots` tiles of 64 x 64 cells, so that a return to a mapped place puts the old cells back under the
+ * sensor.  The shift rule and everything N14 writes are N14's, word for word: s_x and s_y, the caps, offset, origin
+ * from base, the surviving cells, shift and scrolled.  The reference has nothing of the kind; the specification is
+ * this comment (restated in NumPy by tests/test_grid_store.py).  One sensor per batch entry, three launches on the
+ * stream (stage, plan, commit).
+ * State per sensor beside N14's (grid, origin, base, offset, the workspace scratch), every field persistent and all
+ *   zeros after a reset:  store [B][S][64][64] int16;  store_key [B][S][2] int32, the world tile (x, y) a slot holds;
+ *   store_stamp [B][S] int32, 0 = the slot is free, else the value of clock at the scroll that wrote it;  clock [B]
+ *   int32, the scrolls made since the reset.  Workspaces whose content means nothing between calls: plan_in and
+ *   plan_out [B][H / 64 * W / 64] int32.
+ * World tile: window tile (tx, ty) under offset o is world tile o + (tx, ty); N14's cap keeps it inside int32.
+ * A call with the shift s = (s_x, s_y) != 0, o the offset before it, o' = o + s, TW = W / 64, TH = H / 64:
+ *   Arriving tiles: the destination tiles (tx, ty) whose source (tx + s_x, ty + s_y) lies outside the window; world
+ *     tile k = o' + (tx, ty).  With a slot j that has store_stamp != 0 and store_key = k -- the lowest such j --
+ *     grid'[tile] = store[j] and slot j is RELEASED; otherwise the tile is 0 as in N14.  restored = their number.
+ *   Departing tiles: the source tiles (tx, ty) whose destination (tx - s_x, ty - s_y) lies outside the window; world
+ *     tile k = o + (tx, ty).  One whose cells are all 0 is not stored (unknown needs no slot); the others are ranked
+ *     in ascending tile index ty TW + tx.
+ *   Slot order: the effective stamp of a slot is 0 when it was free before the call or is released by it, else its
+ *     store_stamp; the slots are ordered by (effective stamp, slot index), ascending -- free slots first, then the
+ *     oldest (first in, first out).
+ *   Assignment: the r-th ranked departing tile takes the r-th slot of that order, r < S: its 4096 cells are copied
+ *     there bit for bit, store_key = k, store_stamp = clock + 1.  stored = the tiles placed, evicted = those among
+ *     them whose slot had a non-zero effective stamp, dropped = the ranked tiles with r >= S.
+ *   A released slot that nothing took ends with store_stamp = 0.  clock += 1.
+ *   A world tile is in the window or in the store, never in both.
+ * Without a shift nothing is stored to any state field.
+ * Outputs, always written: N14's shift [B][2] int32 and scrolled [B] uint8; counts [B][4] int32 = (restored, stored,
+ *   evicted, dropped), zeros without a shift.
+ * Integers and bitwise copies, no atomics, no floating point beyond N14's two divisions: the same bits in every run,
+ *   at every batch position and in a graph replay.
+ * POF_E_BADARG (nothing written): a NULL pointer, slots outside [1, 1024], and N14's.  POF_E_SHAPE (nothing written):
+ *   N14's, and a store that is not 16-byte aligned.  B = 0 is POF_OK.
+ * ---------------------------------------------------------------------- */
+int pof_grid_scroll_store(const double *trans, double res, int margin, int slots, int B, int H, int W, int16_t *grid,
+                          double *origin, const double *base, int32_t *offset, int16_t *scratch, int16_t *store,
+                          int32_t *store_key, int32_t *store_stamp, int32_t *clock, int32_t *plan_in,
+                          int32_t *plan_out, int32_t *shift, uint8_t *scrolled, int32_t *counts, pof_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * N15 map-checked tracks: per-track evidence from the occupancy grid.  The detection row of the NMS is a rank that
  * changes with every scan and only a track (N7) carries identity over time; this stage joins what the grid (N12) says
  * about the row a track was matched with to the track's slot, sums it there, and derives a class per track: a walker's

@@ -61,6 +61,7 @@ SIGNATURES = {
     "pof_grid_match": (_i, [_p] * 5 + [_d] * 2 + [_p] * 2 + [_d, _p] + [_i] * 9 + [_p] * 11),
     "pof_grid_refine": (_i, [_p] * 5 + [_d] * 2 + [_p] * 2 + [_d] + [_i] * 3 + [_d] * 5 + [_i] * 4 + [_p] * 12),
     "pof_grid_scroll": (_i, [_p, _d] + [_i] * 4 + [_p] * 8),
+    "pof_grid_scroll_store": (_i, [_p, _d] + [_i] * 5 + [_p] * 15),
     "pof_track_map": (_i, [_p] * 9 + [_i] * 3 + [_p] * 12 + [_i] * 5 + [_d, _i, _p]),
     "pof_grid_cast": (_i, [_p] * 9 + [_d] * 3 + [_i] * 6 + [_p] * 12),
     "pof_novel_segments": (_i, [_p] * 6 + [_d, _d, _i, _i, _d, _i, _i] + [_p] * 11),

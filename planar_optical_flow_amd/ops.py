@@ -1778,6 +1778,18 @@ def grid_scroll(trans, state, scroll, *, res, margin=None, out=None):
     it, and a grid that does not scroll keeps every bit.
     -> ``GridScroll``: shift [B,2] i32 = the shift of this call in tiles (x, y), scrolled [B] u8.  The same bits in every
     run.  ``out``: a ``GridScroll`` of preallocated tensors (``grid_scroll_buffers``)."""
+    trans, state, scroll, B, H, W, dev = _scroll_input(trans, state, scroll)
+    out = _out_of(GridScroll, out, dev, B=B)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.call("pof_grid_scroll", _ptr(trans), float(res), int(grid_scroll_margin(H, W) if margin is None else margin),
+                  B, H, W, *[_ptr(t) for t in state], *[_ptr(t) for t in scroll], *[_ptr(t) for t in out], _stream())
+    return out
+
+
+def _scroll_input(trans, state, scroll):
+    """What ``grid_scroll`` and ``grid_scroll_store`` take alike, checked -> (trans, state, scroll, B, H, W, device)."""
     if trans is None:
         raise TypeError("trans must be a tensor on the HIP device (no CPU path)")
     trans = _dev(trans, torch.float64, "trans")
@@ -1785,13 +1797,74 @@ def grid_scroll(trans, state, scroll, *, res, margin=None, out=None):
         raise ValueError("trans must be [B,2]")
     B, dev = trans.shape[0], trans.device
     state, H, W = _grid_state(state, B)
-    scroll = _checked(GridScrollState, scroll, "scroll", B=B, H=H, W=W)
-    out = _out_of(GridScroll, out, dev, B=B)
+    return trans, state, _checked(GridScrollState, scroll, "scroll", B=B, H=H, W=W), B, H, W, dev
+
+
+# the store of tiles behind the window carries over from scan to scan; "S" slots, "tiles" = H / 64 * W / 64
+GridStoreState = _record("GridStoreState",
+                         persistent=dict(store=(_I16, "B", "S", 64, 64), store_key=(_I32, "B", "S", 2),
+                                         store_stamp=(_I32, "B", "S"), clock=(_I32, "B")),
+                         plan_in=(_I32, "B", "tiles"), plan_out=(_I32, "B", "tiles"))
+GridScrollStore = _record("GridScrollStore", shift=(_I32, "B", 2), scrolled=(_U8, "B"), counts=(_I32, "B", 4))
+GRID_STORE_MAX_SLOTS = 1024
+
+
+def grid_store_slots(slots):
+    """The ``slots`` setting of the tile store, in [1, 1024], or this raises: what wraps the stage checks its setting
+    here, before anything is allocated."""
+    if not 1 <= int(slots) <= GRID_STORE_MAX_SLOTS:
+        raise ValueError("slots must be in [1, %d]" % GRID_STORE_MAX_SLOTS)
+    return int(slots)
+
+
+def grid_scroll_store_buffers(B, device="cuda"):
+    """The three outputs of ``grid_scroll_store`` for B sensors, zero-filled, as its ``out=`` (allocate once, before a
+    graph capture)."""
+    return _zeros_of(GridScrollStore, device, B=B)
+
+
+def grid_store_state(B, H, W, slots, device="cuda"):
+    """The tile store of ``grid_scroll_store`` for B sensors with grids of H x W cells: ``slots`` tiles of 64 x 64 cells
+    per sensor (8 KiB each) with their keys and stamps, the scroll clock, and the plan workspace of the launches, all
+    zeros -- an empty store (allocate once, before a graph capture).  -> ``GridStoreState``."""
+    H, W = grid_shape((H, W))
+    return _zeros_of(GridStoreState, device, B=B, S=grid_store_slots(slots), tiles=(H // 64) * (W // 64))
+
+
+def grid_store_reset(store):
+    """Empties the store: store_stamp <- 0 and clock <- 0, in place, with tensor ops on the current stream (no host
+    sync).  Call it with every ``grid_scroll_reset``: the keys count tiles from the origin that one sets."""
+    store = GridStoreState(*store)
+    store.store_stamp.zero_()
+    store.clock.zero_()
+    return store
+
+
+def grid_scroll_store(trans, state, scroll, store, *, res, margin=None, out=None):
+    """N20: ``grid_scroll`` with a store of tiles behind the window, three launches per batch (include/pof_abi.h states
+    the rule in full).
+
+    trans, ``state``, ``scroll``, ``res`` and ``margin`` are ``grid_scroll``'s, and so is all it does to them: the
+    shift, the offset, the origin and the cells that stay inside.  ``store``: a ``GridStoreState``
+    (``grid_store_state``), UPDATED IN PLACE.  A tile that leaves the window and is not all unknown is copied into a
+    slot of the store under its world tile -- free slots first, then the slot written longest ago -- and a tile that
+    scrolls in is looked up there: found, its cells come back bit for bit and its slot is released; not found, it is
+    unknown (0) as in ``grid_scroll``.
+    -> ``GridScrollStore``: shift [B,2] i32, scrolled [B] u8, counts [B,4] i32 = (restored, stored, evicted, dropped)
+    tiles of this call.  The same bits in every run.  ``out``: a ``GridScrollStore`` of preallocated tensors
+    (``grid_scroll_store_buffers``)."""
+    trans, state, scroll, B, H, W, dev = _scroll_input(trans, state, scroll)
+    if not isinstance(store[0], torch.Tensor) or store[0].dim() != 4:
+        raise TypeError("store.store must be a [B,S,64,64] tensor on the HIP device (no CPU path)")
+    S = store[0].shape[1]
+    store = _checked(GridStoreState, store, "store", B=B, S=grid_store_slots(S), tiles=(H // 64) * (W // 64))
+    out = _out_of(GridScrollStore, out, dev, B=B)
     if B == 0:
         return out
     with torch.cuda.device(dev):
-        _lib.call("pof_grid_scroll", _ptr(trans), float(res), int(grid_scroll_margin(H, W) if margin is None else margin),
-                  B, H, W, *[_ptr(t) for t in state], *[_ptr(t) for t in scroll], *[_ptr(t) for t in out], _stream())
+        _lib.call("pof_grid_scroll_store", _ptr(trans), float(res),
+                  int(grid_scroll_margin(H, W) if margin is None else margin), S, B, H, W, *[_ptr(t) for t in state],
+                  *[_ptr(t) for t in scroll], *[_ptr(t) for t in store], *[_ptr(t) for t in out], _stream())
     return out
 
 

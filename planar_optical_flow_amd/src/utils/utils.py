@@ -602,12 +602,26 @@ class OccupancyGrid:
     (``ops.grid_scroll``, two more launches in front of ``update`` and ``localize``): within ``margin`` cells of a border
     (None: a quarter of the shorter side in whole tiles) it is shifted by whole tiles of 64 cells so that the sensor
     stands on the middle tile again.  The result dicts then hold ``shift`` [2] = this call's shift in tiles (x, y),
-    ``offset`` is the shift since the last reset [2] and ``origin`` moves with it."""
+    ``offset`` is the shift since the last reset [2] and ``origin`` moves with it.
+    ``store=dict(slots=64)`` (needs ``scroll``; None: what leaves the grid is gone): a store of ``slots`` tiles behind the
+    grid (``ops.grid_scroll_store`` in the place of ``ops.grid_scroll``, three launches): a tile that scrolls out and is
+    not all unknown is kept, first in free slots and then in the one written longest ago, and a tile that scrolls in
+    comes back from there bit for bit, so a return to a mapped place finds its map.  The result dicts then also hold
+    ``store_counts`` [4] = this call's (restored, stored, evicted, dropped) tiles, ``store_tiles`` is the number of
+    tiles in the store, and ``reset`` empties it."""
 
-    def __init__(self, scan_phi, res=0.1, size=512, scroll=None, **kw):
+    def __init__(self, scan_phi, res=0.1, size=512, scroll=None, store=None, **kw):
         # the settings first: a wrong one raises before anything touches the device
         self._min_dist = kw.pop("min_dist", 0.5)
         self._scroll_kw = None if scroll is None else dict(_stage_kw(ops.grid_scroll, "scroll", dict(scroll), "res"))
+        self._store = None
+        if store is not None:
+            if scroll is None:
+                raise ValueError("store keeps what scroll moves out of the grid: give both")
+            store = dict({"slots": 64}, **store)
+            if set(store) != {"slots"}:
+                raise ValueError("unknown store settings: %s" % sorted(set(store) - {"slots"}))
+            slots = ops.grid_store_slots(store["slots"])
         _stage_kw(ops.grid_map_update, "grid_map", kw, "res")
         self.res = float(res)
         if not self.res > 0.0:
@@ -624,6 +638,9 @@ class OccupancyGrid:
         if self._scroll_kw is not None:
             self._scroll = ops.grid_scroll_state(1, *self.shape, self._tab.device)
             self._scroll_out = ops.grid_scroll_buffers(1, self._tab.device)
+        if store is not None:
+            self._store = ops.grid_store_state(1, *self.shape, slots, self._tab.device)
+            self._scroll_out = ops.grid_scroll_store_buffers(1, self._tab.device)
 
     def reset(self, origin=None):
         self._reset(origin)
@@ -633,11 +650,18 @@ class OccupancyGrid:
         ops.grid_map_reset(self._state, origin)
         if self._scroll_kw is not None:
             ops.grid_scroll_reset(self._scroll, self._state)
+        if self._store is not None:
+            ops.grid_store_reset(self._store)
 
     def _scrolled(self, trans):
-        """With ``scroll``: the grid follows the sensor at trans [1,2] (device) -> {"shift": [2]}; else {}."""
+        """With ``scroll``: the grid follows the sensor at trans [1,2] (device) -> {"shift": [2]}, with ``store`` also
+        "store_counts": [4]; else {}."""
         if self._scroll_kw is None:
             return {}
+        if self._store is not None:
+            out = ops.grid_scroll_store(trans, self._state, self._scroll, self._store, res=self.res, out=self._scroll_out,
+                                        **self._scroll_kw)
+            return {"shift": _host(out.shift), "store_counts": _host(out.counts)}
         out = ops.grid_scroll(trans, self._state, self._scroll, res=self.res, out=self._scroll_out, **self._scroll_kw)
         return {"shift": _host(out.shift)}
 
@@ -813,6 +837,11 @@ class OccupancyGrid:
     def offset(self):
         """The shift since the last reset in tiles of 64 cells [2] = (x, y); zeros without ``scroll``."""
         return _host(self._scroll.offset) if self._scroll_kw is not None else np.zeros(2, np.int32)
+
+    @property
+    def store_tiles(self):
+        """The tiles the store holds; 0 without ``store``."""
+        return int((self._store.store_stamp != 0).sum().item()) if self._store is not None else 0
 
     @property
     def logodds(self):

@@ -48,6 +48,9 @@ dead-reckoned pose to the map below the size of a cell.
 With ``grid_scroll`` (and ``grid_map``) ``ops.grid_scroll`` stands behind the pose launch and in front of every stage
 that reads cells: a sensor that comes near a border of its grid has the grid shifted by whole tiles so
 that it stands on the middle tile again, origin included, on the device -- the map follows a sensor that travels.
+With ``grid_store`` (and ``grid_scroll``) that launch is ``ops.grid_scroll_store``: the tiles that scroll
+out are kept in a store per sensor and come back bit for bit when the sensor returns, so the map behind the window is
+as large as the store and a return finds it.
 With ``track_map`` (and ``tracks`` plus ``grid_map``) ``ops.track_map`` stands behind the grid map: what
 the grid says about the detection a track was matched with is summed per track slot on the device, and every track has
 a class -- free-standing, unsupported, background -- that an intermittent false positive on a static object cannot shed.
@@ -81,7 +84,7 @@ _MATCHERS = {"scan_match": ops.scan_match, "keyframe": ops.keyframe_match, "keyf
 
 def stage_defaults(arg, cls_thresh=0.5, method="flow"):
     """What the dict given as the constructor argument ``arg`` ("ego_motion" with its ``method``, "tracks",
-    "person_motion", "grid_map", "grid_match", "grid_refine", "grid_scroll", "track_map", "grid_cast", "novel_segments", "merge_detections") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
+    "person_motion", "grid_map", "grid_match", "grid_refine", "grid_scroll", "grid_store", "track_map", "grid_cast", "novel_segments", "merge_detections") may hold, with the defaults: the settings of the ``ops`` wrapper behind it, as its
     signature has them (``ops.stage_settings``), and -- stated here and nowhere else -- what the detector overrides or
     adds.  ``cls_thresh``: the detector's."""
     if arg == "ego_motion" and method == "flow":
@@ -110,6 +113,8 @@ def stage_defaults(arg, cls_thresh=0.5, method="flow"):
         kw = ops.stage_settings(ops.merge_detections)
         del kw["cls_thresh"]
         return dict(kw, gate_map=True)
+    if arg == "grid_store":
+        return dict(slots=64)                                  # the size of ops.grid_store_state, not a wrapper's keyword
     if arg in ("grid_scroll", "grid_cast"):
         kw = ops.stage_settings({"grid_scroll": ops.grid_scroll, "grid_cast": ops.grid_cast}[arg])
         del kw["res"]                                          # the grid's: a key of grid_map's dict
@@ -220,6 +225,14 @@ class StreamingDetector:
     middle one again, and what scrolls in is unknown.  ``grid_scroll()`` returns the shift; ``reset()`` puts the grid
     back around the start pose and clears the offset.
 
+    ``grid_store`` (needs ``grid_scroll``): None, or a dict of ``slots`` (64, in [1, 1024]), the tiles of 64 x 64 cells
+    (8 KiB each) kept per sensor behind the grid.  The scroll is then ``ops.grid_scroll_store``, in the same place: a
+    tile that scrolls out and is not all unknown goes into the store -- free slots first, then the slot written longest
+    ago -- and a tile that scrolls in comes back from it bit for bit, so a sensor that returns to a mapped place finds
+    its map.  ``grid_store()`` returns the tiles restored, stored, evicted and dropped by the last step;
+    ``grid_scroll()`` returns the shift as before; ``reset()`` empties the store.  The store is part of the stage's
+    warm-up snapshot, so the first captured step holds a second copy of it (batch x slots x 8 KiB) while it warms up.
+
     ``track_map`` (needs ``tracks`` and ``grid_map``; works with ``person_motion`` and every ``method`` that argument
     accepts, and with ``flow_model`` plus ``det(scan, pose=...)``): None, or a dict of ``occ_thresh`` (17), ``free_pct``
     (50), ``occ_pct`` (50), ``min_points`` (20), ``min_scans`` (3), ``travel`` (0.5 m) and ``cap`` (4096) of
@@ -269,7 +282,7 @@ class StreamingDetector:
     def __init__(self, model, num_pts=450, batch=1, angle_inc=None, cutout_kwargs=None, graph=True, device="cuda",
                  nms_min_dist=None, flow_model=None, cls_thresh=0.5, ego_motion=None, tracks=None, person_motion=None,
                  grid_map=None, grid_match=None, grid_scroll=None, track_map=None, grid_cast=None,
-                 novel_segments=None, merge_detections=None, grid_refine=None):
+                 novel_segments=None, merge_detections=None, grid_refine=None, grid_store=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StreamingDetector needs the GPU (no CPU path)")
         self._refuse_float16(model)
@@ -303,7 +316,7 @@ class StreamingDetector:
         # without tracks carries no data attribute named after them, tests/test_tracks_gpu.py holds it to that)
         self._flow_model = self._ego_kw = self._match_kw = self._key_kw = self._pm_kw = self._filter_kw = None
         self._gm_kw = self._sg_kw = self._gs_kw = self._tm_kw = self._gc_kw = self._ns_kw = self._mg_kw = None
-        self._gr_kw = None
+        self._gr_kw = self._st_kw = None
         if person_motion is not None:
             if flow_model is not None:
                 raise ValueError("person_motion stands in for the per-person flow: give flow_model or person_motion")
@@ -332,6 +345,8 @@ class StreamingDetector:
                 raise ValueError("grid_refine with a flow_model is not built: flow_trans is not corrected")
         if grid_scroll is not None and grid_map is None:
             raise ValueError("grid_scroll scrolls the grid of grid_map: give both")
+        if grid_store is not None and grid_scroll is None:
+            raise ValueError("grid_store keeps what grid_scroll moves out of the grid: give both")
         if grid_cast is not None and grid_map is None:
             raise ValueError("grid_cast walks the grid of grid_map: give both")
         if novel_segments is not None:
@@ -412,7 +427,16 @@ class StreamingDetector:
             ops.grid_scroll_margin(*shape, self._gs_kw["margin"])
             self._gs_state = ops.grid_scroll_state(self.B, *shape, dev)
             self._gs_out = ops.grid_scroll_buffers(self.B, dev)
-            stages.append(Stage(self._grid_scroll_stage, (self._gs_state.base, self._gs_state.offset)))
+            if grid_store is None:
+                stages.append(Stage(self._grid_scroll_stage, (self._gs_state.base, self._gs_state.offset)))
+            else:
+                # the same entry of the table, the storing launch: the store's persistent fields join the snapshot
+                self._st_kw = stage_settings("grid_store", grid_store)
+                self._st_state = ops.grid_store_state(self.B, *shape, self._st_kw["slots"], dev)
+                self._st_out = ops.grid_scroll_store_buffers(self.B, dev)
+                self._gs_out = ops.GridScroll(self._st_out.shift, self._st_out.scrolled)
+                stages.append(Stage(self._grid_scroll_stage, (self._gs_state.base, self._gs_state.offset) +
+                                    tuple(getattr(self._st_state, k) for k in ops.GridStoreState.persistent)))
         if grid_match is not None:
             # directly behind the pose launch: every later stage reads the corrected terms.  The grid is allocated
             # below, so the stage reads self._gm_state when it runs; it advances nothing but the pose, which is in
@@ -713,6 +737,10 @@ class StreamingDetector:
 
     # Behind the pose launch and in front of every stage that reads cells: the grid follows the sensor.
     def _grid_scroll_stage(self, first):
+        if self._st_kw is not None:
+            ops.grid_scroll_store(self._pose_trans, self._gm_state, self._gs_state, self._st_state,
+                                  res=self._gm_kw["res"], out=self._st_out, **self._gs_kw)
+            return
         ops.grid_scroll(self._pose_trans, self._gm_state, self._gs_state, res=self._gm_kw["res"], out=self._gs_out,
                         **self._gs_kw)
 
@@ -724,6 +752,8 @@ class StreamingDetector:
         self._gm_state.origin.copy_(torch.from_numpy(origin))
         if self._gs_kw is not None:
             ops.grid_scroll_reset(self._gs_state, self._gm_state)
+        if self._st_kw is not None:
+            ops.grid_store_reset(self._st_state)
 
     def _keep_scan(self, first):
         self._prev_scan.copy_(self._scan.view(self.B, self.N, 1))
@@ -904,6 +934,19 @@ class StreamingDetector:
              "offset": self._gs_state.offset.cpu().numpy(), "origin": self._gm_state.origin.cpu().numpy()}
         return [{"shift": h["shift"][b], "scrolled": bool(h["scrolled"][b]), "offset": h["offset"][b],
                  "origin": h["origin"][b]} for b in range(self.B)], o
+
+    def grid_store(self):
+        """-> (list with one dict per sensor of the last step's traffic with the tile store: restored, stored, evicted
+        and dropped tiles of this step, held = the tiles in the store now, clock = the scrolls since the reset;  the
+        device-resident ``ops.GridScrollStore``, valid until the next call).  Needs ``grid_store`` and one scan.
+        Synchronises."""
+        if self._st_kw is None or self._seen < 1:
+            raise RuntimeError("construct the detector with grid_store and feed it a scan first")
+        o = self._st_out
+        counts, clock = o.counts.cpu().numpy(), self._st_state.clock.cpu().numpy()
+        held = (self._st_state.store_stamp != 0).sum(dim=1).cpu().numpy()
+        return [dict(zip(("restored", "stored", "evicted", "dropped"), (int(v) for v in counts[b])), held=int(held[b]),
+                     clock=int(clock[b])) for b in range(self.B)], o
 
     def grid_cast(self):
         """-> the last step's ``ops.GridCast``, device-resident and valid until the next call: per beam exp_range,

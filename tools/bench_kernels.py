@@ -1,5 +1,5 @@
 """Per-kernel timing on the GPU box (events on torch's current stream, which is the
-stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [refine] [gridscroll] [cast] [novel] [merge] ..."""
+stream the C-ABI launches on).  Usage: python tools/bench_kernels.py [cutout] [attn] [corr] [person] [grid] [gridmatch] [refine] [gridscroll] [gridstore] [cast] [novel] [merge] ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -234,7 +234,7 @@ if "person" in which:
             % (M, ms_tm[M], ms_t[M], (tm_state[M].ev_scans > 0).sum().item() / B,
                tm_out[M].class_count.sum(dim=0).tolist()) for M in tracks))
 
-if which & {"grid", "gridmatch", "refine", "gridscroll", "cast", "novel", "merge"}:
+if which & {"grid", "gridmatch", "refine", "gridscroll", "gridstore", "cast", "novel", "merge"}:
     # N12: the occupancy grid map, 450 beams into 512 x 512 cells of 0.1 m per sensor, for 1024, 8 and 1 sensors, next
     # to person_motion on the same scans, NMS results and pose (alternating, three repeats of 50 launches).  The same
     # scan every call, with lo / hi at the int16 limits so that no cell saturates inside the run and every launch
@@ -375,6 +375,56 @@ if which & {"grid", "gridmatch", "refine", "gridscroll", "cast", "novel", "merge
                       "sensor, %.0f GB/s against the bound of 4*H*W*2 bytes per sensor) next to "
                       "grid_map_update %.3f ms" % (B, H, W, RES, ms_0, ms_1, ms_1 / B * 1e3, moved / ms_1 / 1e6, ms_g))
             del gs_state, gs_scroll
+        if "gridstore" in which:
+            # N20 next to N14 on copies of the same grid with every unknown cell set to 1, so that every tile that
+            # leaves is stored: 64 slots per sensor, the same two cases and positions as gridscroll.  What the first
+            # scroll brings in is unknown and would take no slot on its way out, so it is set to 1 as well: from the
+            # second call on every scrolling call stores the 39 tiles that leave and restores the 39 that come back.
+            full = torch.where(gm_state.grid == 0, torch.ones_like(gm_state.grid), gm_state.grid)
+            at = lambda cx, cy: torch.tensor([(cx + 0.5) * RES, (cy + 0.5) * RES], dtype=torch.float64, device=dev)
+            middle, up, down = at(W // 2, H // 2), at(W - 64, H - 64), at(64, 64)
+            legs = {}
+            for name in ("grid_scroll", "grid_scroll_store"):
+                st = ops.GridMapState(full.clone(), gm_state.origin.clone())
+                sc = ops.grid_scroll_reset(ops.grid_scroll_state(B, H, W, dev), st)
+                if name == "grid_scroll":
+                    out = ops.grid_scroll_buffers(B, dev)
+                    call = lambda pos, st=st, sc=sc, out=out: ops.grid_scroll(st.origin + pos, st, sc, res=RES, out=out)
+                else:
+                    out, tiles = ops.grid_scroll_store_buffers(B, dev), ops.grid_store_state(B, H, W, 64, dev)
+                    call = lambda pos, st=st, sc=sc, out=out, tiles=tiles: ops.grid_scroll_store(
+                        st.origin + pos, st, sc, tiles, res=RES, out=out)
+                legs[name] = (call, out, [0], st)
+
+            def stays(name):
+                return lambda: legs[name][0](middle)
+
+            def scrolls(name):
+                def f():
+                    legs[name][2][0] ^= 1
+                    legs[name][0](up if legs[name][2][0] else down)
+                return f
+
+            for name in legs:
+                scrolls(name)()
+                legs[name][3].grid.masked_fill_(legs[name][3].grid == 0, 1)
+                scrolls(name)()
+                assert bool(legs[name][1].scrolled.all())
+            for rep in range(3):
+                ms = {(name, case): timeit(f(name), iters=50) for name in legs for case, f in (("stays", stays), ("scrolls", scrolls))}
+                counts = legs["grid_scroll_store"][1].counts
+                assert bool((counts[:, 2:] == 0).all()) and bool((counts[:, 0] == counts[:, 1]).all())
+                moved = int(counts[0, 1])
+                plain, stored = B * 4 * H * W * 2, B * (4 * H * W * 2 + 2 * 2 * moved * 8192)
+                print("gridstore B=%d %dx%d at %.2f m, 64 slots: no sensor scrolls %.3f ms (grid_scroll %.3f ms, +%.4f ms); every "
+                      "sensor scrolls, %d tiles stored and %d restored per sensor %.3f ms (%.2f us per sensor, %.0f GB/s against "
+                      "4*H*W*2 + 2*2*%d*8192 bytes per sensor) next to grid_scroll %.3f ms (%.0f GB/s against 4*H*W*2)"
+                      % (B, H, W, RES, ms["grid_scroll_store", "stays"], ms["grid_scroll", "stays"],
+                         ms["grid_scroll_store", "stays"] - ms["grid_scroll", "stays"], moved, int(counts[0, 0]),
+                         ms["grid_scroll_store", "scrolls"], ms["grid_scroll_store", "scrolls"] / B * 1e3,
+                         stored / ms["grid_scroll_store", "scrolls"] / 1e6, moved, ms["grid_scroll", "scrolls"],
+                         plain / ms["grid_scroll", "scrolls"] / 1e6))
+            del legs, full
         if "cast" in which:
             gc_state = ops.GridMapState(gm_state.grid.clone(), gm_state.origin.clone())
             gc_out = ops.grid_cast_buffers(B, N, dev)

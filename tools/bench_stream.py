@@ -1,5 +1,5 @@
 """Streaming DR-SPAAM step latency (one scan per call): eager launches vs one hipGraph replay.
-    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-refine] [--grid-scroll] [--grid-cast] [--novel] [--merge] [--track-map]
+    python tools/bench_stream.py [B ...] [--embed=library|hip] [--storage=float32|float16] [--nms] [--flow=prototype|diff] [--ego[=scan_match|keyframe|keyframe_map]] [--tracks] [--person-motion] [--grid] [--grid-match] [--grid-refine] [--grid-scroll] [--grid-store] [--grid-cast] [--novel] [--merge] [--track-map]
 --embed=hip: the gate's embedding on ops.attn_embed; --storage=float16 needs it (float16 cutout and template).
 --nms: the centre NMS inside the step; --flow (implies --nms): the per-person flow as the step's tail, with a fused
 Prototype or an elementwise scan difference as the flow model, a pose per scan.  --ego (with --flow): the replayed
@@ -25,6 +25,9 @@ scan-to-grid match.
 with grid_refine=dict() behind the pose launch, so one process gives those steps without and with the grid refine.
 --grid-scroll (with --grid): one more step in the same process, the keyframe step with grid_map=dict() and
 grid_scroll=dict() behind the keyframe launch, so one process gives the map step without and with the scrolling grid.
+--grid-store (with --grid --grid-scroll): one more step in the same process, that step with grid_store=dict() -- the
+scroll's entry of the stage table then calls the storing launch -- so one process gives the step without and with the
+tile store behind the window.
 --grid-cast (with --grid): one more step in the same process, the keyframe step with grid_map=dict() and
 grid_cast=dict() directly in front of the grid map, so one process gives the map step without and with the ray cast.
 --novel (with --grid; brings the --grid-cast step with it): one more step in the same process, that step with
@@ -62,6 +65,7 @@ GRID = "--grid" in sys.argv
 GRID_MATCH = "--grid-match" in sys.argv
 GRID_REFINE = "--grid-refine" in sys.argv
 GRID_SCROLL = "--grid-scroll" in sys.argv
+GRID_STORE = "--grid-store" in sys.argv
 GRID_CAST = "--grid-cast" in sys.argv
 NOVEL = "--novel" in sys.argv
 MERGE = "--merge" in sys.argv
@@ -112,6 +116,9 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             if GRID_SCROLL:
                 scrolling = mk(ego_motion=KEYFRAME, grid_map=dict(), grid_scroll=dict())
                 steps["keyframe + grid_map + grid_scroll"] = lambda t: scrolling(scans[:, t])
+            if GRID_SCROLL and GRID_STORE:
+                storing = mk(ego_motion=KEYFRAME, grid_map=dict(), grid_scroll=dict(), grid_store=dict())
+                steps["keyframe + grid_map + grid_scroll + grid_store"] = lambda t: storing(scans[:, t])
             if GRID_CAST or NOVEL:
                 casting = mk(ego_motion=KEYFRAME, grid_map=dict(), grid_cast=dict())
                 steps["keyframe + grid_map + grid_cast"] = lambda t: casting(scans[:, t])
@@ -219,6 +226,8 @@ for B in ([int(v) for v in sys.argv[1:]] or [1, 8]):
             moved_by, _ = scrolling.grid_scroll()
             print("   grid_scroll at the last scan: shift %s, offset %s" % ([m["shift"].tolist() for m in moved_by],
                                                                              [m["offset"].tolist() for m in moved_by]))
+        if GRID and GRID_SCROLL and GRID_STORE:
+            print("   grid_store at the last scan: %s" % storing.grid_store()[0])
         if GRID and (GRID_CAST or NOVEL):
             o = casting.grid_cast()
             print("   grid_cast at the last scan: points per class (none, map, novel, through, unknown) %s, cells read %s"
